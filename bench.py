@@ -2,6 +2,7 @@
 """joint_train step throughput on N MI355X (BASELINE.json metric), one process per GPU.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + what the last timed step computed: DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        # N > 1 without WORLD_SIZE in the environment: spawns the line above itself
@@ -452,7 +453,7 @@ def time_with_input(tr, batch, cmvn_d, dev, steps, world):
     # DataLoader workers' job in the reference and is done once here, outside the timed loop; every timed step pays what remains on
     # the training process: one H2D copy per feature stream + re2e_pack_pad on the copy stream, two batches ahead, event hand-off.
     staged = stage_batch(samples)
-    pf = DevicePrefetcher([staged] * (warm + steps), dev)      # its own copy stream: a fifth stream, see GPU_MAX_HW_QUEUES in main()
+    pf = DevicePrefetcher([staged] * (warm + steps), dev)      # its own copy stream, beside the step's
     it = iter(pf)
     for _ in range(warm):
         tr.step(next(it), 0.0, cmvn_d)
@@ -537,6 +538,39 @@ def make_stepper(cfg_id, opt, nets, batch, cmvn_d, dev):
     raise SystemExit('bench: --config must be 2, 3, 4 or 5 (config 1 is the CPU plumbing case of the tests)')
 
 
+DUMP_SAMPLE = 1 << 21        # elements kept of a larger output (8 MB as float32): the few outputs of a step stay under 64 MB together
+
+
+def dump_outputs(path, out, tr, nets, optimizers):
+    """--dump-outputs: what the last timed step computed, as ``path/<name>.npy`` -- every meter the step returned (``train/loss`` ->
+    ``train_loss.npy``), the trainer's ``last`` tensors (``enhance_out``, ``enhance_feat``) and the parameters the step updated, one flat
+    array per network in ``named_parameters`` order (``params_enh``, ``params_asr``, ``params_gan``).  float64 stays float64, anything
+    else is written as float32.  An output of more than DUMP_SAMPLE elements is written as DUMP_SAMPLE of its flattened elements at
+    sorted indices drawn from a fixed seed: the same elements for every run and build at the same shape."""
+    import numpy as np
+    arrays = {k.replace('/', '_'): v for k, v in out.items()}
+    arrays.update(getattr(tr, 'last', {}))
+    trained = {id(p) for o in optimizers for p in o.params}
+    for name, m in zip(('enh', 'fbank', 'asr', 'gan'), nets):
+        ps = [p.detach().reshape(-1) for p in m.parameters() if id(p) in trained] if m is not None else []
+        if ps:
+            arrays['params_' + name] = torch.cat(ps)
+    host = {}
+    for name, v in arrays.items():
+        t = v.detach() if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(1234)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        host[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    assert total <= 64 << 20, 'bench: --dump-outputs would write %d bytes' % total
+    os.makedirs(path, exist_ok=True)
+    for name, a in sorted(host.items()):
+        np.save(os.path.join(path, name + '.npy'), a)
+    log('dumped %d outputs of the last timed step (%.1f MB) to %s' % (len(host), total / 2 ** 20, path))
+
+
 def time_other_config(cfg_id, dev, steps=10, warmup=3):
     """One of the other BASELINE configurations (2: asr_train, 3: enhance_gan_train, 5: joint_train on long utterances) in THIS process:
     fresh networks, its own synthetic batch and CMVN, ``warmup`` untimed + ``steps`` timed steps.  N = 1 only."""
@@ -598,13 +632,12 @@ def main():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-input-side', action='store_true', help='skip the second timed loop that feeds HOST batches through the device prefetcher')
     ap.add_argument('--no-other-configs', action='store_true', help='skip the 5-step runs of configurations 2, 3 and 5 (N = 1, --config 4 only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (rank 0) as DIR/<name>.npy, see dump_outputs()')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
 
-    # The step runs on three streams besides the default one; the input-side loop adds a copy stream.  A process gets four hardware
-    # queues by default and a fifth stream is multiplexed onto an occupied one (it serialises against it: 65 -> 386 ms per step
-    # measured with the prefetcher's stream): ask for eight BEFORE the runtime initialises (no effect on the resident-batch loop:
-    # 64.70 against 64.68 ms).
-    os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(a.gpus, sys.argv[1:]))
 
@@ -685,6 +718,8 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                 # before the untimed steps below move the weights on
+        dump_outputs(a.dump_outputs, out, tr, (enh, fb, asr, gan), optimizers)
     comm = None
     if world > 1:
         # ONE more, untimed step with an event timeline of its gradient all-reduces: when each was issued and when the step could

@@ -46,5 +46,7 @@ def test_rank_process_does_not_spawn_again(monkeypatch):
     monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '2'])
     from robust_e2e_gan_amd import dist as rdist
     monkeypatch.setattr(rdist, 'init_from_env', lambda: (0, 2, 0))
+    import torch
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)     # a machine with a GPU too: stop at the check, not run a rank
     with pytest.raises(AssertionError, match='needs a GPU'):   # gets as far as the GPU check (none here), without spawning
         bench.main()

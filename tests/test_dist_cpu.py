@@ -10,8 +10,15 @@ class _Opt:
         self.grad = g
 
 
-def _worker(rank, world, port, q):
+def _cpu_rank(rank, world, port):
+    """Environment of a spawned CPU rank.  The ranks stay CPU processes over gloo on a machine with a GPU as well: with a device visible
+    dist.init_from_env takes nccl and device LOCAL_RANK, and a one-GPU machine has no device 1."""
+    torch.cuda.is_available = lambda: False
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+
+
+def _worker(rank, world, port, q):
+    _cpu_rank(rank, world, port)
     from robust_e2e_gan_amd import dist as rdist
     r, w, _ = rdist.init_from_env()
     assert (r, w) == (rank, world)
@@ -65,7 +72,7 @@ def _dp_worker(rank, world, port, q, golden):
     """the data-parallel result is the MEAN of the per-shard gradients, and the clip norm is taken on the
     reduced gradients.  Each rank runs the oracle's joint step on its utterance shard (r::N of the length-sorted batch),
     puts the gradients into the product's flat buffers (optim.FlatOptimizer) and exchanges them with dist.GradSync."""
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    _cpu_rank(rank, world, port)
     import numpy as np
     from oracle import joint as oj
     from robust_e2e_gan_amd import dist as rdist
@@ -136,7 +143,7 @@ def test_dp_is_mean_of_shard_gradients_world2():
 
 
 def _sync_rows_worker(rank, world, port, q):
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    _cpu_rank(rank, world, port)
     from robust_e2e_gan_amd import dist as rdist
     from robust_e2e_gan_amd import lib, ops
     rdist.init_from_env()

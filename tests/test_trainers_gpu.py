@@ -304,12 +304,12 @@ def test_blstmp_frame_subsampling(golden_dir):
               ['enc.enc1.bilstm0.weight_ih_l0', 'enc.enc1.bt1.weight', 'enc.enc1.bilstm2.weight_hh_l0_reverse', 'dec.output.weight', 'ctc.ctc_lo.weight'])
 
 
-def test_blstmp_maxpooling_subsampling(golden_dir):
+def test_blstmp_maxpooling_subsampling(golden_dir, tmp_path):
     import numpy as _np
     fx = _fx(golden_dir, 'n4_tiny.npz')
     fx2 = {('mp.p.' + k[len('sub.p.'):] if k.startswith('sub.p.') else k): v for k, v in fx.items()}
-    _np.savez('/tmp/n4_mp.npz', **fx2)
-    _e2e_case('/tmp', 'mp.', dict(etype='blstmp', elayers=3, subsample='1_2_2_1_1', subsample_type='maxpooling'),
+    _np.savez(str(tmp_path / 'n4_mp.npz'), **fx2)
+    _e2e_case(str(tmp_path), 'mp.', dict(etype='blstmp', elayers=3, subsample='1_2_2_1_1', subsample_type='maxpooling'),
               ['enc.enc1.bilstm0.weight_ih_l0', 'enc.enc1.bt1.weight', 'enc.enc1.bilstm2.weight_hh_l0_reverse', 'dec.output.weight', 'ctc.ctc_lo.weight'],
               name='n4_mp.npz')
 
