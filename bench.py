@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 10 --warmup 3
     python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + what the last timed step computed: DIR/<name>.npy
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full               # + every measurement and check beside the headline (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...        # N > 1 without WORLD_SIZE in the environment: spawns the line above itself
@@ -14,7 +15,13 @@ on one synthetic AISHELL-shaped batch (config 4: B=32 per GPU, T=800, F=257->80,
 that is already resident in HBM.  Weak scaling: every rank processes its own B=32 batch and the
 flat gradient buffers are averaged with RCCL.  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: metric, value, unit, ms_per_step, the
+configuration, the final losses, and the gates that need no run of their own (no persistent-kernel aborts, finite losses and, with
+N > 1, identical replicas).  Everything that needs runs of its own is --full only, where the --no-* options can drop parts of it:
+the extra untimed steps (FLOP meter -> step_executed_*, the all-reduce timeline -> comm_timeline with N > 1), the second timed loop fed
+from host memory (input_side) and the objects below.  The warm-up steps are the same with and without --full.
+
+Extra objects on the line (--full):
   roofline     -- the dominant convolution (3x3 at the VGG conv1_2 shape of this workload, as the step launches it:
                   fused Winograd + ReLU + pool) timed live with HIP events on the launch stream; achieved / frac = EXECUTED
                   matrix-core FLOPs against the fp32-MFMA peak (<= 1), the direct-form figure is direct_equivalent_tflops
@@ -628,6 +635,9 @@ def main():
     ap.add_argument('--batch', type=int, default=None)
     ap.add_argument('--frames', type=int, default=None)
     ap.add_argument('--labels', type=int, default=None)
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement and check beside the headline: extra untimed steps, input_side, rooflines, other '
+                         'configurations, cpu_baseline and parity (the --no-* options below drop parts of it)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-input-side', action='store_true', help='skip the second timed loop that feeds HOST batches through the device prefetcher')
@@ -688,12 +698,14 @@ def main():
     cmvn_d = cmvn.to(dev)
     step, tr, optimizers = make_stepper(a.config, opt, (enh, fb, asr, gan), batch, cmvn_d, dev)
     joint = a.config in (4, 5)
-    want_cpu = world == 1 and joint and not a.no_cpu_baseline
+    parity_run = world == 1 and joint and not a.no_cpu_baseline     # runs in which --full has a parity gate
+    want_cpu = a.full and parity_run
     sd0 = [{k: v.detach().cpu().clone() for k, v in m.state_dict().items()} for m in (enh, asr, gan)] if want_cpu else None
 
     log('warm-up (%d steps)' % a.warmup)
     gpu_first, host_ms = None, None
-    nwarm = max(a.warmup, 1 if want_cpu else 0)        # the parity gate needs the first step un-timed
+    # the parity gate needs the first step un-timed; a plain run warms up the same way, so both time the same steps
+    nwarm = max(a.warmup, 1 if parity_run else 0)
     for i in range(nwarm):
         torch.cuda.synchronize()
         h0 = time.perf_counter()
@@ -721,7 +733,7 @@ def main():
     if a.dump_outputs and rank == 0:                 # before the untimed steps below move the weights on
         dump_outputs(a.dump_outputs, out, tr, (enh, fb, asr, gan), optimizers)
     comm = None
-    if world > 1:
+    if world > 1 and a.full:
         # ONE more, untimed step with an event timeline of its gradient all-reduces: when each was issued and when the step could
         # continue behind it, in ms from the step's start, on every rank -- the first multi-GPU run shows exposed communication directly
         rdist.COMM_TIMING = True
@@ -757,11 +769,13 @@ def main():
         raise SystemExit('bench: non-finite losses after the timed region: %r' % (losses,))
     # ONE more, untimed step under the host-side FLOP meter (robust_e2e_gan_amd/flops.py): the matrix-core FLOPs the launches of a step really
     # execute -- valid rows of the ragged batch, row-limited Winograd heights, Winograd-reduced products -- and their direct-form equivalent
-    from robust_e2e_gan_amd import flops as rflops
-    with rflops.meter() as fmeter:
-        step()
-    torch.cuda.synchronize()
-    exe_flop, direct_flop = rflops.totals(fmeter)
+    fmeter = None
+    if a.full:
+        from robust_e2e_gan_amd import flops as rflops
+        with rflops.meter() as fmeter:
+            step()
+        torch.cuda.synchronize()
+        exe_flop, direct_flop = rflops.totals(fmeter)
     replicas_identical = None
     rccl_ranks = torch.distributed.get_world_size() if (world > 1 and torch.distributed.is_initialized()) else 1
     if world > 1:
@@ -775,7 +789,7 @@ def main():
         if not replicas_identical:
             raise SystemExit('bench: replicas differ after %d data-parallel steps: %r vs %r' % (a.steps, lo.tolist(), hi.tolist()))
     input_side = None
-    if joint and not a.no_input_side:
+    if a.full and joint and not a.no_input_side:
         input_side = time_with_input(tr, batch, cmvn_d, dev, a.steps, world)
     if rank != 0:
         return
@@ -796,24 +810,30 @@ def main():
         # whole-step fraction of the fp32-MFMA roofline: utterances/s x SURVEY 8(d) FLOP per utterance / (N x 157.3 TFLOP/s); the FLOP
         # count holds for the configuration's own (T, L) whatever the batch, so it is given for weak and strong scaling alike
         'step_mfma_frac': round(value * FLOP_PER_UTT[a.config] / (world * PEAK_FP32_MFMA_TFLOPS * 1e12), 4) if (T, L) == CONFIG_SHAPES[a.config][1:] else None,
-        # ... and the honest twin of it (round 6): the FLOP count above prices every padded row of the (B, Tmax) box, while the step no longer
-        # computes them (products over the valid rows, row-limited VGG launches).  step_executed_* = matrix-core FLOPs of the launches one step
-        # of THIS rank really made (host-side meter over lib.call, robust_e2e_gan_amd/flops.py: valid rows, row-limited heights, Winograd-reduced
-        # products) over the measured step time; flop_per_utt_valid_rows = the direct-form equivalent of those launches per utterance (what
-        # SURVEY 8(d)'s figure becomes when padding is not counted); step_valid_rows_frac = utt/s x that / peak
-        'step_executed_tflop': round(exe_flop / 1e12, 4),
-        'step_executed_tflops': round(exe_flop / (dt / a.steps) / 1e12, 2),
-        'step_executed_frac': round(exe_flop / (dt / a.steps) / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
-        'flop_per_utt_valid_rows': round(direct_flop / max(local_b, 1) / 1e9, 2),
-        'flop_per_utt_valid_rows_unit': 'GFLOP (direct form, padded rows not counted; SURVEY 8(d) with padding: %.2f)' % (FLOP_PER_UTT[a.config] / 1e9),
-        'step_valid_rows_frac': round(direct_flop / (dt / a.steps) / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
-        'step_executed_by_entry_point_gflop': {k: round(v / 1e9, 1) for k, v in sorted(fmeter.items(), key=lambda kv: -kv[1]) if k != rflops.DIRECT},
+    }
+    if fmeter is not None:
+        line.update({
+            # ... and the honest twin of it (round 6): the FLOP count above prices every padded row of the (B, Tmax) box, while the step no longer
+            # computes them (products over the valid rows, row-limited VGG launches).  step_executed_* = matrix-core FLOPs of the launches one step
+            # of THIS rank really made (host-side meter over lib.call, robust_e2e_gan_amd/flops.py: valid rows, row-limited heights, Winograd-reduced
+            # products) over the measured step time; flop_per_utt_valid_rows = the direct-form equivalent of those launches per utterance (what
+            # SURVEY 8(d)'s figure becomes when padding is not counted); step_valid_rows_frac = utt/s x that / peak
+            'step_executed_tflop': round(exe_flop / 1e12, 4),
+            'step_executed_tflops': round(exe_flop / (dt / a.steps) / 1e12, 2),
+            'step_executed_frac': round(exe_flop / (dt / a.steps) / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
+            'flop_per_utt_valid_rows': round(direct_flop / max(local_b, 1) / 1e9, 2),
+            'flop_per_utt_valid_rows_unit': 'GFLOP (direct form, padded rows not counted; SURVEY 8(d) with padding: %.2f)' % (FLOP_PER_UTT[a.config] / 1e9),
+            'step_valid_rows_frac': round(direct_flop / (dt / a.steps) / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
+            'step_executed_by_entry_point_gflop': {k: round(v / 1e9, 1) for k, v in sorted(fmeter.items(), key=lambda kv: -kv[1]) if k != rflops.DIRECT},
+        })
+    line.update({
         'default_shape': default_shape,
         'final_losses': {k: round(v, 5) for k, v in losses.items()}, 'persistent_kernel_aborts': aborts,
         'rccl_ranks': rccl_ranks, 'replicas_identical': replicas_identical, 'self_spawned': os.environ.get('RE2E_BENCH_SPAWNED') == '1',
         'rank_ms_per_step': {'min': round(min(rank_ms), 3), 'max': round(max(rank_ms), 3)},
         'host_enqueue_ms_per_step': round(host_ms, 2) if host_ms is not None else None,
-    }
+        'full': a.full,
+    })
     if comm is not None:
         line['comm_timeline'] = {'what': 'one extra untimed step per rank: every gradient all-reduce with the time it was issued and the time the step '
                                          'could continue behind it (HIP events, ms from the step\'s start); ASR (largest) is issued after backward '
@@ -821,11 +841,11 @@ def main():
     if input_side is not None:
         input_side['delta_ms'] = round(input_side['ms_per_step'] - line['ms_per_step'], 3)
         line['input_side'] = input_side
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         line['roofline'] = conv_roofline(dev)
         line['roofline_engine'] = engine_roofline(dev)
         line['roofline_chain'] = chain_roofline(dev)
-    if world == 1 and a.config == 4 and default_shape and not a.no_other_configs:
+    if a.full and world == 1 and a.config == 4 and default_shape and not a.no_other_configs:
         # step_mfma_frac of the other configurations, measured by THIS run (5 timed steps each): `frac` = utt/s x SURVEY 8(d) FLOP / fp32-MFMA peak
         line['other_configs'] = {str(c): time_other_config(c, dev) for c in (2, 3, 5)}
         log('other configurations: %s' % {c: v['ms'] for c, v in line['other_configs'].items()})

@@ -59,7 +59,7 @@ def main(path, steps):
     import os, re
     m = re.match(r'(r\d+)_', os.path.basename(path))
     print('# HBM-bound kernels of one config-4 training step: achieved GB/s against 8 TB/s (%s)\n' % (m.group(1) if m else '?'))
-    print('Source: `%s` (rocprofv3 --kernel-trace --stats of `RE2E_NO_OVERLAP=1 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline`: ONE stream, so a kernel\'s '
+    print('Source: `%s` (rocprofv3 --kernel-trace --stats of `RE2E_NO_OVERLAP=1 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline`: ONE stream, so a kernel\'s '
           'duration is its own; %d steps in the run).  Bytes are ALGORITHMIC (each tensor the kernel has to touch, once), summed over the '
           'kernel\'s launches in one step; formulas in `tools/hbm_table.py`.  Peak 8.0 TB/s (MI355X_MICROARCH.md; 6.3 TB/s is what a float4 copy '
           'reaches).  Rows marked approx. mix several shapes whose exact launch mix was not separated.\n' % (path, steps))

@@ -2,7 +2,7 @@
 
 Run on the GPU box:
     RE2E_IGEMM_LOG=1 RE2E_NO_OVERLAP=1 rocprofv3 --kernel-trace --output-format csv -d OUT -- \
-        python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline 2> OUT/log.txt
+        python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-roofline 2> OUT/log.txt
     python3 tools/igemm_table.py OUT/log.txt OUT/*/*_kernel_trace.csv
 
 The k-th "[igemm]" log line is the k-th engine launch (igemm_kernel, gemm_nt2_kernel, the halo / Winograd kernels; single stream => launch

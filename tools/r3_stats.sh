@@ -1,7 +1,7 @@
 # overlapped kernel stats of the default step for a few kernels:  bash tools/r3_stats.sh "<name substrings separated by |>"
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3_stats; rm -rf $O; mkdir -p $O; cd $R
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -- python3 bench.py --no-cpu-baseline --no-roofline --no-input-side --steps 10 --warmup 3 > $O/out.json 2> $O/log.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -- python3 bench.py --full --no-cpu-baseline --no-roofline --no-input-side --steps 10 --warmup 3 > $O/out.json 2> $O/log.txt
 cp $O/p/*/*_kernel_stats.csv $O/kernel_stats.csv; rm -rf $O/p
 python3 - "$1" <<'PY'
 import csv, sys, json, os

@@ -6,7 +6,7 @@ TAG=$1; shift
 O=$R/gpurun_out/r4_trace_$TAG; rm -rf $O; mkdir -p $O
 cd $R
 for kv in "$@"; do export $kv; done
-rocprofv3 --kernel-trace --output-format rocpd -d $O/t -- python3 bench.py --no-cpu-baseline --no-roofline --no-input-side --no-other-configs --steps 3 --warmup 3 > $O/out.json 2> $O/log.txt
+rocprofv3 --kernel-trace --output-format rocpd -d $O/t -- python3 bench.py --full --no-cpu-baseline --no-roofline --no-input-side --no-other-configs --steps 3 --warmup 3 > $O/out.json 2> $O/log.txt
 DB=$(ls $O/t/*/*.db | head -1)
 python3 tools/trace_bins.py $DB 1 > $O/bins.txt 2>&1
 python3 tools/trace_list.py $DB 0 90 0 0 > $O/main_list.txt 2>&1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Whole-step counters of `RE2E_NO_OVERLAP=1 bench.py --steps 3 --no-cpu-baseline` (three separate rocprofv3 --pmc passes:
+"""Whole-step counters of `RE2E_NO_OVERLAP=1 bench.py --full --steps 3 --no-cpu-baseline` (three separate rocprofv3 --pmc passes:
 SQ_VALU_MFMA_BUSY_CYCLES + SQ_BUSY_CYCLES, FETCH_SIZE, WRITE_SIZE) summed per kernel and over the run.
 usage: python3 tools/step_pmc.py gpurun_out/r3_final > step_pmc.json"""
 import csv
@@ -40,7 +40,7 @@ for k in sq:
     rows.append({'kernel': k, 'launches': b[0], 'SQ_VALU_MFMA_BUSY_CYCLES': m[1], 'SQ_BUSY_CYCLES': b[1], 'mfma_over_busy': (m[1] / b[1]) if b[1] else None,
                  'FETCH_bytes_x2': fe.get(k, {}).get('FETCH_SIZE', [0, 0.0])[1] * 2048, 'WRITE_bytes': wr.get(k, {}).get('WRITE_SIZE', [0, 0.0])[1] * 1024})
 rows.sort(key=lambda r: -r['SQ_BUSY_CYCLES'])
-json.dump({'command': 'RE2E_NO_OVERLAP=1 rocprofv3 --kernel-trace --pmc <set> -- python3 bench.py --steps 3 --no-cpu-baseline ; three passes: '
+json.dump({'command': 'RE2E_NO_OVERLAP=1 rocprofv3 --kernel-trace --pmc <set> -- python3 bench.py --full --steps 3 --no-cpu-baseline ; three passes: '
                       '{SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES}, {FETCH_SIZE}, {WRITE_SIZE} (tools/final_evidence_r3.sh)',
            'scope': 'every kernel the process launched: CMVN passes, warm-up and the 3 timed steps (%d steps counted from the Adadelta launches); '
                     'ratios are over the whole run, per-step figures divide by that step count and so include the CMVN passes\' share' % steps,
