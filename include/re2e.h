@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 319
+#define RE2E_ABI_VERSION 320
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -479,6 +479,26 @@ int re2e_attloc_dpre(const float* pre, const float* conv_all, const float* dp_al
 /* d_enc[b,t,:] = beta*d_enc + sum_i w_all[i,b,t] * dc_all[i,b,:]  (w_all (L1,B,T), dc_all (L1,B,eprojs)) */
 int re2e_attloc_denc(const float* w_all, const float* dc_all, int L1, int B, int T, int eprojs, float* d_enc, float beta,
                      re2e_stream_t stream);
+
+/* ---- RNNLM shallow fusion at decode time (model/lm.py:125-146, e2e_decoder.py:270-285; csrc/rnnlm.hip) ----
+ * Few-row kernels: n = the live hypotheses of a beam-search position, 1 <= n <= 64; any widths (the loads are as wide as the
+ * operands' alignment allows).  None needs a workspace.
+ * nn.LSTMCell for n rows in one launch: gates = W_ih x + b_ih + W_hh h_prev + b_hh (w_ih (4H, I), w_hh (4H, H), gate order i, f, g, o),
+ * c_out = f * c_prev + i * g, h_out = o * tanh(c_out), all (n, H).  ids_dev == NULL: x is (n, I) with leading dimension ldx;
+ * otherwise x is an embedding table (n_embed, I; ldx) and row r reads x[ids_dev[r]] (an id outside the table gives a NaN row).
+ * h_prev / c_prev may be NULL (zeros).  h_out / c_out must not alias h_prev or x; c_out may alias c_prev. */
+int re2e_lm_lstm_cell(const float* x, long ldx, const int* ids_dev, int n_embed, int I, const float* w_ih, const float* w_hh,
+                      const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float* h_out,
+                      float* c_out, re2e_stream_t stream);
+/* logits (n, V) = h (n, H) w (V, H)^T + b */
+int re2e_lm_output(const float* h, const float* w, const float* b, int n, int V, int H, float* logits, re2e_stream_t stream);
+/* lsm (n, V) = log_softmax(logits) row-wise and, with att / comb (both or neither), comb = att + lm_weight * lsm in the same pass
+ * (product and sum rounded separately: e2e_decoder.py:272). */
+int re2e_lm_log_softmax_combine(const float* logits, int n, int V, const float* att, float lm_weight, float* lsm, float* comb,
+                                re2e_stream_t stream);
+/* local[k][j] += lm_weight * lm[k][cand_dev[k][j]], k < n, j < ncand (e2e_decoder.py:284-285 on re2e_ctc_prefix_score's outputs);
+ * a candidate outside [0, V) gives NaN. */
+int re2e_lm_add_cands(float* local, const float* lm, const int* cand_dev, int n, int ncand, int V, float lm_weight, re2e_stream_t stream);
 
 /* ---- K11 optimizer (joint_train.py:131-140,188-193; Appendix A.16) ------------------------ */
 /* stats[0]=||g||_2, stats[1]=clip coefficient (<=1), stats[2]=1 if finite else 0; from sumsq[0];

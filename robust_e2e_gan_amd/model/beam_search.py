@@ -14,7 +14,13 @@ LDS / registers, the combined local score); the hypotheses' CTC states never lea
 the (nh, V) attention scores plus a numpy recursion per hypothesis.  ``ctc_beam`` > 64 (ctc_weight == 1.0 scores all V
 labels upstream, e2e_decoder.py:233-234) takes its candidate list from a device-side stable sort of the attention scores
 (re2e_ctc_prefix_score_cands, one thread per candidate).  The host scorer below -- upstream's own numpy algorithm -- is kept as the
-tests' arbiter (HOST_CTC_SCORER)."""
+tests' arbiter (HOST_CTC_SCORER).
+
+RNNLM shallow fusion (e2e_decoder.py:270-272,284-285; model/lm.py here): the LM is fed the last label of every live hypothesis
+in one ``predict`` call per position, its four state tensors (nh, n_units) stay on the device and follow the survivors through the
+same ``parents`` gather as the decoder state.  Attention-only search ranks ``att + lm_weight * lm`` over all V labels; with CTC
+the candidates are chosen on the attention scores alone and ``lm_weight * lm[cand]`` is added to their local scores -- on the
+device-CTC path by re2e_lm_add_cands before the 3 x nh x ctc_beam copy, so the LM's (nh, V) rows never cross to the host there."""
 import numpy as np
 import torch
 
@@ -83,9 +89,10 @@ DEVICE_CTC_MAX_BEAM = 64        # re2e_ctc_prefix_score: one thread per candidat
 HOST_CTC_SCORER = False         # tests: upstream's numpy CTCPrefixScore on the host instead (the arbiter of the device scorers)
 
 
-def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None):
+def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=None):
     """``p``: reference-named decoder / attention Parameters; ``h``: (T, eprojs) encoder states of ONE utterance on the
-    GPU; ``lpz``: (T, V) CTC log posteriors (numpy) or None.  Returns the n-best list of {'yseq', 'score'}."""
+    GPU; ``lpz``: (T, V) CTC log posteriors (numpy) or None; ``rnnlm``: a model.lm.ClassifierWithState on the same device or None
+    (``recog_args.lm_weight`` is read only with one).  Returns the n-best list of {'yseq', 'score'}."""
     dev = h.device
     T, E = h.shape
     beam, penalty, ctc_weight = recog_args.beam_size, recog_args.penalty, recog_args.ctc_weight
@@ -97,6 +104,8 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None):
     V, Dd, D, A = out_w.shape[0], embed.shape[1], w_hh.shape[1], mlp_dec.shape[0]
     C, Fh = loc_conv.shape[0], (loc_conv.shape[3] - 1) // 2
     ldw = Dd + E
+    lm_weight = np.float32(recog_args.lm_weight) if rnnlm is not None else None
+    lm_state = None
     with torch.no_grad():
         pre1 = ops.linear(h.unsqueeze(0), p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'])   # (1,T,A)
         h_rep = h.unsqueeze(0).expand(beam, T, E).contiguous()          # every hypothesis attends over the same utterance
@@ -138,6 +147,10 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None):
             logits, lsm = torch.empty(nh, V, device=dev), torch.empty(nh, V, device=dev)
             ops.gemm(z_new, out_w, logits, nh, V, D, transb=True, bias=out_b)
             call('re2e_log_softmax_rows', logits.data_ptr(), nh, V, V, lsm.data_ptr())
+            if rnnlm is not None:
+                # att + lm_weight * lm over all V labels is what an attention-only search ranks (e2e_decoder.py:272,291); with CTC only the
+                # candidates' LM scores are used (:284-285)
+                lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if lpz is None else None, lm_weight)
             if dev_ctc:
                 last = host_to_dev(np.asarray([hp['yseq'][-1] for hp in hyps], np.int32), dev)
                 if max(len(hp['yseq']) - 1 for hp in hyps) > T:
@@ -162,9 +175,12 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None):
                     call('re2e_ctc_prefix_score_cands', lpz_d.data_ptr(), T, V, lsm.data_ptr(), nh, r_prev.data_ptr(), last.data_ptr(), olen.data_ptr(),
                          prev.data_ptr(), cand_d.data_ptr(), ctc_beam, float(np.float32(1.0 - ctc_weight)), float(np.float32(ctc_weight)), 0, eos,
                          out_d[0].data_ptr(), out_d[1].data_ptr(), r_new.data_ptr())
+                if rnnlm is not None:
+                    call('re2e_lm_add_cands', out_d[0].data_ptr(), lm_lp.data_ptr(), cand_d.data_ptr(), nh, ctc_beam, V, float(lm_weight))
                 cand_all, out_all = cand_d.cpu().numpy(), out_d.cpu().numpy()      # 3 x nh x ctc_beam numbers: this position's host round trip
             else:
-                local_all = lsm.cpu().numpy()                             # host scorer: the (nh, V) local scores cross once per position
+                local_all = (lsm if rnnlm is None or lpz is not None else att_lm).cpu().numpy()   # the (nh, V) local scores cross once per position
+                lm_all = lm_lp.cpu().numpy() if rnnlm is not None and lpz is not None else None   # host CTC scorer (the arbiter) only
             kept = []
             for k, hyp in enumerate(hyps):
                 if dev_ctc:
@@ -179,6 +195,8 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None):
                     _, cand = _topk(local_att, ctc_beam)
                     ctc_scores, ctc_states = ctc(hyp['yseq'], cand, hyp['ctc_state'])
                     local = (np.float32(1.0 - ctc_weight) * local_att[cand] + np.float32(ctc_weight) * (ctc_scores - hyp['ctc_score'])).astype(np.float32)
+                    if lm_all is not None:
+                        local = (local + lm_weight * lm_all[k][cand]).astype(np.float32)
                     best_scores, joint = _topk(local, beam)
                     best_ids = cand[joint]
                 else:
@@ -209,6 +227,8 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None):
                 break
             parents = host_to_dev(np.asarray([hp['parent'] for hp in hyps], np.int64), dev, torch.int64)
             z, c, a_prev = z_new.index_select(0, parents), c_new.index_select(0, parents), w_new.index_select(0, parents)
+            if lm_state is not None:
+                lm_state = {key: v.index_select(0, parents) for key, v in lm_state.items()}
             if dev_ctc:                                                   # the survivors' CTC states, gathered on the device
                 rows = host_to_dev(np.asarray([hp['ctc_row'] for hp in hyps], np.int64), dev, torch.int64)
                 r_prev = r_new.index_select(0, rows)

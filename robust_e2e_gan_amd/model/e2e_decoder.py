@@ -91,6 +91,7 @@ class Decoder(torch.nn.Module):
         self.output = LinearParams(dunits, odim)
         self.att = att
         self.sos, self.eos = sos, eos
+        self.fusion = fusion
         self.ignore_id = -1
         self.loss = None
         self.return_acc_tensor = False
@@ -106,15 +107,32 @@ class Decoder(torch.nn.Module):
         return loss, (acc if self.return_acc_tensor else float(acc))
 
     def recognize_beam(self, h, lpz, recog_args, char_list=None, rnnlm=None, fstlm=None):
-        """e2e_decoder.py:171-369 (no LM): n-best list of {'yseq', 'score'} for the encoder states ``h`` (T', eprojs) of one
-        utterance; ``lpz`` = CTC log posteriors (T', V) or None.  All live hypotheses are advanced as one GPU batch."""
-        if rnnlm is not None or fstlm is not None:
-            raise Re2eError('LM fusion at decode time is out of scope (SURVEY section 2)')
+        """e2e_decoder.py:171-369: n-best list of {'yseq', 'score'} for the encoder states ``h`` (T', eprojs) of one
+        utterance; ``lpz`` = CTC log posteriors (T', V) or None.  All live hypotheses are advanced as one GPU batch.
+        ``rnnlm``: a model.lm.ClassifierWithState over an RNNLM for shallow fusion with weight ``recog_args.lm_weight``
+        (:270-272,284-285); no other LM is supported."""
+        if fstlm is not None:
+            raise Re2eError('decode-time LM: only RNNLM shallow fusion (rnnlm=ClassifierWithState(RNNLM(...))) is supported; '
+                            'n-gram / FST LMs (fstlm) are out of scope')
+        if rnnlm is not None:
+            from .lm import RNNLM, ClassifierWithState
+            if self.fusion in ('deep_fusion', 'cold_fusion'):
+                raise Re2eError("decode-time LM: only shallow fusion is supported; fusion=%r changes the trained decoder and is out of scope"
+                                % self.fusion)
+            if not isinstance(rnnlm, ClassifierWithState) or not isinstance(rnnlm.predictor, RNNLM):
+                raise Re2eError('decode-time LM: only a ClassifierWithState over an RNNLM is supported (shallow fusion); word-level LMs '
+                                '(MultiLevelLM, LookAheadWordLM), the FS-RNN LM and %s are out of scope' % type(rnnlm).__name__)
+            if rnnlm.predictor.n_vocab != self.output.weight.shape[0]:
+                raise Re2eError('the RNNLM has %d labels, the decoder %d' % (rnnlm.predictor.n_vocab, self.output.weight.shape[0]))
+            if rnnlm.predictor.lo.weight.device != h.device:
+                raise Re2eError('the RNNLM is on %s, the encoder states on %s' % (rnnlm.predictor.lo.weight.device, h.device))
+            if rnnlm.training or rnnlm.predictor.training:
+                raise Re2eError('the RNNLM must be in evaluation mode (rnnlm.eval())')
         from .beam_search import recognize_beam
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
         p.update({'att.' + k: v for k, v in self.att.named_parameters()})
         lp = lpz.detach().cpu().numpy() if isinstance(lpz, torch.Tensor) else lpz
-        return recognize_beam(p, h, lp, recog_args, self.eos, lpz_dev=lpz if isinstance(lpz, torch.Tensor) and lpz.is_cuda else None)
+        return recognize_beam(p, h, lp, recog_args, self.eos, lpz_dev=lpz if isinstance(lpz, torch.Tensor) and lpz.is_cuda else None, rnnlm=rnnlm)
 
     def calculate_all_attentions(self, hpad, hlen, ys):
         """e2e_decoder.py:371-461 -- attention weights (B, Lmax+1, T').  NB the reference's pass is GREEDY: for i > 0 it

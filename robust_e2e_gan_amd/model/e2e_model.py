@@ -43,7 +43,8 @@ class E2E(ModelBase):
             logging.error('Error: need to specify an appropriate attention archtecture')
             sys.exit()
         if getattr(args, 'fusion', '') in ('deep_fusion', 'cold_fusion'):
-            raise Re2eError('LM fusion is decode-time only and out of scope (SURVEY section 2, row 15)')
+            raise Re2eError('deep / cold fusion change the trained decoder and are out of scope (SURVEY section 2, row 15); shallow fusion: '
+                            'recognize(..., rnnlm=ClassifierWithState(RNNLM(...)))')
         self.dec = Decoder(args.eprojs, odim, args.dlayers, args.dunits, self.sos, self.eos, self.att, self.verbose, self.char_list,
                            labeldist, args.lsm_weight)
         self.init_like_chainer()
