@@ -5,6 +5,7 @@
 order of operations (Appendix A.12-14): freeze toggling, clip on the ASR net only, NaN guard
 gating both G optimizers, D clipped separately.  Every rank runs it on its own utterance shard;
 gradients are averaged by dist.GradSync (RCCL) before clipping."""
+import collections
 import copy
 import logging
 import math
@@ -22,6 +23,11 @@ from .model.gan_model import CORAL, GANLoss, replay_running_stats
 from .optim import FlatOptimizer
 
 _LOSS_KIND = {'L2': lib.LOSS_L2, 'L1': lib.LOSS_L1, 'smooth_L1': lib.LOSS_SMOOTH_L1}
+
+# What one step's phases hand on (``JointTrainer._step``).  _Forward.clean_branch / d_real: None unless they ran on the side stream;
+# _DFake: the G-step's D(fake) graph, its loss term, the BatchNorm statistics and layers ``_d_step`` needs to walk it again.
+_Forward = collections.namedtuple('_Forward', 'enhance_out enhance_feat clean_feat clean_branch d_real')
+_DFake = collections.namedtuple('_DFake', 'd_fake gan_loss stats bn_layers')
 
 
 class stepwise_kernels(object):
@@ -108,50 +114,15 @@ class JointTrainer(object):
         # run the D passes on a side HIP stream under the latency-bound recurrent chains (RE2E_NO_OVERLAP=1: profiling)
         self.overlap_dstep = os.environ.get('RE2E_NO_OVERLAP', '0') != '1'
         self.marks = [] if os.environ.get('RE2E_TIMELINE') else None
-        # the D-step's D(fake) forward equals the G-step's (same input, same weights): keep that graph and walk it twice
-        self.early_dreal = lib.exp_env('RE2E_NO_EARLY_DREAL', '0') != '1'     # D-step real half under the enhancer's forward chain
-        self.reuse_dfake = lib.exp_env('RE2E_NO_DFAKE_REUSE', '0') != '1' 
-        self.side_stream = self.wgrad_stream = None
+        # The step runs on its OWN high-priority stream, never on the legacy default stream (which synchronises implicitly with blocking
+        # streams: 91 -> 140 ms); the launch-per-step chains gain from the priority (91.4 vs 92.4 ms; the device's range is (0, -1): there is
+        # no lower priority to give the fillers).  side / wgrad: the filler streams.  ONE set per process: see lib.step_streams.
+        # NB: no further streams.  A process gets 4 hardware queues by default; a fifth stream (default + main + side + wgrad + one more) is
+        # multiplexed onto an occupied queue and serialises against it (measured with a dedicated D-step stream: 91 -> 155 ms/step).  The
+        # schedule variants that were measured and rejected: DESIGN.md section 5 and Appendix A.
+        self.main_stream = self.side_stream = self.wgrad_stream = None
         if torch.cuda.is_available():
-            # filler streams: optionally restricted to a subset of the CUs (RE2E_FILLER_CUS, default all) so that the
-            # chains on the main stream always find idle CUs
-            # MI355X sweeps (ms/step).  With launch-per-step recurrences: 128: 112.5, 160: 103.1, 192: 99.6, 224: 98.0, 256: 99.5.
-            # With the persistent recurrences: 192: 90.6, 208: 91.2, 224: 89.0, 240: 90.1, 256 (no mask): 88.2 -- resident
-            # chains no longer need CUs kept free for their launches, so the fillers get the whole chip.
-            ncu = int(lib.exp_env('RE2E_FILLER_CUS', '256'))
-            dev = next(enhance_model.parameters()).device
-            if 0 < ncu < 256:
-                self.side_stream = lib.cu_masked_stream(ncu, 256, dev)
-                self.wgrad_stream = lib.cu_masked_stream(ncu, 256, dev)
-            shared = lib.step_streams(dev, int(lib.exp_env('RE2E_MAIN_PRIORITY', '-1')))       # ONE set per process: see lib.step_streams
-            if self.side_stream is None:
-                self.side_stream, self.wgrad_stream = shared[1], shared[2]
-            else:
-                # both run beside the resident recurrences of the main stream: 4-wave engine tiles there (re2e_stream_role)
-                lib.set_stream_role(self.side_stream, True)
-                lib.set_stream_role(self.wgrad_stream, True)
-            # NB: no further streams.  A process gets 4 hardware queues by default; a fifth stream (default + main + side
-            # + wgrad + one more) is multiplexed onto an occupied queue and serialises against it (measured with a
-            # dedicated D-step stream: 91 -> 155 ms/step).  Measured and rejected as well: running the D-step's
-            # forward/backward early, under the ASR forward (+2.3 ms/step: it slows the encoder chain more than it
-            # relieves the backward) -- and again with the persistent recurrences, only the FAKE half, started exactly when the
-            # encoder's chain starts: ASR forward +3.9 ms, enhancer backward -2.7 ms, step 88.9 -> 91.0 ms; holding the G-step's
-            # backward through D until the decoder's backward chain is done (decoder backward -1.9 ms, BLSTMP backward +1.6 ms:
-            # within the noise of the step); the FAKE half of the D-step between two backward calls cut at the encoder output,
-            # i.e. under the BLSTMP's backward recurrences (75.25 -> 75.6 ms); a dedicated stream for the recurrent sequences masked to the 32 CUs the fillers leave
-            # alone (GPU_MAX_HW_QUEUES=8): the chains are no faster there (16.9 vs 18 ms for the enhancer forward under the
-            # D(real) filler -- the slowdown under load is not CU sharing) and 256-workgroup sequences do not fit 32 CUs.
-        self.main_stream = None
-        if torch.cuda.is_available():
-            # The step runs on its OWN stream, never on the legacy default stream (which synchronises implicitly with
-            # the blocking CU-masked filler streams: 91 -> 140 ms).  It is a high-priority stream (RE2E_MAIN_PRIORITY,
-            # default -1; the device's range is (0, -1): there is no lower priority to give the fillers): the launch-per-step chains gain from it (91.4 vs 92.4 ms).  A fifth, normal-priority stream for
-            # the persistent sequences (GPU_MAX_HW_QUEUES=8) changed nothing: what slows a resident chain beside the
-            # fillers is two of its workgroups sharing a CU (tools/bench_fill_under_chain.py), not the queue it came from.
-            try:
-                self.main_stream = lib.step_streams(next(enhance_model.parameters()).device, int(lib.exp_env('RE2E_MAIN_PRIORITY', '-1')))[0]
-            except Exception:
-                self.main_stream = None
+            self.main_stream, self.side_stream, self.wgrad_stream = lib.step_streams(next(enhance_model.parameters()).device)
 
     def step(self, data, sche_samp_rate, enhance_cmvn):
         """One training iteration (joint_train.py:157-213).  Returns a dict of DEVICE scalars (call
@@ -160,8 +131,12 @@ class JointTrainer(object):
         With overlap enabled the critical path (recurrent chains, decoder) runs on a HIGH-priority stream and the
         filler work (clean-branch convs, discriminator passes, weight gradients) on normal-priority streams, so
         that the short dependent launches of the chains are dispatched ahead of queued bulk kernels."""
-        try:
-            if not (self.overlap_dstep and self.main_stream is not None):
+        overlap = self.overlap_dstep
+        # the stream routing is this step's: ops used outside it (validation, other trainers, tests) stay on ONE stream
+        # (sync_bn: for runs that shard ONE global batch over the ranks)
+        with ops.routing(wgrad=self.wgrad_stream if overlap else None, aux=self.side_stream if overlap else None, marks=self.marks, multi=overlap,
+                         sync_bn=bool(getattr(self.opt, 'sync_bn', False)) and rdist.world_size() > 1):
+            if not (overlap and self.main_stream is not None):
                 return self._step(data, sche_samp_rate, enhance_cmvn)
             caller = torch.cuda.current_stream()
             self.main_stream.wait_stream(caller)
@@ -169,10 +144,6 @@ class JointTrainer(object):
                 out = self._step(data, sche_samp_rate, enhance_cmvn)
             caller.wait_stream(self.main_stream)
             return out
-        finally:
-            # the stream routing is this step's: ops used outside it (validation, other trainers, tests) stay on ONE stream
-            ops.MULTI_STREAM, ops.WGRAD_STREAM, ops.AUX_STREAM, ops.MARKS = False, None, None, None
-            ops.SYNC_BN = False
 
     def _mark(self, label):
         """RE2E_TIMELINE=1: remember (label, host time, event on the current stream) -- ``timeline()`` prints how far the
@@ -181,6 +152,11 @@ class JointTrainer(object):
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
             self.marks.append((label, time.perf_counter(), ev))
+
+    def _mark_on(self, stream, label):
+        if self.marks is not None:
+            with torch.cuda.stream(stream):
+                self._mark(label)
 
     def timeline(self):
         torch.cuda.synchronize()
@@ -191,208 +167,215 @@ class JointTrainer(object):
         return rows
 
     def _step(self, data, sche_samp_rate, enhance_cmvn):
+        """The phases of a step in the order they are enqueued, and what passes between them.  That host-side order IS the schedule
+        (DESIGN.md section 5): every launch, event and stream switch inside a phase method keeps its place relative to all the others."""
         opt = self.opt
         self._mark('start')
-        ops.MARKS = self.marks
         clean_inputs, mix_inputs, mix_log_inputs, targets, input_sizes, target_sizes = data[2], data[4], data[5], data[7], data[8], data[9]
-        overlap = self.overlap_dstep
-        ops.MULTI_STREAM = bool(overlap)
-        ops.SYNC_BN = bool(getattr(opt, 'sync_bn', False)) and rdist.world_size() > 1     # ONE global batch sharded over the ranks
-        ops.WGRAD_STREAM = self.wgrad_stream if overlap else None
-        ops.AUX_STREAM = self.side_stream if (overlap and lib.exp_env('RE2E_CTC_MAIN') != '1') else None
-        main = torch.cuda.current_stream()
         hold = self._hold_factor()
-        clean_branch, d_real_part = None, None
-        if overlap and getattr(self.asr_model, 'etype', '').startswith('vgg'):
-            # the clean branch (fbank -> CMVN -> VGG conv stack) does not depend on the enhancer: enqueue it on the side
-            # stream first so that it fills the CUs the enhancer's 1600-launch recurrent chain leaves idle
-            side = self.side_stream
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                with torch.no_grad():
-                    clean_feat = self.feat_model(clean_inputs)
-                ev_cf = torch.cuda.Event()
-                ev_cf.record()
-                clean_branch = self.asr_model.encode_clean(clean_feat, enhance_cmvn, input_sizes)
-            self._mark('clean branch enqueued (side)')
-            enhance_out = self.enhance_model(mix_inputs, mix_log_inputs, input_sizes)
-            self._mark('enhancer fwd')
-            if self.isGAN and self.reuse_dfake and self.early_dreal:
-                # D-step, real half (joint_train.py:198-201): needs only clean_feat and D's current weights, so it goes
-                # under the enhancer's forward chain instead of under the (already saturated) backward chain.  Enqueued
-                # AFTER the enhancer: its ~2.5 ms of host launches must not delay the start of that chain.
-                with torch.cuda.stream(side):
-                    d_real_part = self._d_real(clean_feat, enhance_cmvn, hold)
-            ops.mark_grad(enhance_out, 'enhance_out (fbank bwd done)')
-            enhance_feat = self.feat_model(enhance_out)
-            ops.mark_grad(enhance_feat, 'enhance_feat (VGG, D, L1 bwd done)')
-            main.wait_event(ev_cf)
-            clean_feat.record_stream(main)
+        fwd = self._enhancer_forward(clean_inputs, mix_inputs, mix_log_inputs, input_sizes, enhance_cmvn, hold)
+        enhance_loss = opt.enhance_loss_lambda * ops.mean_loss(fwd.enhance_feat, fwd.clean_feat, 0.0, _LOSS_KIND[opt.enhance_loss_type])
+        d_fwd = self._gstep_d_forward(fwd.enhance_feat, enhance_cmvn) if self.isGAN else None
+        self._mark('fbank + G-step D fwd enqueued (side)')
+        loss, out, asr_meters = self._asr_forward_and_loss(fwd, d_fwd, enhance_loss, targets, input_sizes, target_sizes, sche_samp_rate,
+                                                           enhance_cmvn, hold)
+        self.enhance_optimizer.zero_grad()
+        self.asr_optimizer.zero_grad()
+        sync = GradSync()
+        armed = fwd.clean_branch is None       # with the clean branch on the side stream the ASR gradients are complete only
+        if armed:                              # after that stream has been joined, so the early all-reduce hook is not used
+            # the ASR weight-gradient kernels run on the wgrad stream (and the CTC branch on the aux stream) when the step is
+            # multi-stream: the hook issues the collective from the wgrad stream, behind events of the other two
+            sync.arm(fwd.enhance_feat, self.asr_optimizer, issue_stream=ops.WGRAD_STREAM, also_wait=[ops.AUX_STREAM])
+        if self.isGAN and self.overlap_dstep:
+            loss_D, armed = self._backward_two_phase(loss, fwd, d_fwd, enhance_cmvn, hold, sync, armed)
         else:
+            loss_D = self._backward_single(loss, fwd)
+        grad_norm, loss_D, aborts = self._update(fwd, d_fwd, loss_D, enhance_cmvn, hold, sync, armed)
+        if self.isGAN:
+            out['train/loss_D'] = loss_D.detach()
+        out.update(asr_meters)
+        out.update({'grad_norm': grad_norm.clone(),      # a copy: the optimizer's stats buffer is rewritten by the next step (NaN when the gate refused)
+                    'aborts': aborts.clone()})           # give-ups of persistent kernels since the last acknowledgement, counted at the end of this step
+        self.last = dict(enhance_out=fwd.enhance_out, enhance_feat=fwd.enhance_feat)
+        self._mark('optimizers')
+        return out
+
+    def _enhancer_forward(self, clean_inputs, mix_inputs, mix_log_inputs, input_sizes, enhance_cmvn, hold):
+        """Enhancer -> fbank on the current (main) stream.  With overlap and a VGG encoder the clean branch and, GAN, the early real half of the
+        D-step go on the side stream, under the enhancer's recurrent chain."""
+        if not (self.overlap_dstep and getattr(self.asr_model, 'etype', '').startswith('vgg')):
             enhance_out = self.enhance_model(mix_inputs, mix_log_inputs, input_sizes)
             enhance_feat = self.feat_model(enhance_out)
             with torch.no_grad():
                 clean_feat = self.feat_model(clean_inputs)
-        enhance_loss = opt.enhance_loss_lambda * ops.mean_loss(enhance_feat, clean_feat, 0.0, _LOSS_KIND[opt.enhance_loss_type])
-        out = {}
-        gan_loss = None
-        overlap = self.isGAN and self.overlap_dstep
+            return _Forward(enhance_out, enhance_feat, clean_feat, None, None)
+        # the clean branch (fbank -> CMVN -> VGG conv stack) does not depend on the enhancer: enqueue it on the side
+        # stream first so that it fills the CUs the enhancer's 1600-launch recurrent chain leaves idle
+        main, side = torch.cuda.current_stream(), self.side_stream
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            with torch.no_grad():
+                clean_feat = self.feat_model(clean_inputs)
+            ev_cf = torch.cuda.Event()
+            ev_cf.record()
+            clean_branch = self.asr_model.encode_clean(clean_feat, enhance_cmvn, input_sizes)
+        self._mark('clean branch enqueued (side)')
+        enhance_out = self.enhance_model(mix_inputs, mix_log_inputs, input_sizes)
+        self._mark('enhancer fwd')
+        d_real = None
         if self.isGAN:
-            # G-step discriminator pass (joint_train.py:175-182).  It depends only on enhance_feat, so with
-            # overlap it is enqueued on the side stream BEFORE the ASR forward and runs under it; autograd runs
-            # its backward on the same side stream.
-            reuse = self.reuse_dfake
-            # upstream freezes D here (:176); with ``reuse`` the graph is built with trainable parameters instead and the
-            # G-step backward is told not to produce their gradients (ops.FROZEN_PARAMS below) -- same arithmetic
-            set_requires_grad([self.gan_model], reuse)
-            fake_stats = [] if reuse else None
+            # D-step, real half (joint_train.py:198-201): needs only clean_feat and D's current weights, so it goes
+            # under the enhancer's forward chain instead of under the (already saturated) backward chain (46.2 against 49.9 ms per step,
+            # profiles/r06_ab_dstep_inline_wgrad.txt).  Enqueued AFTER the enhancer: its ~2.5 ms of host launches must not delay the
+            # start of that chain.
+            with torch.cuda.stream(side):
+                d_real = self._d_real(clean_feat, enhance_cmvn, hold)
+        ops.mark_grad(enhance_out, 'enhance_out (fbank bwd done)')
+        enhance_feat = self.feat_model(enhance_out)
+        ops.mark_grad(enhance_feat, 'enhance_feat (VGG, D, L1 bwd done)')
+        main.wait_event(ev_cf)
+        clean_feat.record_stream(main)
+        return _Forward(enhance_out, enhance_feat, clean_feat, clean_branch, d_real)
 
-            def d_fake_forward():
-                ops.BN_STATS_SINK = fake_stats
-                try:
-                    d = self.gan_model(enhance_feat, enhance_cmvn)
-                finally:
-                    ops.BN_STATS_SINK = None
-                return d, opt.gan_loss_lambda * self.criterionGAN(d, True)
-            if overlap:
-                self.side_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(self.side_stream):
-                    enhance_feat.record_stream(self.side_stream)
-                    d_fake, gan_loss = d_fake_forward()
-                    ops.mark_grad(d_fake, 'd_fake (side: G-step D bwd starts)')
-            else:
-                d_fake, gan_loss = d_fake_forward()
-            fake_bn_layers = list(self.gan_model._bn_layers_last)
-        self._mark('fbank + G-step D fwd enqueued (side)')
-        loss_ctc, loss_att, acc, clean_context, mix_context = self.asr_model(
-            clean_feat, enhance_feat, targets, input_sizes, target_sizes, sche_samp_rate, enhance_cmvn, clean_branch=clean_branch,
+    def _gstep_d_forward(self, enhance_feat, enhance_cmvn):
+        """G-step discriminator pass (joint_train.py:175-182), on the side stream with overlap."""
+        # It depends only on enhance_feat, so with overlap it is enqueued on the side stream BEFORE the ASR forward and runs under it;
+        # autograd runs its backward on the same side stream.  The D-step's D(fake) forward equals this one (same input, same weights):
+        # the graph is kept and ``_d_step`` walks it a second time.
+        # upstream freezes D here (:176); the graph is built with trainable parameters instead and the G-step backward is told not to
+        # produce their gradients (ops.frozen_params) -- same arithmetic
+        set_requires_grad([self.gan_model], True)
+        stats = []
+
+        def forward():
+            with ops.bn_stats(stats):
+                d = self.gan_model(enhance_feat, enhance_cmvn)
+            return d, self.opt.gan_loss_lambda * self.criterionGAN(d, True)
+        if self.overlap_dstep:
+            self.side_stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(self.side_stream):
+                enhance_feat.record_stream(self.side_stream)
+                d_fake, gan_loss = forward()
+                ops.mark_grad(d_fake, 'd_fake (side: G-step D bwd starts)')
+        else:
+            d_fake, gan_loss = forward()
+        return _DFake(d_fake, gan_loss, stats, list(self.gan_model._bn_layers_last))
+
+    def _asr_forward_and_loss(self, fwd, d_fwd, enhance_loss, targets, input_sizes, target_sizes, sche_samp_rate, enhance_cmvn, hold):
+        """ASR forward, then the step's loss.  Returns the loss to differentiate, the meters known so far and the ASR meters that close the dict."""
+        opt = self.opt
+        loss_ctc, loss_att, acc, _, _ = self.asr_model(
+            fwd.clean_feat, fwd.enhance_feat, targets, input_sizes, target_sizes, sche_samp_rate, enhance_cmvn, clean_branch=fwd.clean_branch,
             context_loss=lambda cc, mc: opt.coral_loss_lambda * CORAL(cc, mc))      # on the filler stream, beside the decoder
         self._mark('ASR fwd')
         coral_loss = self.asr_model.last_context_loss
         asr_loss = opt.mtlalpha * loss_ctc.view(()) + (1 - opt.mtlalpha) * loss_att
         loss = asr_loss + enhance_loss + coral_loss
-        if self.isGAN:
-            if overlap:
-                torch.cuda.current_stream().wait_stream(self.side_stream)
-            loss = loss + gan_loss
-            out['train/gan_loss'] = opt.gan_loss_lambda * gan_loss.detach()
-        out['train/loss'] = loss.detach()
-        # x 1.0 (exact) -- or x NaN while a step that a persistent kernel gave up on has not been repeated yet: this step was enqueued before
-        # the host could know, it must apply nothing (on any replica: the NaN travels through the gradient average), see ``fit``
-        loss = loss * hold
-        self.enhance_optimizer.zero_grad()
-        self.asr_optimizer.zero_grad()
-        sync = GradSync()
-        armed = clean_branch is None       # with the clean branch on the side stream the ASR gradients are complete only
-        if armed:                          # after that stream has been joined, so the early all-reduce hook is not used
-            # the ASR weight-gradient kernels run on the wgrad stream (and the CTC branch on the aux stream) when the step is
-            # multi-stream: the hook issues the collective from the wgrad stream, behind events of the other two
-            sync.arm(enhance_feat, self.asr_optimizer, issue_stream=ops.WGRAD_STREAM, also_wait=[ops.AUX_STREAM])
-        if self.isGAN and self.overlap_dstep:
-            # Phase 1: backward of everything downstream of the enhancer (ASR, D, fbank) on the main stream.
-            main = torch.cuda.current_stream()
-            ev_fwd = torch.cuda.Event()
-            ev_fwd.record(main)
-            # The ASR parameters are listed as inputs so that autograd also runs the nodes that lead ONLY to them (the
-            # clean branch's conv stack reaches the loss through CORAL but not enhance_out and would be pruned);
-            # the fused ops accumulate parameter gradients themselves and hand None back for them.
-            asr_params = [p for p in self.asr_model.parameters() if p.requires_grad]
-            reuse = self.isGAN and self.reuse_dfake
-            ops.FROZEN_PARAMS = frozenset(id(p) for p in self.gan_model.parameters()) if reuse else frozenset()
-            cut = getattr(self.asr_model, 'clean_cut', None) if clean_branch is not None else None
-            self.asr_model.clean_cut = None
-            ev_cut, cut_fired = torch.cuda.Event(), []
-            if cut is not None:
-                def on_cut_grad(g):            # BLSTMP backward enqueued on main: d(loss)/d(leaf) is on its way
-                    ev_cut.record(main)
-                    cut_fired.append(True)
-                cut[1].register_hook(on_cut_grad)
-            try:
-                gs = torch.autograd.grad(loss, [enhance_out] + ([cut[1]] if cut else []) + asr_params, allow_unused=True, retain_graph=reuse)
-            finally:
-                ops.FROZEN_PARAMS = frozenset()
-            g_eo = gs[0]
-            self._mark('bwd phase 1 (ASR, D, fbank)')
-            ev_bwd1 = torch.cuda.Event()
-            ev_bwd1.record(main)
-            phase2_first = lib.exp_env('RE2E_PHASE2_FIRST', '0') == '1' and rdist.world_size() == 1     # experiment: enqueue order only
-            if phase2_first:
-                enhance_out.backward(g_eo)
-                self._mark('bwd phase 2 (enhancer)')
-            if cut is not None and gs[1] is not None:
-                # the clean branch's conv-stack backward (reached through CORAL and the shared BLSTMP): side stream, not
-                # joined into main before the enhancer's backward chain starts -- it runs under that chain
-                side = self.side_stream
-                side.wait_event(ev_cut if cut_fired else ev_bwd1)
-                with torch.cuda.stream(side):
-                    gs[1].record_stream(side)
-                    # (its weight gradients stay on the weight-gradient stream: inline here, like the D-step's, 46.0 -> 46.7 ms per step,
-                    #  profiles/r06_ab_dstep_inline_wgrad.txt)
-                    torch.autograd.backward([cut[0]], [gs[1]])
-            ev_side_bwd = torch.cuda.Event()          # clean-branch conv backward (ASR gradients) enqueued on the side stream
-            ev_side_bwd.record(self.side_stream)
-            if self.marks is not None:
-                for st_, nm_ in ((self.side_stream, 'side'), (self.wgrad_stream, 'wgrad')):
-                    with torch.cuda.stream(st_):
-                        self._mark('  %s stream: phase-1 work done' % nm_)
-            # D-step (joint_train.py:195-212) on a side stream: it only needs the forward results, so it fills
-            # the CUs that the latency-bound enhancer BLSTM backward (1600 dependent launches) leaves idle.
-            side = self.side_stream
-            side.wait_event(ev_fwd)
-            with torch.cuda.stream(side):
-                for t_ in (enhance_feat, clean_feat, enhance_cmvn):
-                    if isinstance(t_, torch.Tensor) and t_.is_cuda:
-                        t_.record_stream(side)
-                loss_D = self._d_step(clean_feat, enhance_feat, enhance_cmvn, d_fake=d_fake if reuse else None, fake_stats=fake_stats,
-                                      fake_bn=fake_bn_layers, real_part=d_real_part, hold=hold)
-            self._mark('D-step enqueued (side)')
-            if self.marks is not None:
-                with torch.cuda.stream(side):
-                    self._mark('  side stream: D-step done')
-            if not armed and rdist.world_size() > 1:
-                # Data parallel: every ASR gradient kernel has been enqueued (phase 1 on main, the clean-branch / CTC
-                # backward on side, the weight gradients on wgrad), so the 116 MB ASR all-reduce starts as soon as those
-                # finish and runs over xGMI UNDER the enhancer's backward chain instead of after it.  RCCL orders its
-                # stream behind the stream the collective is issued from: issue it from the wgrad stream, behind events
-                # of the other two.
-                ws = self.wgrad_stream
-                with torch.cuda.stream(ws):
-                    ws.wait_event(ev_bwd1)
-                    ws.wait_event(ev_side_bwd)
-                    work = rdist.allreduce_mean_(self.asr_optimizer.grad, async_op=True)
-                if work is not None:
-                    sync.pending.append(work)
-                armed = True
-            # Phase 2: the enhancer backward chain on the main stream.
-            if not phase2_first:
-                enhance_out.backward(g_eo)
-                self._mark('bwd phase 2 (enhancer)')
-            if self.marks is not None:
-                with torch.cuda.stream(self.wgrad_stream):
-                    self._mark('  wgrad stream: all weight gradients done')
-            torch.cuda.current_stream().wait_event(ev_side_bwd)
-        else:
-            reuse = self.isGAN and self.reuse_dfake
-            ops.FROZEN_PARAMS = frozenset(id(p) for p in self.gan_model.parameters()) if reuse else frozenset()
-            # ShareE2E cuts the graph at the clean conv stack's output whenever that stack ran on the side stream
-            # (clean_branch is not None), GAN or not: d(loss)/d(leaf) lands in the leaf's .grad and the conv-stack
-            # backward (reached through CORAL and the shared BLSTMP) is run here, on the side stream.
-            cut = getattr(self.asr_model, 'clean_cut', None) if clean_branch is not None else None
-            self.asr_model.clean_cut = None
-            try:
-                loss.backward(retain_graph=reuse)
-            finally:
-                ops.FROZEN_PARAMS = frozenset()
-            if cut is not None and cut[1].grad is not None:
-                side = self.side_stream
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    cut[1].grad.record_stream(side)
-                    torch.autograd.backward([cut[0]], [cut[1].grad])
-                cut[1].grad = None
-            loss_D = None
+        out = {}
+        if d_fwd is not None:
             if self.overlap_dstep:
                 torch.cuda.current_stream().wait_stream(self.side_stream)
+            loss = loss + d_fwd.gan_loss
+            out['train/gan_loss'] = opt.gan_loss_lambda * d_fwd.gan_loss.detach()
+        out['train/loss'] = loss.detach()
+        asr_meters = {'train/loss_ctc': loss_ctc.detach().view(()), 'train/acc': acc, 'train/loss_att': loss_att.detach(),
+                      'train/enhance_loss': enhance_loss.detach(), 'train/coral_loss': coral_loss.detach()}
+        # x 1.0 (exact) -- or x NaN while a step that a persistent kernel gave up on has not been repeated yet: this step was enqueued before
+        # the host could know, it must apply nothing (on any replica: the NaN travels through the gradient average), see ``fit``
+        return loss * hold, out, asr_meters
+
+    def _take_clean_cut(self, clean_branch):
+        """(graph tensor, leaf) of the cut ShareE2E makes at the clean conv stack's output when that stack ran on the side stream, else None."""
+        cut = getattr(self.asr_model, 'clean_cut', None) if clean_branch is not None else None
+        self.asr_model.clean_cut = None
+        return cut
+
+    def _clean_conv_backward(self, cut, grad, after):
+        """The clean conv stack's backward (reached through CORAL and the shared BLSTMP) from d(loss)/d(leaf), on the side stream behind ``after``."""
+        side = self.side_stream
+        side.wait_event(after)
+        with torch.cuda.stream(side):
+            grad.record_stream(side)
+            # (its weight gradients stay on the weight-gradient stream: inline here, like the D-step's, 46.0 -> 46.7 ms per step,
+            #  profiles/r06_ab_dstep_inline_wgrad.txt)
+            torch.autograd.backward([cut[0]], [grad])
+
+    def _backward_single(self, loss, fwd):
+        """One ``loss.backward()`` on the current stream: the single-stream step, and the overlap step without a discriminator."""
+        cut = self._take_clean_cut(fwd.clean_branch)
+        with ops.frozen_params(self.gan_model if self.isGAN else ()):
+            loss.backward(retain_graph=self.isGAN)
+        if cut is not None and cut[1].grad is not None:
+            self._clean_conv_backward(cut, cut[1].grad, torch.cuda.current_stream().record_event())
+            cut[1].grad = None
+        if self.overlap_dstep:
+            torch.cuda.current_stream().wait_stream(self.side_stream)
+        return None
+
+    def _backward_two_phase(self, loss, fwd, d_fwd, enhance_cmvn, hold, sync, armed):
+        """GAN with overlap.  Phase 1: backward of everything downstream of the enhancer (ASR, D, fbank) on the main stream; the clean branch's
+        conv-stack backward and the D-step follow on the side stream; phase 2: the enhancer's backward chain on the main stream, over them.
+        Returns (loss_D, whether the ASR gradient average has been issued)."""
+        main, side = torch.cuda.current_stream(), self.side_stream
+        ev_fwd = torch.cuda.Event()
+        ev_fwd.record(main)
+        # The ASR parameters are listed as inputs so that autograd also runs the nodes that lead ONLY to them (the
+        # clean branch's conv stack reaches the loss through CORAL but not enhance_out and would be pruned);
+        # the fused ops accumulate parameter gradients themselves and hand None back for them.
+        asr_params = [p for p in self.asr_model.parameters() if p.requires_grad]
+        cut = self._take_clean_cut(fwd.clean_branch)
+        ev_cut, cut_fired = torch.cuda.Event(), []
+        if cut is not None:
+            def on_cut_grad(g):            # BLSTMP backward enqueued on main: d(loss)/d(leaf) is on its way
+                ev_cut.record(main)
+                cut_fired.append(True)
+            cut[1].register_hook(on_cut_grad)
+        with ops.frozen_params(self.gan_model):
+            gs = torch.autograd.grad(loss, [fwd.enhance_out] + ([cut[1]] if cut else []) + asr_params, allow_unused=True, retain_graph=True)
+        self._mark('bwd phase 1 (ASR, D, fbank)')
+        ev_bwd1 = torch.cuda.Event()
+        ev_bwd1.record(main)
+        if cut is not None and gs[1] is not None:
+            # not joined into main before the enhancer's backward chain starts -- it runs under that chain
+            self._clean_conv_backward(cut, gs[1], ev_cut if cut_fired else ev_bwd1)
+        ev_side_bwd = torch.cuda.Event()          # clean-branch conv backward (ASR gradients) enqueued on the side stream
+        ev_side_bwd.record(side)
+        self._mark_on(side, '  side stream: phase-1 work done')
+        self._mark_on(self.wgrad_stream, '  wgrad stream: phase-1 work done')
+        # D-step (joint_train.py:195-212) on the side stream: it only needs the forward results, so it fills
+        # the CUs that the latency-bound enhancer BLSTM backward (1600 dependent launches) leaves idle.
+        side.wait_event(ev_fwd)
+        with torch.cuda.stream(side):
+            for t_ in (fwd.enhance_feat, fwd.clean_feat, enhance_cmvn):
+                if isinstance(t_, torch.Tensor) and t_.is_cuda:
+                    t_.record_stream(side)
+            loss_D = self._d_step(fwd.clean_feat, enhance_cmvn, d_fwd, fwd.d_real, hold)
+        self._mark('D-step enqueued (side)')
+        self._mark_on(side, '  side stream: D-step done')
+        if not armed and rdist.world_size() > 1:
+            # Data parallel: every ASR gradient kernel has been enqueued (phase 1 on main, the clean-branch / CTC
+            # backward on side, the weight gradients on wgrad), so the 116 MB ASR all-reduce starts as soon as those
+            # finish and runs over xGMI UNDER the enhancer's backward chain instead of after it.  RCCL orders its
+            # stream behind the stream the collective is issued from: issue it from the wgrad stream, behind events
+            # of the other two.
+            ws = self.wgrad_stream
+            with torch.cuda.stream(ws):
+                ws.wait_event(ev_bwd1)
+                ws.wait_event(ev_side_bwd)
+                work = rdist.allreduce_mean_(self.asr_optimizer.grad, async_op=True)
+            if work is not None:
+                sync.pending.append(work)
+            armed = True
+        fwd.enhance_out.backward(gs[0])
+        self._mark('bwd phase 2 (enhancer)')
+        self._mark_on(self.wgrad_stream, '  wgrad stream: all weight gradients done')
+        main.wait_event(ev_side_bwd)
+        return loss_D, armed
+
+    def _update(self, fwd, d_fwd, loss_D, enhance_cmvn, hold, sync, armed):
+        """Joins, gradient average, clip, step gate, optimizer updates (D's last).  Returns device scalars: ASR gradient norm, loss_D, give-ups."""
+        opt = self.opt
         if self.overlap_dstep:
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)      # deferred weight-gradient kernels
         sync.finish([self.enhance_optimizer] if armed else [self.asr_optimizer, self.enhance_optimizer])
@@ -408,8 +391,7 @@ class JointTrainer(object):
         nxt = holds[(self._step_no + 1) % 2]
         if self.isGAN:
             if loss_D is None:
-                loss_D = self._d_step(clean_feat, enhance_feat, enhance_cmvn, d_fake=d_fake if self.reuse_dfake else None,
-                                      fake_stats=fake_stats, fake_bn=fake_bn_layers, hold=hold)
+                loss_D = self._d_step(fwd.clean_feat, enhance_cmvn, d_fwd, None, hold)
             else:
                 torch.cuda.current_stream().wait_stream(self.side_stream)
             # D's update (:211) is the step's LAST kernel, behind the gate: a step that a persistent kernel gave up on is repeated as a
@@ -419,17 +401,10 @@ class JointTrainer(object):
             call_gate(None, None, self.gan_optimizer.stats.data_ptr(), self.asr_optimizer.stats.data_ptr() + 8 if dp else None, nxt.data_ptr(),
                       delta.data_ptr())
             self.gan_optimizer.step()
-            out['train/loss_D'] = loss_D.detach()
         else:
             call_gate(None, None, None, None, nxt.data_ptr(), delta.data_ptr())
         self._step_no += 1
-        out.update({'train/loss_ctc': loss_ctc.detach().view(()), 'train/acc': acc, 'train/loss_att': loss_att.detach(),
-                    'train/enhance_loss': enhance_loss.detach(), 'train/coral_loss': coral_loss.detach(),
-                    'grad_norm': grad_norm.clone(),      # a copy: the optimizer's stats buffer is rewritten by the next step (NaN when the gate refused)
-                    'aborts': delta.clone()})            # give-ups of persistent kernels since the last acknowledgement, counted at the end of this step
-        self.last = dict(enhance_out=enhance_out, enhance_feat=enhance_feat)
-        self._mark('optimizers')
-        return out
+        return grad_norm, loss_D, delta
 
     def _hold_factor(self):
         """The device scalar this step's losses are multiplied by (see ``_step``); first call: allocate the gate's state and acknowledge
@@ -480,69 +455,54 @@ class JointTrainer(object):
             raise lib.Re2eError('%s gave up with the launch-per-step kernels as well' % what)
         return res
 
-    def _d_real(self, clean_feat, enhance_cmvn, hold=None):
+    def _d_real(self, clean_feat, enhance_cmvn, hold):
         """Real half of the discriminator update on the CURRENT stream, ahead of the G-step: forward of D(clean) with the
         BatchNorm running-statistics update deferred (upstream applies it AFTER the G-step's D(fake) pass; ``_d_step``
         replays it there), then the backward of 0.5 * loss_D_real into D's (freshly zeroed) gradient buffers -- the same
-        terms, in the same accumulation order (real before fake), as the single backward of 0.5 * (real + fake)."""
+        terms, in the same accumulation order (real before fake), as the single backward of 0.5 * (real + fake).
+        Returns (loss_D_real, the deferred statistics, an event behind this half's kernels on the weight-gradient stream or None)."""
         set_requires_grad([self.gan_model], True)
         self.gan_optimizer.zero_grad()
         stats = []
-        ops.BN_STATS_SINK, ops.BN_DEFER_RUNNING = stats, True
-        try:
+        with ops.bn_stats(stats, defer=True):
             d_real = self.gan_model(clean_feat.detach(), enhance_cmvn)
-        finally:
-            ops.BN_STATS_SINK, ops.BN_DEFER_RUNNING = None, False
         loss_D_real = self.criterionGAN(d_real, True)
         gan_params = [p for p in self.gan_model.parameters() if p.requires_grad]
-        torch.autograd.grad(loss_D_real * 0.5 if hold is None else loss_D_real * 0.5 * hold, gan_params, allow_unused=True)
-        self._ev_dreal_wgrad = None
-        if ops.WGRAD_STREAM is not None:
-            self._ev_dreal_wgrad = torch.cuda.Event()          # behind this half's weight gradients on the weight-gradient stream
-            self._ev_dreal_wgrad.record(ops.WGRAD_STREAM)
-        return loss_D_real.detach(), stats
+        torch.autograd.grad(loss_D_real * 0.5 * hold, gan_params, allow_unused=True)
+        ev_wgrad = ops.WGRAD_STREAM.record_event() if ops.WGRAD_STREAM is not None else None
+        return loss_D_real.detach(), stats, ev_wgrad
 
-    def _d_step(self, clean_feat, enhance_feat, enhance_cmvn, d_fake=None, fake_stats=None, fake_bn=None, real_part=None, hold=None):
+    def _d_step(self, clean_feat, enhance_cmvn, d_fwd, real_part, hold):
         """Discriminator step (joint_train.py:195-212) on the CURRENT stream up to and including the clipping of its gradients; the update
-        itself (``gan_optimizer.step()``) is the caller's, behind the step's gate (``_step``).  ``d_fake``: D(enhance_feat) of the G-step
+        itself (``gan_optimizer.step()``) is the caller's, behind the step's gate (``_update``).  ``d_fwd``: D(enhance_feat) of the G-step
         (same input, same weights as upstream's second evaluation) -- its graph is walked again for the parameter
         gradients instead of recomputing the forward; the BatchNorm running statistics get the update that forward would
-        have applied (``fake_stats``), in upstream's order (after the D(real) pass)."""
-        opt = self.opt
+        have applied (``d_fwd.stats``), in upstream's order (after the D(real) pass).  ``real_part``: what ``_d_real`` returned when the real
+        half ran early, else None."""
         set_requires_grad([self.gan_model], True)
         # D's weight gradients of THIS pass run inline, on the stream of the D-step (the side stream), not behind the weight-gradient stream's
         # backlog (round 6): that stream was the last of the three to finish (46.6 ms of the step against 45.7 / 45.6), and the D-step's update
         # waited for all of it.  46.47 -> 45.99 ms per step (five interleaved rounds, profiles/r06_ab_dstep_inline_wgrad.txt).
-        # RE2E_DSTEP_WGRAD_STREAM=1 (experiments build): as before.
-        wg_keep = ops.WGRAD_STREAM
-        if lib.exp_env('RE2E_DSTEP_WGRAD_STREAM') != '1':
-            ops.WGRAD_STREAM = None
-        if real_part is not None:
-            loss_D_real, real_stats = real_part
-            replay_running_stats(real_stats)
-        else:
-            self.gan_optimizer.zero_grad()
-            loss_D_real = self.criterionGAN(self.gan_model(clean_feat.detach(), enhance_cmvn), True)
-        if d_fake is not None:
-            replay_running_stats(fake_stats)
-            for bn in fake_bn:
+        with ops.inline_weight_grads():
+            if real_part is not None:
+                loss_D_real, real_stats, ev_real_wgrad = real_part
+                replay_running_stats(real_stats)
+            else:
+                ev_real_wgrad = None
+                self.gan_optimizer.zero_grad()
+                loss_D_real = self.criterionGAN(self.gan_model(clean_feat.detach(), enhance_cmvn), True)
+            replay_running_stats(d_fwd.stats)
+            for bn in d_fwd.bn_layers:
                 bn.num_batches_tracked += 1
-            loss_D_fake = self.criterionGAN(d_fake, False)
-            loss_D = (loss_D_real + loss_D_fake) * 0.5
+            loss_D = (loss_D_real + self.criterionGAN(d_fwd.d_fake, False)) * 0.5
             gan_params = [p for p in self.gan_model.parameters() if p.requires_grad]
-            torch.autograd.grad(loss_D if hold is None else loss_D * hold, gan_params, allow_unused=True)      # the fused ops accumulate the gradients themselves
-        else:
-            loss_D_fake = self.criterionGAN(self.gan_model(enhance_feat.detach(), enhance_cmvn), False)
-            loss_D = (loss_D_real + loss_D_fake) * 0.5
-            (loss_D if hold is None else loss_D * hold).backward()
-        inline = ops.WGRAD_STREAM is None and wg_keep is not None
-        ops.WGRAD_STREAM = wg_keep
-        if inline and real_part is not None and getattr(self, '_ev_dreal_wgrad', None) is not None:
-            torch.cuda.current_stream().wait_event(self._ev_dreal_wgrad)      # only the early real half went through the weight-gradient stream
+            torch.autograd.grad(loss_D * hold, gan_params, allow_unused=True)      # the fused ops accumulate the gradients themselves
+        if ev_real_wgrad is not None:
+            torch.cuda.current_stream().wait_event(ev_real_wgrad)      # only the early real half went through the weight-gradient stream
         elif ops.WGRAD_STREAM is not None:
             torch.cuda.current_stream().wait_stream(ops.WGRAD_STREAM)
         GradSync().finish([self.gan_optimizer])
-        self.gan_optimizer.clip_grad_norm(opt.grad_clip)
+        self.gan_optimizer.clip_grad_norm(self.opt.grad_clip)
         return loss_D
 
     def validate(self, data, enhance_cmvn, want_attention=False):
@@ -556,9 +516,8 @@ class JointTrainer(object):
         modes = [m.training for m in nets]
         for m in nets:
             m.eval()
-        ops.MULTI_STREAM, ops.WGRAD_STREAM, ops.AUX_STREAM = False, None, None
         try:
-            with torch.no_grad():
+            with ops.routing(), torch.no_grad():          # ONE stream, whatever routing the caller runs under
                 enhance_out = self.enhance_model(mix_inputs, mix_log_inputs, input_sizes)
                 enhance_feat = self.feat_model(enhance_out)
                 clean_feat = self.feat_model(clean_inputs)

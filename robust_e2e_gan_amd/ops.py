@@ -6,6 +6,7 @@ accumulated by the kernels straight into ``param.grad`` (GEMM/conv epilogue ``be
 what lets the optimizer and the RCCL all-reduce work on one flat buffer per network
 (robust_e2e_gan_amd/optim.py, dist.py).
 """
+import contextlib
 import os
 import time
 import torch
@@ -182,7 +183,8 @@ def colsum_into(A2d, M, N, out, beta, lda=None):
     call('re2e_colsum', A2d.data_ptr(), M, N, lda if lda is not None else N, out.data_ptr(), float(beta), ws.data_ptr(), wsb)
 
 
-MULTI_STREAM = False     # set by JointTrainer when branches run on side streams
+# Ambient state the wrappers below read.  Nothing but the four context managers behind it writes it, so they nest and nothing leaks.
+MULTI_STREAM = False     # branches of the step run on side streams (``routing``)
 WGRAD_STREAM = None      # optional stream for weight-gradient kernels (see ``param_grads``)
 AUX_STREAM = None        # optional filler stream for independent branches inside a module (ShareE2E: the CTC branch)
 FROZEN_PARAMS = frozenset()   # id()s of parameters whose gradients must NOT be produced by the backward now running (the trainer
@@ -191,6 +193,42 @@ MARKS = None             # RE2E_TIMELINE: list of (label, host time, event) shar
 SYNC_BN = False          # data-parallel runs that shard ONE global batch: BatchNorm statistics over all ranks' rows (BnLreluFn)
 BN_DEFER_RUNNING = False  # with a sink: leave the running statistics alone in this forward (the owner replays the update later, in order)
 BN_STATS_SINK = None     # optional list: every BatchNorm forward appends (running_mean, running_var, mean, invstd, P, momentum, eps)
+
+
+@contextlib.contextmanager
+def _ambient(**values):
+    """Set the named attributes above for the body; the previous values come back on exit, also when the body raises."""
+    g = globals()
+    prev = {k: g[k] for k in values}
+    g.update(values)
+    try:
+        yield
+    finally:
+        g.update(prev)
+
+
+def routing(wgrad=None, aux=None, marks=None, sync_bn=False, multi=None):
+    """``with routing(...):`` the stream routing of one step.  ``multi`` (default: whether a stream was given): branches run on side streams
+    at all.  No arguments: everything on ONE stream."""
+    multi = (wgrad is not None or aux is not None) if multi is None else bool(multi)
+    return _ambient(MULTI_STREAM=multi, WGRAD_STREAM=wgrad, AUX_STREAM=aux, MARKS=marks, SYNC_BN=bool(sync_bn))
+
+
+def inline_weight_grads():
+    """``with inline_weight_grads():`` the weight-gradient kernels of the body stay on the stream their backward runs on."""
+    return _ambient(WGRAD_STREAM=None)
+
+
+def frozen_params(module_or_params):
+    """``with frozen_params(m):`` backward passes in the body produce no gradients for m's parameters (a module, or an iterable of parameters)."""
+    ps = module_or_params.parameters() if hasattr(module_or_params, 'parameters') else module_or_params
+    return _ambient(FROZEN_PARAMS=frozenset(id(p) for p in ps))
+
+
+def bn_stats(sink, defer=False):
+    """``with bn_stats(sink):`` every train-mode BatchNorm forward of the body appends its statistics to the list ``sink``; ``defer``: and leaves
+    its running statistics alone (the owner replays the update later, ``gan_model.replay_running_stats``)."""
+    return _ambient(BN_STATS_SINK=sink, BN_DEFER_RUNNING=bool(defer))
 
 
 def mark_grad(t, label):

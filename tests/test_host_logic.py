@@ -1,5 +1,6 @@
 """CPU-only tests of the host-side mirror of the reference interface: collate, options, loop
 utilities, state_dict contract."""
+import contextlib
 import os
 
 import numpy as np
@@ -269,3 +270,107 @@ def test_row_maps_and_vgg_row_limits_host_logic():
         assert i22 == o21 and i21 == (o12 + 1) // 2
         assert all(v % 16 == 0 or v in (400, 800) for v in (o12, i12, o21, o22))
     assert l12.out_tail == Tm - min(int(v) for v in l12.out) and vgg.row_limits([Tm] * 8, Tm, 'cpu') is None
+
+
+_AMBIENT = ('MULTI_STREAM', 'WGRAD_STREAM', 'AUX_STREAM', 'MARKS', 'SYNC_BN', 'FROZEN_PARAMS', 'BN_STATS_SINK', 'BN_DEFER_RUNNING')
+
+
+def _ambient_state():
+    from robust_e2e_gan_amd import ops
+    return {k: getattr(ops, k) for k in _AMBIENT}
+
+
+def test_ops_context_managers_restore_the_previous_state():
+    """ops.routing / inline_weight_grads / frozen_params / bn_stats: each sets its attributes for the body, leaves the others alone, and puts
+    the previous values back after a normal exit and after an exception."""
+    import pytest
+    from robust_e2e_gan_amd import ops
+    wg, aux, marks, sink = object(), object(), [], []
+    ps = [torch.nn.Parameter(torch.zeros(2)) for _ in range(3)]
+    lin = torch.nn.Linear(2, 2)
+    cases = [
+        (lambda: ops.routing(wgrad=wg, aux=aux, marks=marks, sync_bn=True),
+         dict(MULTI_STREAM=True, WGRAD_STREAM=wg, AUX_STREAM=aux, MARKS=marks, SYNC_BN=True)),
+        (lambda: ops.routing(wgrad=wg, multi=False), dict(MULTI_STREAM=False, WGRAD_STREAM=wg, AUX_STREAM=None, MARKS=None, SYNC_BN=False)),
+        (lambda: ops.routing(multi=True), dict(MULTI_STREAM=True, WGRAD_STREAM=None, AUX_STREAM=None, MARKS=None, SYNC_BN=False)),
+        (lambda: ops.routing(), dict(MULTI_STREAM=False, WGRAD_STREAM=None, AUX_STREAM=None, MARKS=None, SYNC_BN=False)),
+        (lambda: ops.inline_weight_grads(), dict(WGRAD_STREAM=None)),
+        (lambda: ops.frozen_params(ps), dict(FROZEN_PARAMS=frozenset(id(p) for p in ps))),
+        (lambda: ops.frozen_params(lin), dict(FROZEN_PARAMS=frozenset(id(p) for p in lin.parameters()))),
+        (lambda: ops.frozen_params(()), dict(FROZEN_PARAMS=frozenset())),
+        (lambda: ops.bn_stats(sink), dict(BN_STATS_SINK=sink, BN_DEFER_RUNNING=False)),
+        (lambda: ops.bn_stats(sink, defer=True), dict(BN_STATS_SINK=sink, BN_DEFER_RUNNING=True)),
+    ]
+    outer_wg, outer_sink, outer_frozen = object(), [], frozenset([1, 2])
+    # once from the defaults, once from a state in which every attribute differs from its default (what a nested use finds)
+    for outer in (False, True):
+        with contextlib.ExitStack() as stack:
+            if outer:
+                stack.enter_context(ops.routing(wgrad=outer_wg, aux=object(), marks=[], sync_bn=True))
+                stack.enter_context(ops.bn_stats(outer_sink, defer=True))
+                stack.enter_context(ops.frozen_params([torch.nn.Parameter(torch.zeros(1))]))
+            before = _ambient_state()
+            for make, want in cases:
+                with make():
+                    inside = _ambient_state()
+                    for k in _AMBIENT:
+                        exp = want[k] if k in want else before[k]
+                        assert inside[k] is exp or inside[k] == exp, (k, inside[k], exp)
+                assert all(v is before[k] for k, v in _ambient_state().items())
+                with pytest.raises(ZeroDivisionError):
+                    with make():
+                        assert _ambient_state() != before or want == {k: before[k] for k in want}
+                        1 / 0
+                assert all(v is before[k] for k, v in _ambient_state().items())
+    default = dict(MULTI_STREAM=False, WGRAD_STREAM=None, AUX_STREAM=None, MARKS=None, SYNC_BN=False, FROZEN_PARAMS=frozenset(),
+                   BN_STATS_SINK=None, BN_DEFER_RUNNING=False)
+    assert _ambient_state() == default
+
+
+def test_ops_routing_nests():
+    """A routing inside a routing (validation inside a caller's routing, a trainer's step inside another's) shows its own values in its body
+    and the outer ones again behind it -- also when the inner body raises; inline_weight_grads inside routing(wgrad=X) shows None inside and X
+    again afterwards."""
+    import pytest
+    from robust_e2e_gan_amd import ops
+    X, A, Y, marks = object(), object(), object(), []
+    with ops.routing(wgrad=X, aux=A, marks=marks, sync_bn=True):
+        with ops.routing(wgrad=Y):
+            assert (ops.MULTI_STREAM, ops.WGRAD_STREAM, ops.AUX_STREAM, ops.MARKS, ops.SYNC_BN) == (True, Y, None, None, False)
+            with ops.routing():
+                assert (ops.MULTI_STREAM, ops.WGRAD_STREAM, ops.AUX_STREAM, ops.MARKS, ops.SYNC_BN) == (False, None, None, None, False)
+            assert ops.WGRAD_STREAM is Y and ops.MULTI_STREAM is True
+        assert ops.MULTI_STREAM is True and ops.WGRAD_STREAM is X and ops.AUX_STREAM is A and ops.MARKS is marks and ops.SYNC_BN is True
+        with ops.inline_weight_grads():
+            assert ops.WGRAD_STREAM is None
+            assert ops.MULTI_STREAM is True and ops.AUX_STREAM is A and ops.MARKS is marks and ops.SYNC_BN is True      # nothing else moves
+        assert ops.WGRAD_STREAM is X
+        with pytest.raises(KeyError):
+            with ops.inline_weight_grads():
+                with ops.routing(wgrad=Y, aux=Y):
+                    raise KeyError('from the innermost body')
+        assert ops.MULTI_STREAM is True and ops.WGRAD_STREAM is X and ops.AUX_STREAM is A and ops.MARKS is marks and ops.SYNC_BN is True
+    assert (ops.MULTI_STREAM, ops.WGRAD_STREAM, ops.AUX_STREAM, ops.MARKS, ops.SYNC_BN) == (False, None, None, None, False)
+
+
+def test_ambient_state_has_one_writer():
+    """Nothing in the package or the tools outside ops.py assigns the ambient attributes, and the retired schedule switches are gone from
+    the code (their measurements live in DESIGN.md)."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    assign = re.compile(r'^\s*(?:[\w.]+\s*,\s*)*ops\.(%s)\b(?:\s*,\s*[\w.]+)*\s*[-+*/|&]?=(?!=)' % '|'.join(_AMBIENT))      # plain, tuple, augmented
+    retired = re.compile('RE2E_(FILLER_CUS|MAIN_PRIORITY|CTC_MAIN|PHASE2_FIRST|NO_EARLY_DREAL|NO_DFAKE_REUSE|DSTEP_WGRAD_STREAM)')
+    hits = []
+    for top in ('robust_e2e_gan_amd', 'tools'):
+        for d, _, files in os.walk(os.path.join(root, top)):
+            for f in files:
+                if not f.endswith(('.py', '.sh', '.hip', '.h', '.cpp')):
+                    continue
+                path = os.path.join(d, f)
+                for no, line in enumerate(open(path, errors='replace'), 1):
+                    code = line.split('#', 1)[0]
+                    if f.endswith('.py') and not path.endswith(os.path.join('robust_e2e_gan_amd', 'ops.py')) and assign.search(code):
+                        hits.append('%s:%d: %s' % (path, no, line.strip()))
+                    if retired.search(line):
+                        hits.append('%s:%d: %s' % (path, no, line.strip()))
+    assert not hits, '\n'.join(hits)

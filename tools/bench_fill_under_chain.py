@@ -73,16 +73,16 @@ def main(filler='conv', which='fwd'):
     def dreal():
         # dreal: forward + backward with the weight gradients on a second masked stream (as in the step); drealf: forward only;
         # dreal1: forward + backward on ONE stream
-        ops.MULTI_STREAM = filler == 'dreal'
-        ops.WGRAD_STREAM = wgrad_stream if filler == 'dreal' else None
         if filler == 'drealf':
             with torch.no_grad():
                 gan(feat, None)
             return
-        loss = crit(gan(feat, None), True)
-        torch.autograd.grad(loss * 0.5, gparams, allow_unused=True)
-        if ops.WGRAD_STREAM is not None:
-            torch.cuda.current_stream().wait_stream(ops.WGRAD_STREAM)
+        wg = wgrad_stream if filler == 'dreal' else None
+        with ops.routing(wgrad=wg, multi=filler == 'dreal'):
+            loss = crit(gan(feat, None), True)
+            torch.autograd.grad(loss * 0.5, gparams, allow_unused=True)
+        if wg is not None:
+            torch.cuda.current_stream().wait_stream(wg)
 
     def fill():
         if gan is not None:
