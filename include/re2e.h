@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 320
+#define RE2E_ABI_VERSION 321
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -347,6 +347,13 @@ int re2e_lstm_seq_fwd(float* xg_f, float* xg_r, const float* whh_f, const float*
 int re2e_lstm_seq_bwd(float* g_f, float* g_r, const float* whh_f, const float* whh_r, const float* dy,
                       const float* ybuf, const float* cbuf, float* dc_state, const int* lens_dev, int T, int B, int H,
                       float* dbias, void* workspace, size_t workspace_bytes, re2e_stream_t stream);
+/* Which kernel re2e_lstm_seq_fwd (backward == 0) / re2e_lstm_seq_bwd would run for this shape, as one line of space-separated key=value
+ * pairs in `out`; nothing is launched.  The same host functions make the choice for the two entry points above.
+ *   family=fwd2_persist|fwd2_step tiles=.. nj=..   family=fwd_persist waves=.. qn=..   family=fwd_step waves=..
+ *   family=bwd3 un=.. tpw=..   family=bwd_persist tpw=.. uw=..   family=bwd_step jt=..
+ * followed by grid=XxYxZ lds=<dynamic LDS bytes>.  cus > 0: plan for a chip of that many CUs (no device is touched); cus == 0: the
+ * current device's count.  The recurrent weights are assumed 16-byte aligned.  RE2E_EUNSUPPORTED when no kernel is built for H. */
+int re2e_lstm_plan(int T, int B, int H, int backward, int cus, char* out, size_t out_bytes);
 
 /* ---- K8 LSTMCell pointwise (decoder, e2e_decoder.py:131), embedding, cross-entropy -------- */
 /* gates [B,4H] pre-activation in -> activated out; c_prev [B,H] -> c_out, h_out */

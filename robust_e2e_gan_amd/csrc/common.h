@@ -44,7 +44,9 @@ bool re2e_stream_is_filler(hipStream_t stream);     // core.hip: re2e_stream_rol
 //   RE2E_IGEMM_LOG                                 one stderr line per engine call (tools/igemm_table.py), no effect on results
 //   RE2E_DEBUG_HOOKS = 1                           lets re2e_debug_force_abort / re2e_debug_occupy answer (tests/conftest.py sets it)
 // Everything else -- tile variants, occupancy probes, rejected forms kept for A/B measurements -- is compiled in only with
-// -DRE2E_EXPERIMENTS (make EXPERIMENTS=1 -> libre2e_hip_exp.so, used by tools/ through RE2E_LIB) and answers "unset" otherwise.
+// -DRE2E_EXPERIMENTS (make EXPERIMENTS=1 -> libre2e_hip_exp.so, used by tools/ through RE2E_LIB) and answers "unset" otherwise.  Of the
+// recurrences (lstm.hip) that is RE2E_LSTM_STAMPS (phase stamps), RE2E_LSTM_BWD3_UN (tools/lstm_stamps.py) and RE2E_LSTM_WAVES_FWD
+// (tools/bench_lstm.py); the switches of their rejected forms went with the forms.
 #ifdef RE2E_EXPERIMENTS
 static inline const char* exp_env(const char* name) { return getenv(name); }
 #else

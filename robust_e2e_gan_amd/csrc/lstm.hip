@@ -196,10 +196,11 @@ constexpr unsigned kSpinLimit = 1u << 24;
 // then one sweep, 16-byte stores -- in place of the granules: half the bytes through the fabric and the same rate alone at 64 workgroups (3.27
 // against 3.24 us per step at H = 256 / B = 32; 5.0 against 6.2 at H = 512 / B = 64, where lstm_fwd2 runs anyway), but the training step
 // loses 0.4 ms with it (56.3 against 55.9, two A/B rounds); consuming the k-groups in arrival order on top of it: 3.55-3.72 alone.)
-// UW = 2: a workgroup owns 16 hidden units (two 32-column gate tiles): it sweeps the recurrent state ONCE for both, runs two MFMA
-// chains on it, and 512 of its threads apply the cell.  Half as many workgroups sweep (the swept traffic through the fabric
-// halves) and the 512-wide layers' grid fits half of the chip, so it can reserve its CUs like the narrower layers do (the
-// launcher's 160 KB LDS request): what slows a chain beside the filler streams is sharing SIMDs with their MFMA streams.
+// (Rounds 2-6, measured and rejected, DESIGN.md Appendix A: 16 hidden units per workgroup -- UW = 2, one sweep of the recurrent state feeding two
+// MFMA chains -- at H = 512 and at H = 256, and 16 wavefronts x 4 k-groups at H = 512.  Only UW = 1 is instantiated.  The parameter and its
+// u loops stay in the source: written without them the compiler orders the LDS writes of the accumulator tile differently inside the step loop,
+// and the enhancer's forward chain, which this kernel is, read 3.30 against the parent's 3.24-3.25 us per step in two of three runs of
+// profiles/lstm_plan_ab.txt.  Kept as it is, the code object is instruction for instruction the measured one.)
 template <int WAVES, int QN, int UW>
 __global__ __launch_bounds__(WAVES * 64) void lstm_fwd_persist(float* xg_f, float* xg_r, const float* __restrict__ wfrag, float* ybuf,
                                                                float* cbuf, u64* hx_, unsigned* err, const int* __restrict__ lens,
@@ -361,21 +362,19 @@ __device__ __forceinline__ bool tags_are(const u32x4& v, unsigned want) {
   return (((v[0] & v[1] & v[2] & v[3]) ^ want) & kTagBit) == 0u && (((v[0] | v[1] | v[2] | v[3]) ^ want) & kTagBit) == 0u;
 }
 
-// TT (round 6): utterance tiles per workgroup.  TT = 2: ONE workgroup carries TWO independent 16-utterance tiles (same units, same W_hh registers,
-// own tags / parity buffers / cell state per tile) and alternates between them inside a step: publish tile A's h(t) -> poll, MFMA and cell of
-// tile B -> poll A, meant to fill the ~1-1.5 us a workgroup waits for its peers' h(t) (profiles/r04_chain_budget.md section 2) with the other
-// tile's ~0.8 us of work.  Per tile the instruction sequence is the TT = 1 one: bitwise-equal results.  Measured slower and not selected
-// (fwd2_config: why); experiments build only, RE2E_LSTM_FWD2_TT=2.
-template <int TILES, int NJ, bool PERSIST, int TT = 1>
+// (Round 6, measured and rejected, profiles/r06_chain_two_tiles.txt: TWO 16-utterance tiles per workgroup, one tile's poll / MFMA / cell filling the
+// wait for the other's h(t), so that B = 32 / H = 256 would run on 64 CUs.  Bitwise equal and 5.14 against 3.22 us per step: vmcnt retires in
+// order and counts stores, so the poll of tile B cannot return before the write-through publish of tile A and its output stores are
+// acknowledged (~0.7 us) -- the hand-off latency the interleave was to hide is paid once per TILE instead of once per step.)
+template <int TILES, int NJ, bool PERSIST>
 __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const float* __restrict__ whh_f, const float* __restrict__ whh_r,
                                                  float* ybuf, float* cbuf, unsigned* hx_, unsigned* err, const int* __restrict__ lens, int T,
-                                                 int B, int H, int s_arg, int mode) {
-  static_assert(TT == 1 || PERSIST, "two tiles per workgroup: the persistent form only");
+                                                 int B, int H, int s_arg) {
   constexpr int KS = 4;                                         // K quarters = waves
-  extern __shared__ __attribute__((aligned(16))) float lds2[];  // TT x part[2][TILES][KS][64] f32x4 | abort word
-  f32x4* part_all = reinterpret_cast<f32x4*>(lds2);
-  int* abortw = reinterpret_cast<int*>(lds2 + TT * 2 * TILES * KS * 64 * 4);
-  const int dir = blockIdx.z, MT = gridDim.y * TT, x = blockIdx.x;
+  extern __shared__ __attribute__((aligned(16))) float lds2[];  // part[2][TILES][KS][64] f32x4 | abort word
+  f32x4* part = reinterpret_cast<f32x4*>(lds2);
+  int* abortw = reinterpret_cast<int*>(lds2 + 2 * TILES * KS * 64 * 4);
+  const int dir = blockIdx.z, mt = blockIdx.y, MT = gridDim.y, x = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6, n = lane & 15, kk = lane >> 4;
   const int ft = ks < TILES ? ks : -1;                           // the tile this wave finishes (gates, cell, publish), if any
   float* xg = dir ? xg_r : xg_f;
@@ -397,51 +396,33 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
   const bool fin = ft >= 0;
   const int j = 4 * TILES * x + 4 * (fin ? ft : 0) + kk;                               // the unit whose cell this lane owns
   const int s0 = PERSIST ? 0 : s_arg, s1 = PERSIST ? T : s_arg + 1;
-  // ---- per utterance tile u of this workgroup ----
-  int b_[TT], ln_[TT];
-  bool ok_[TT];
-  unsigned rd_w_[TT], poll_w_[TT], wr_w_[TT];
-  float c_[TT], pre_[TT][4];
-  u32x4 ld_[TT][NJ];
+  const int grp = (dir * MT + mt) * H * 16;
+  const int b = 16 * mt + n;
+  const unsigned rd_w = (unsigned)(grp + ((4 * ks * NJ + kk) * 16 + n) * 4);          // + jj * 256 words
+  const unsigned poll_w = (unsigned)(grp + ((4 * ks * NJ + (lane < 4 * NJ ? lane : 0)) * 16) * 4);     // utterance 0 of piece lane of this quarter
+  const bool ok = fin && b < B;
+  const int ln = ok ? lens[b] : 0;
+  const unsigned wr_w = (unsigned)(grp + ((TILES * x + (fin ? ft : 0)) * 16 + n) * 4);
+  float c = 0.f, pre[4] = {0.f, 0.f, 0.f, 0.f};
+  if (ok) {
+    const int t0 = dir ? T - 1 - s0 : s0;
+    const float* gp = xg + ((long)t0 * B + b) * 4 * H + j;
 #pragma unroll
-  for (int u = 0; u < TT; ++u) {
-    const int mt = blockIdx.y * TT + u;
-    const int grp = (dir * MT + mt) * H * 16;
-    b_[u] = 16 * mt + n;
-    rd_w_[u] = (unsigned)(grp + ((4 * ks * NJ + kk) * 16 + n) * 4);          // + jj * 256 words
-    poll_w_[u] = (unsigned)(grp + ((4 * ks * NJ + (lane < 4 * NJ ? lane : 0)) * 16) * 4);     // utterance 0 of piece lane of this quarter
-    ok_[u] = fin && b_[u] < B;
-    ln_[u] = ok_[u] ? lens[b_[u]] : 0;
-    wr_w_[u] = (unsigned)(grp + ((TILES * x + (fin ? ft : 0)) * 16 + n) * 4);
-    c_[u] = 0.f;
+    for (int g = 0; g < 4; ++g) pre[g] = gp[g * H];
+    if (!PERSIST) c = cbuf[((long)(dir ? t0 + 2 : t0) * B + b) * H2 + dir * H + j];
+  }
+  u32x4 ld[NJ];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) pre_[u][g] = 0.f;
-    if (ok_[u]) {
-      const int t0 = dir ? T - 1 - s0 : s0;
-      const float* gp = xg + ((long)t0 * B + b_[u]) * 4 * H + j;
+  for (int jj = 0; jj < NJ; ++jj) ld[jj] = u32x4{0u, 0u, 0u, 0u};
+  if (!PERSIST && s0 > 0) {                       // plain loads: the previous launch wrote them
+    const u32x4* src = reinterpret_cast<const u32x4*>(hx_ + ((s0 & 1) ^ 1) * par_w) + rd_w / 4;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) pre_[u][g] = gp[g * H];
-      if (!PERSIST) c_[u] = cbuf[((long)(dir ? t0 + 2 : t0) * B + b_[u]) * H2 + dir * H + j];
-    }
-#pragma unroll
-    for (int jj = 0; jj < NJ; ++jj) ld_[u][jj] = u32x4{0u, 0u, 0u, 0u};
-    if (!PERSIST && s0 > 0) {                       // plain loads: the previous launch wrote them
-      const u32x4* src = reinterpret_cast<const u32x4*>(hx_ + ((s0 & 1) ^ 1) * par_w) + rd_w_[u] / 4;
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) ld_[u][jj] = src[jj * 64];
-    }
+    for (int jj = 0; jj < NJ; ++jj) ld[jj] = src[jj * 64];
   }
   LSTM_STAMP_DECL;
   if (PERSIST) __syncthreads();
-  bool aborted = false;
-  for (int s = s0; s < s1 && !aborted; ++s) {
+  for (int s = s0; s < s1; ++s) {
     const int t = dir ? T - 1 - s : s;
-#pragma unroll
-   for (int u = 0; u < TT; ++u) {
-    const int b = b_[u], ln = ln_[u];
-    const bool ok = ok_[u];
-    const unsigned rd_w = rd_w_[u], poll_w = poll_w_[u], wr_w = wr_w_[u];
-    f32x4* part = part_all + u * (2 * TILES * KS * 64);
     LSTM_STAMP(0); LSTM_STAMP(10);
     constexpr int NACC = TILES == 1 ? 2 : TILES;            // one tile: two chains (even / odd k) hide the 40-cycle dependent latency
     f32x4 acc[NACC];
@@ -462,24 +443,25 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
         asm volatile("" ::: "memory");
       };
       if (PERSIST) {
-        if (mode & 1) {                         // poll first, sweep once
-          wait_producers();
+        // poll first, sweep once.  (Round 4, measured and rejected: the sweep issued right behind the publish, falling back to the poll when it came
+        // too early -- within the run-to-run spread where a sweep is small (H = 256: 3.14 / 3.43 against 3.18 / 3.17 us per step in two
+        // sessions), worse where it is not (H = 512, B = 64: 6.05 against 5.39).)
+        wait_producers();
 #pragma unroll
-          for (int jj = 0; jj < NJ; ++jj) ld_[u][jj] = __builtin_amdgcn_raw_buffer_load_b128(hx_rs, rd_b + (unsigned)jj * 1024u, 0, 16);
-        }
+        for (int jj = 0; jj < NJ; ++jj) ld[jj] = __builtin_amdgcn_raw_buffer_load_b128(hx_rs, rd_b + (unsigned)jj * 1024u, 0, 16);
         LSTM_STAMP(7);
       }
 #pragma unroll
       for (int jj = 0; jj < NJ; ++jj) {
-        u32x4 v = ld_[u][jj];
+        u32x4 v = ld[jj];
         if (PERSIST) {
           if (!__all(tags_are(v, want))) {
             // the sweep came before this chunk's producer had published: wait for all producers (cheap poll), read this and the
             // later chunks again; should the chunk still be stale (the poll looks at one piece per producer), poll it alone
             wait_producers();
 #pragma unroll
-            for (int j2 = jj; j2 < NJ; ++j2) ld_[u][j2] = __builtin_amdgcn_raw_buffer_load_b128(hx_rs, rd_b + (unsigned)j2 * 1024u, 0, 16);
-            v = ld_[u][jj];
+            for (int j2 = jj; j2 < NJ; ++j2) ld[j2] = __builtin_amdgcn_raw_buffer_load_b128(hx_rs, rd_b + (unsigned)j2 * 1024u, 0, 16);
+            v = ld[jj];
             for (unsigned spins = 0; !__all(tags_are(v, want)); ++spins) {
               asm volatile("" ::: "memory");
               v = __builtin_amdgcn_raw_buffer_load_b128(hx_rs, rd_b + (unsigned)jj * 1024u, 0, 16);
@@ -513,8 +495,8 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
     LSTM_STAMP(2);
     __syncthreads();
     LSTM_STAMP(3);
-    if (PERSIST && *abortw) { aborted = true; break; }
-    float og[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // activated gates, c, h of this lane's cell: written after the next sweep is on its way
+    if (PERSIST && *abortw) break;
+    float og[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // activated gates, c, h of this lane's cell: written behind the publish
     if (fin) {
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       f32x4 mine = acc[0];
@@ -522,23 +504,12 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
       for (int tt = 1; tt < TILES; ++tt) mine = ft == tt ? acc[tt] : mine;
 #pragma unroll
       for (int k2 = 0; k2 < KS; ++k2) v += k2 == ks ? mine : pp[(ft * KS + k2) * 64 + lane];      // fixed order
-      float gi, gf, gg, go, cn, h;
-#ifdef RE2E_EXPERIMENTS
-      if (mode & 16) {                           // v_rcp_f32 (1 ulp) instead of the IEEE division: experiment
-        auto sg = [](float x_) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x_)); };
-        auto th = [](float x_) { float e = __expf(-2.0f * fabsf(x_)); return copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x_); };
-        gi = sg(v[0] + pre_[u][0]); gf = sg(v[1] + pre_[u][1]); gg = th(v[2] + pre_[u][2]); go = sg(v[3] + pre_[u][3]);
-        cn = gf * c_[u] + gi * gg;
-        h = go * th(cn);
-      } else
-#endif
-      {
-        gi = sigmoidf_(v[0] + pre_[u][0]); gf = sigmoidf_(v[1] + pre_[u][1]); gg = tanhf_(v[2] + pre_[u][2]); go = sigmoidf_(v[3] + pre_[u][3]);
-        cn = __builtin_fmaf(gf, c_[u], gi * gg);     // spelled out: the persistent kernel and its launch-per-step twin must not contract differently
-        h = go * tanhf_(cn);
-      }
+      // (Measured and rejected: v_rcp_f32 (1 ulp) in place of the IEEE divisions of the cell.)
+      const float gi = sigmoidf_(v[0] + pre[0]), gf = sigmoidf_(v[1] + pre[1]), gg = tanhf_(v[2] + pre[2]), go = sigmoidf_(v[3] + pre[3]);
+      float cn = __builtin_fmaf(gf, c, gi * gg);     // spelled out: the persistent kernel and its launch-per-step twin must not contract differently
+      float h = go * tanhf_(cn);
       if (t >= ln) { cn = 0.f; h = 0.f; }        // packed semantics (also rows b >= B: ln = 0)
-      c_[u] = cn;
+      c = cn;
       // The next step's pre-activations are loaded HERE: a whole step before the cell needs them, and in front of the publish.  The
       // compiler guards a load into registers it cannot prove idle with s_waitcnt vmcnt(0) (the poll loops have exits it cannot count
       // across): behind the publish that wait is the write-through latency of the sc1 store (0.7 us per step at H = 512), just in front
@@ -547,7 +518,7 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
       if (PERSIST && ok && s + 1 < T) {
         const float* gp = xg + ((long)(dir ? t - 1 : t + 1) * B + b) * 4 * H + j;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) pre_[u][g] = gp[g * H];
+        for (int g = 0; g < 4; ++g) pre[g] = gp[g * H];
       }
       if (!PERSIST || s + 1 < T) {
         // the four units of a 16-byte piece sit in lanes n, n + 16, n + 32, n + 48: gather them into lane n, one store per piece
@@ -569,14 +540,7 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
     // (Measured and rejected: the speculative sweep timed by a per-wave delay behind the publish that hovers at the edge of being too
     // early -- one late wave anywhere delays its workgroup's publish and with it EVERY peer's next sweep, so with 512 waves a
     // per-wave miss rate of 1 in 64 is a miss on every step: 2.85 against 2.93 us at H = 256, no gain at 512, 43 us at B = 8.)
-    // Behind the publish: (mode 0: the next step's sweep, then) this step's outputs -- stores write no register, so no wait guards them.
-    auto next_sweep = [&]() {
-      const unsigned rd_n = (unsigned)(((s & 1) * par_w) * 4) + rd_w * 4u;
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int jj = 0; jj < NJ; ++jj) ld_[u][jj] = __builtin_amdgcn_raw_buffer_load_b128(hx_rs, rd_n + (unsigned)jj * 1024u, 0, 16);
-    };
-    if (PERSIST && (mode & 1) == 0 && s + 1 < T) next_sweep();
+    // Behind the publish: this step's outputs -- stores write no register, so no wait guards them.
     LSTM_STAMP(5);
     if (ok) {
       float* go_ = xg + ((long)t * B + b) * 4 * H + j;
@@ -585,13 +549,9 @@ __global__ __launch_bounds__(256) void lstm_fwd2(float* xg_f, float* xg_r, const
       ybuf[((long)(t + 1) * B + b) * H2 + dir * H + j] = og[5];
     }
     LSTM_STAMP(6);
-   }
   }
-  if (PERSIST && *abortw) {                           // a peer never published: make the failure visible downstream
-#pragma unroll
-    for (int u = 0; u < TT; ++u)
-      if (ok_[u])
-        for (int t = 0; t < T; ++t) ybuf[((long)(t + 1) * B + b_[u]) * H2 + dir * H + j] = __uint_as_float(0x7fc00000u);
+  if (PERSIST && *abortw && ok) {                     // a peer never published: make the failure visible downstream
+    for (int t = 0; t < T; ++t) ybuf[((long)(t + 1) * B + b) * H2 + dir * H + j] = __uint_as_float(0x7fc00000u);
   }
 }
 
@@ -1180,14 +1140,15 @@ __global__ void zero_kernel(float* p, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = 0.f;
 }
 
-int pick_waves(int K, int min_kc, const char* env = nullptr) {
-  if (env) {                       // tuning override (tools/bench_lstm.py): RE2E_LSTM_WAVES_{FWD,BWD}
-    const char* v = exp_env(env);
-    if (v) { int w = atoi(v); if (w >= 1 && w <= 16 && (w & (w - 1)) == 0 && K % (8 * w) == 0) return w; }
+// wavefronts of lstm_fwd_step (they split K = H, a multiple of 8): as many as leave each at least 32 of it
+int fwd_step_waves(int H) {
+  if (const char* v = exp_env("RE2E_LSTM_WAVES_FWD")) {      // tuning override, experiments build (tools/bench_lstm.py)
+    const int w = atoi(v);
+    if (w >= 1 && w <= 16 && (w & (w - 1)) == 0 && H % (8 * w) == 0) return w;
   }
-  for (int w = 16; w >= 1; w >>= 1)
-    if (K % (8 * w) == 0 && K / w >= min_kc) return w;
-  return K % 8 == 0 ? 1 : 0;
+  for (int w = 16; w > 1; w >>= 1)
+    if (H % (8 * w) == 0 && H / w >= 32) return w;
+  return 1;
 }
 
 // workspace (floats): fwd  = wfrag[2][4H*H] | hfrag[2][2][MT][H*32]
@@ -1204,275 +1165,261 @@ size_t bwd_ws_floats(int B, int H) {
 // (the 16-utterance-tile form has cdiv(B, 16) tiles of up to H / 8 producers)
 size_t bwd_flag_bytes(int B, int H) { long MT = (B + 15) / 16, NX = H / 8; return 16 + (size_t)2 * 2 * MT * NX * 128; }
 
-template <int W>
-void launch_fwd(hipStream_t st, float* xg_f, float* xg_r, const float* wfrag, float* ybuf, float* cbuf, float* hfrag, const int* lens,
-                int T, int B, int H) {
-  size_t lds = (size_t)W * 32 * 33 * sizeof(float);
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&lstm_fwd_step<W>), lds);
-  dim3 grid(H / 8, cdiv(B, 32), 2);
-  for (int s = 0; s < T; ++s)
-    hipLaunchKernelGGL((lstm_fwd_step<W>), grid, dim3(W * 64), lds, st, xg_f, xg_r, wfrag, ybuf, cbuf, hfrag, lens, T, B, H, s);
-}
-template <int JT>
-void launch_bwd(hipStream_t st, float* g_f, float* g_r, const float* wb, const float* dy, const float* cbuf, float* dc, float* slabs,
-                const int* lens, int T, int B, int H) {
-  dim3 grid(H / 8, cdiv(B, 32), 2);
-  for (int s = 0; s < T; ++s)
-    hipLaunchKernelGGL((lstm_bwd_step<JT>), grid, dim3(256), 0, st, g_f, g_r, wb, dy, cbuf, dc, slabs, lens, T, B, H, s);
-}
-
 int cu_count() {
   static const int n = [] { int dev = 0; hipDeviceProp_t p; return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 1; }();
   return n;
 }
 
-// dynamic-LDS limits of the persistent kernels, one per instantiation (raised on first use, or all at once by re2e_warmup)
-template <int W, int QN, int UW> LdsLimit& fwd_lim() { static LdsLimit l; return l; }
-template <int TPW, int UW> LdsLimit& bwd_lim() { static LdsLimit l; return l; }
-constexpr size_t kOwnCuLds = 160 * 1024;
+// ---- which kernel runs a sequence: ONE plan per direction, made before anything is enqueued --------------------------------------
+// plan_fwd / plan_bwd are pure host functions of the shape, the environment switches and the chip's CU count: the kernel family, its
+// template parameters (an entry of that family's instantiation table below), the grid and the dynamic-LDS request.  re2e_lstm_seq_fwd / _bwd
+// enqueue exactly what the plan names; re2e_lstm_plan prints it (tests/test_abi.py holds the table of expected plans).
+enum SeqFamily { kFwd2Persist, kFwd2Step, kFwdPersist, kFwdStep, kBwd3, kBwdPersist, kBwdStep };
+struct SeqPlan {
+  SeqFamily family;
+  int a, b;          // the family's template parameters, named per family in kFamilyText (b = 0 where the family has one)
+  dim3 grid;
+  size_t lds;        // dynamic LDS bytes
+};
+const struct { const char *name, *a, *b; } kFamilyText[] = {{"fwd2_persist", "tiles", "nj"}, {"fwd2_step", "tiles", "nj"}, {"fwd_persist", "waves", "qn"},
+                                                            {"fwd_step", "waves", nullptr}, {"bwd3", "un", "tpw"},          {"bwd_persist", "tpw", "uw"},
+                                                            {"bwd_step", "jt", nullptr}};
 
-template <int W, int QN, int UW = 1>
-bool launch_fwd_persist(hipStream_t st, float* xg_f, float* xg_r, const float* wfrag, float* ybuf, float* cbuf, void* hxmem, size_t hxbytes,
-                        const int* lens, int T, int B, int H) {
-  size_t lds = (size_t)UW * W * 32 * 33 * sizeof(float) + 16;
-  dim3 grid(H / (8 * UW), cdiv(B, 32), 2);
-  if ((long)grid.x * grid.y * grid.z > cu_count()) return false;          // every workgroup must be resident
-  // A chain of up to HALF the chip's CUs (RE2E_LSTM_OWN_CU_FRAC = 2 since the end of round 4; rounds 2-3 measured whole = half within 0.2 ms and
-  // shipped whole, with the decoder loop persistent the 256-workgroup chains of the 512-wide layers are better off NOT excluding the
-  // weight-gradient stream from the chip they only use 5-25 % of: 52.1 -> 51.4 ms, profiles/r04_own_cu_ab.txt; a quarter: 54.3)
-  // asks for (almost) a whole CU's LDS per workgroup: nothing else can then be
-  // co-resident on its CUs, so its MFMA pipe and memory queue are its own while the filler streams keep the other CUs.
-  // (RE2E_LSTM_OWN_CU=0 turns it off, =n asks for n KB -- it has to be the whole CU: with 120 KB, which still admits a small filler
-  // workgroup, the step is 74.2 instead of 71.8 ms.  Step 77.9 -> 75.2 ms when introduced: enhancer forward 13.6 -> 9.6, backward 16.7 -> 13.0 ms.)
-  static const int hog = exp_env("RE2E_LSTM_OWN_CU") ? atoi(exp_env("RE2E_LSTM_OWN_CU")) : 160;
-  static const int frac = exp_env("RE2E_LSTM_OWN_CU_FRAC") ? atoi(exp_env("RE2E_LSTM_OWN_CU_FRAC")) : 2;
-  if (hog && (long)grid.x * grid.y * grid.z <= cu_count() / frac) lds = (size_t)hog * 1024;
-  fwd_lim<W, QN, UW>().ensure(reinterpret_cast<const void*>(&lstm_fwd_persist<W, QN, UW>), lds);
-  lstm_stamps_arm();
-  (void)hipMemsetAsync(hxmem, 0, hxbytes, st);                             // tags and the error word start at zero, every call
-  unsigned* err = (unsigned*)hxmem;
-  u64* hx = (u64*)((char*)hxmem + 16);
-  hipLaunchKernelGGL((lstm_fwd_persist<W, QN, UW>), grid, dim3(W * 64), lds, st, xg_f, xg_r, wfrag, ybuf, cbuf, hx, err, lens, T, B, H);
-  return true;
-}
-
-template <int TPW, int UW>
-bool launch_bwd_persist(hipStream_t st, float* g_f, float* g_r, const float* wb, const float* dy, const float* cbuf, float* dc, float* slabs,
-                        void* flagmem, size_t flagbytes, const int* lens, int T, int B, int H) {
-  dim3 grid(H / (8 * UW), cdiv(B, 32), 2);
-  lstm_stamps_arm();
-  (void)hipMemsetAsync(flagmem, 0, flagbytes, st);
-  unsigned* err = (unsigned*)flagmem;
-  unsigned* flags = (unsigned*)((char*)flagmem + 16);
-  static const int hog = exp_env("RE2E_LSTM_OWN_CU") ? atoi(exp_env("RE2E_LSTM_OWN_CU")) : 160;      // see launch_fwd_persist
-  size_t lds = 0;
-  static const int frac = exp_env("RE2E_LSTM_OWN_CU_FRAC") ? atoi(exp_env("RE2E_LSTM_OWN_CU_FRAC")) : 2;
-  if (hog && (long)grid.x * grid.y * grid.z <= cu_count() / frac) lds = (size_t)(hog - 16) * 1024;       // + ~13 KB static
-  bwd_lim<TPW, UW>().ensure(reinterpret_cast<const void*>(&lstm_bwd_persist<TPW, UW>), lds);
-  hipLaunchKernelGGL((lstm_bwd_persist<TPW, UW>), grid, dim3(256), lds, st, g_f, g_r, wb, dy, cbuf, dc, slabs, flags, err, lens, T, B, H);
-  return true;
-}
-
-// ---- round-4 forward (lstm_fwd2): configuration, launch of the persistent kernel and of its launch-per-step twin ----------
-struct Fwd2Cfg { int tiles, nj, tt; };      // tt: utterance tiles per workgroup (2: the interleaved form, persistent launches only)
-template <int TILES, int NJ, bool P, int TT = 1> LdsLimit& fwd2_lim() { static LdsLimit l; return l; }
-
-// RE2E_LSTM_FWD2=0 keeps the round-1..3 forward kernels (also used for widths this form is not instantiated for: H % 64 != 0)
-bool fwd2_config(int B, int H, const float* whh_f, const float* whh_r, Fwd2Cfg& c) {
-  const char* v = getenv("RE2E_LSTM_FWD2");
-  if (v && atoi(v) == 0) return false;
-  if (exp_env("RE2E_LSTM_FWD2_MAXH") && H > atoi(exp_env("RE2E_LSTM_FWD2_MAXH"))) return false;
-  if (exp_env("RE2E_LSTM_FWD2_MINH") && H < atoi(exp_env("RE2E_LSTM_FWD2_MINH"))) return false;
-  if ((reinterpret_cast<uintptr_t>(whh_f) | reinterpret_cast<uintptr_t>(whh_r)) & 15) return false;
-  if (H % 64 != 0) return false;
-  // Where it runs.  In the training step a chain is paid for in CUs x time (it owns its CUs; behind the forward half the step is bound
-  // by the sum of all streams' work): at H = 256 / B = 32 this form is faster alone (2.9 against 3.2 us per step) on TWICE the CUs
-  // (128 against 64) and the step loses 1.7 ms with it (57.4 against 55.7, two A/B rounds); on as many CUs (64: 16 units per workgroup)
-  // it is slower than the round-1..3 kernel (3.7).  It is the better kernel where that one wastes its tile or is bound by its matrix
-  // work: <= 16 utterances (half of a 32-row tile empty: 2.5 against 3.2 us, same CUs) and wide layers (H = 512, B = 64: 5.2 against 6.2).
-  // Round 6, built and measured, NOT selected (RE2E_LSTM_FWD2_TT=2 in the experiments build turns it on): TWO utterance tiles per workgroup
-  // (lstm_fwd2<.., TT = 2>), a workgroup working on one tile while the other's h(t) is on its way, so that B = 32 / H = 256 would keep this form's
-  // 2.9 us per step on the round-1..3 kernel's 64 CUs.  Bitwise equal to the one-tile form -- and 5.14 us per step against 3.22 (the step 51.4
-  // against 47.7 ms, profiles/r06_chain_two_tiles.txt): vmcnt retires in order and counts stores, so the finishing waves' poll of tile B cannot
-  // return before the write-through (sc1) publish of tile A and its output stores are acknowledged by the memory side (~0.7 us) -- the hand-off
-  // latency the interleave was to hide is paid once per TILE instead of once per step.
-  c.nj = H / 64;
-  c.tt = 1;
-  static const int tt_env = exp_env("RE2E_LSTM_FWD2_TT") ? atoi(exp_env("RE2E_LSTM_FWD2_TT")) : 1;
-  const bool two = tt_env == 2 && B > 16 && H < 384 && cdiv(B, 16) % 2 == 0 && (c.nj == 2 || c.nj == 4 || c.nj == 5);
-  if (!exp_env("RE2E_LSTM_FWD2_MINH") && !exp_env("RE2E_LSTM_FWD2_MAXH") && B > 16 && H < 384 && !two) return false;
-  if (!(c.nj == 1 || c.nj == 2 || c.nj == 4 || c.nj == 5 || c.nj == 8)) return false;
-  if (two) {
-    // units per workgroup = 4 x tiles: the smallest that keeps the grid within a quarter of the chip (the chains own their CUs)
-    const long groups = (long)(cdiv(B, 16) / 2) * 2;
-    c.tiles = 0;
-    for (int tl = 1; tl <= 4; tl *= 2)
-      if (H % (4 * tl) == 0 && (long)(H / (4 * tl)) * groups <= cu_count() / 4) { c.tiles = tl; break; }
-    if (c.tiles) { c.tt = 2; return true; }
-    if (!exp_env("RE2E_LSTM_FWD2_MINH") && !exp_env("RE2E_LSTM_FWD2_MAXH")) return false;
-  }
-  // units per workgroup = 4 x tiles: the smallest that keeps the grid within half of the chip (the rest stays with the filler
-  // streams), else within the chip
-  const long per = (long)cdiv(B, 16) * 2;
-  const int te = exp_env("RE2E_LSTM_FWD2_TILES") ? atoi(exp_env("RE2E_LSTM_FWD2_TILES")) : 0;
-  c.tiles = 0;
-  for (int lim = cu_count() / 2; lim <= cu_count() && !c.tiles; lim *= 2)
-    for (int tl = 1; tl <= 4; tl *= 2)
-      if (H % (4 * tl) == 0 && (long)(H / (4 * tl)) * per <= lim) { c.tiles = tl; break; }
-  if (te == 1 || te == 2 || te == 4) c.tiles = te;
-  if (!c.tiles) c.tiles = 4;                          // does not fit: only the launch-per-step twin can run it
-  return true;
-}
-
-template <int TILES, int NJ, int TT = 1>
-bool launch_fwd2(bool persist, hipStream_t st, float* xg_f, float* xg_r, const float* whh_f, const float* whh_r, float* ybuf, float* cbuf, void* hxmem,
-                 size_t hxbytes, const int* lens, int T, int B, int H) {
-  if (TT > 1 && !persist) return launch_fwd2<TILES, NJ, 1>(false, st, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H);
-  size_t lds = (size_t)TT * TILES * 8192 + 16;
-  dim3 grid(H / (4 * TILES), cdiv(B, 16) / TT, 2);
-  unsigned* err = (unsigned*)hxmem;
-  unsigned* hx = (unsigned*)((char*)hxmem + 16);
-  if (!persist) {
-    fwd2_lim<TILES, NJ, false>().ensure(reinterpret_cast<const void*>(&lstm_fwd2<TILES, NJ, false>), lds);
-    for (int s = 0; s < T; ++s)
-      hipLaunchKernelGGL((lstm_fwd2<TILES, NJ, false>), grid, dim3(256), lds, st, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hx, err, lens, T, B, H, s, 0);
-    return true;
-  }
-  if ((long)grid.x * grid.y * grid.z > cu_count()) return false;          // every workgroup must be resident
-  static const int hog = exp_env("RE2E_LSTM_OWN_CU") ? atoi(exp_env("RE2E_LSTM_OWN_CU")) : 160;      // see launch_fwd_persist
-  // mode 1 (default): poll one piece per producer, then sweep once.  mode 0: sweep right behind the publish and fall back to the poll when it
-  // came too early -- within the run-to-run spread of mode 1 where a sweep is small (H = 256: 3.14 / 3.43 against 3.18 / 3.17 us per step in two
-  // sessions), worse where it is not (H = 512, B = 64: 6.05 against 5.39)
-  static const int frac = exp_env("RE2E_LSTM_OWN_CU_FRAC") ? atoi(exp_env("RE2E_LSTM_OWN_CU_FRAC")) : 2;
-  static const int mode_env = exp_env("RE2E_LSTM_FWD2_MODE") ? atoi(exp_env("RE2E_LSTM_FWD2_MODE")) : -1;
-  const int mode = mode_env >= 0 ? mode_env : 1;
-  if (hog && (long)grid.x * grid.y * grid.z <= cu_count() / frac) lds = (size_t)hog * 1024;
-  fwd2_lim<TILES, NJ, true, TT>().ensure(reinterpret_cast<const void*>(&lstm_fwd2<TILES, NJ, true, TT>), lds);
-  lstm_stamps_arm();
-  (void)hipMemsetAsync(hxmem, 0, hxbytes, st);                             // tags and the error word start at zero, every call
-  hipLaunchKernelGGL((lstm_fwd2<TILES, NJ, true, TT>), grid, dim3(256), lds, st, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hx, err, lens, T, B, H, 0, mode);
-  return true;
-}
-
-// RE2E_FWD2_ALL(M): M(TILES, NJ) for every instantiation
+// The instantiation tables: M(a, b) for everything a plan can name.  is_built, the dispatch in run_fwd / run_bwd and re2e_warmup expand them.
 #define RE2E_FWD2_NJ(M, TL) M(TL, 1) M(TL, 2) M(TL, 4) M(TL, 5) M(TL, 8)
-#define RE2E_FWD2_ALL(M) RE2E_FWD2_NJ(M, 1) RE2E_FWD2_NJ(M, 2) RE2E_FWD2_NJ(M, 4)
+#define RE2E_FWD2_ALL(M) RE2E_FWD2_NJ(M, 1) RE2E_FWD2_NJ(M, 2) RE2E_FWD2_NJ(M, 4)                  /* lstm_fwd2<TILES, NJ, *>: H = 64 NJ */
+#define RE2E_FWD_PERSIST_ALL(M) M(8, 8) M(8, 5) M(8, 4) M(8, 3) M(4, 4) M(4, 2) M(4, 1)           /* lstm_fwd_persist<WAVES, QN>: H = 8 WAVES QN */
+#define RE2E_FWD_STEP_ALL(M) M(16, 0) M(8, 0) M(4, 0) M(2, 0) M(1, 0)                               /* lstm_fwd_step<WAVES> */
+#define RE2E_BWD3_UN(M, U) M(U, 1) M(U, 2) M(U, 3) M(U, 4) M(U, 5) M(U, 6) M(U, 7) M(U, 8)
+#define RE2E_BWD3_ALL(M) RE2E_BWD3_UN(M, 8) RE2E_BWD3_UN(M, 16)                                    /* lstm_bwd3<UN, TPW>: H = 64 TPW */
+#define RE2E_BWD_PERSIST_ALL(M) M(1, 1) M(1, 2) M(2, 1) M(2, 2) M(3, 1) M(3, 2) M(4, 1) M(4, 2)  /* lstm_bwd_persist<TPW, UW>: H <= 128 TPW */
+#define RE2E_BWD_STEP_ALL(M) M(1, 0) M(2, 0)                                                        /* lstm_bwd_step<JT> */
 
-bool try_fwd2(const Fwd2Cfg& c, bool persist, hipStream_t st, float* xg_f, float* xg_r, const float* whh_f, const float* whh_r, float* ybuf, float* cbuf,
-              void* hxmem, size_t hxbytes, const int* lens, int T, int B, int H) {
-#ifdef RE2E_EXPERIMENTS
-  if (c.tt == 2) {        // the interleaved form (not selected, experiments build only): instantiated for H in 128 / 256 / 320
-#define RE2E_F2T(TL, NJV) \
-    if (c.tiles == TL && c.nj == NJV) return launch_fwd2<TL, NJV, 2>(persist, st, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H);
-    RE2E_F2T(1, 2) RE2E_F2T(2, 2) RE2E_F2T(4, 2) RE2E_F2T(1, 4) RE2E_F2T(2, 4) RE2E_F2T(4, 4) RE2E_F2T(1, 5) RE2E_F2T(2, 5) RE2E_F2T(4, 5)
-#undef RE2E_F2T
-    return false;
+bool is_built(SeqFamily family, int a, int b) {
+#define RE2E_HAS(A, B) if (a == A && b == B) return true;
+  switch (family) {
+    case kFwd2Persist: case kFwd2Step: RE2E_FWD2_ALL(RE2E_HAS) break;
+    case kFwdPersist: RE2E_FWD_PERSIST_ALL(RE2E_HAS) break;
+    case kFwdStep: RE2E_FWD_STEP_ALL(RE2E_HAS) break;
+    case kBwd3: RE2E_BWD3_ALL(RE2E_HAS) break;
+    case kBwdPersist: RE2E_BWD_PERSIST_ALL(RE2E_HAS) break;
+    case kBwdStep: RE2E_BWD_STEP_ALL(RE2E_HAS) break;
   }
-#else
-  if (c.tt == 2) return false;
-#endif
-#define RE2E_F2(TL, NJV) \
-  if (c.tiles == TL && c.nj == NJV) return launch_fwd2<TL, NJV>(persist, st, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H);
-  RE2E_FWD2_ALL(RE2E_F2)
-#undef RE2E_F2
+#undef RE2E_HAS
   return false;
 }
 
-// round-4 backward on 16-utterance tiles: units per workgroup (0: not applicable -> the round-1..3 kernels).  RE2E_LSTM_BWD3=0 turns it off.
-int bwd3_units(int T, int B, int H) {
-  const char* v = getenv("RE2E_LSTM_BWD3");
-  const char* pv = getenv("RE2E_LSTM_PERSIST_BWD");
-  if ((v && atoi(v) == 0) || (pv && atoi(pv) == 0) || T < 2 || H % 64 != 0 || H / 64 > 8) return 0;
-  if (exp_env("RE2E_LSTM_BWD3_MAXH") && H > atoi(exp_env("RE2E_LSTM_BWD3_MAXH"))) return 0;
-  if (exp_env("RE2E_LSTM_BWD3_MINH") && H < atoi(exp_env("RE2E_LSTM_BWD3_MINH"))) return 0;
-  const long per = (long)cdiv(B, 16) * 2;
-  const int ue = exp_env("RE2E_LSTM_BWD3_UN") ? atoi(exp_env("RE2E_LSTM_BWD3_UN")) : 0;
-  if (ue == 8 || ue == 16) return (long)(H / ue) * per <= cu_count() ? ue : 0;
-  // 8 units while that fits a quarter of the chip, else 16 (half the workgroups, half the slab traffic): at H = 256 / B = 32 the 128-workgroup
-  // form is faster alone (3.35 against 3.66 us per step) and costs the training step 1.1 ms (57.4 against 56.3: CUs x time, see fwd2_config)
-  if ((long)(H / 8) * per <= cu_count() / 4) return 8;
-  if ((long)(H / 16) * per <= cu_count()) return 16;
-  return 0;
+// A chain of at most HALF the chip's CUs asks for a whole CU's LDS per workgroup (160 KB, minus what the kernel holds as static LDS): nothing
+// else can then be co-resident on its CUs, so its MFMA pipe and memory queue are its own while the filler streams keep the other CUs -- what
+// slows a chain beside them is sharing SIMDs with their MFMA streams.  Step 77.9 -> 75.2 ms when introduced: enhancer forward 13.6 -> 9.6,
+// backward 16.7 -> 13.0 ms.  It has to be the whole CU: with 120 KB, which still admits a small filler workgroup, the step is 74.2 instead of
+// 71.8 ms.  Half, not the whole chip, since the end of round 4: rounds 2-3 measured whole = half within 0.2 ms and shipped whole; with the
+// decoder loop persistent the 256-workgroup chains of the 512-wide layers are better off NOT excluding the weight-gradient stream from the chip
+// they only use 5-25 % of: 52.1 -> 51.4 ms, profiles/r04_own_cu_ab.txt; a quarter: 54.3.  Larger chains ask for what they need.
+constexpr size_t kCuLds = 160 * 1024;            // a CU's LDS
+constexpr size_t kBwdStaticLds = 16 * 1024;      // lstm_bwd_persist holds ~13 KB, lstm_bwd3 ~9 KB of static LDS
+size_t own_cu_lds(long workgroups, int cus, size_t static_lds, size_t needed) {
+  return workgroups <= cus / 2 ? kCuLds - static_lds : needed;
 }
-template <int UN, int TPW> LdsLimit& bwd3_lim() { static LdsLimit l; return l; }
-template <int UN, int TPW>
-bool launch_bwd3(hipStream_t st, float* g_f, float* g_r, const float* wb, const float* dy, const float* cbuf, float* dc, float* slabs, void* flagmem,
-                 size_t flagbytes, const int* lens, int T, int B, int H, float* dbp) {
-  dim3 grid(H / UN, cdiv(B, 16), 2);
-  lstm_stamps_arm();
-  (void)hipMemsetAsync(flagmem, 0, flagbytes, st);
-  unsigned* err = (unsigned*)flagmem;
-  unsigned* flags = (unsigned*)((char*)flagmem + 16);
-  static const int hog = exp_env("RE2E_LSTM_OWN_CU") ? atoi(exp_env("RE2E_LSTM_OWN_CU")) : 160;      // see launch_fwd_persist
-  static const int frac = exp_env("RE2E_LSTM_OWN_CU_FRAC") ? atoi(exp_env("RE2E_LSTM_OWN_CU_FRAC")) : 2;
-  size_t lds = hog && (long)grid.x * grid.y * grid.z <= cu_count() / frac ? (size_t)(hog - 16) * 1024 : 0;     // + ~9 KB static
-  bwd3_lim<UN, TPW>().ensure(reinterpret_cast<const void*>(&lstm_bwd3<UN, TPW>), lds);
-  hipLaunchKernelGGL((lstm_bwd3<UN, TPW>), grid, dim3(256), lds, st, g_f, g_r, wb, dy, cbuf, dc, slabs, flags, err, lens, T, B, H, dbp);
+
+bool env_off(const char* name) {      // the switches the tests flip between calls: read on every call
+  const char* v = getenv(name);
+  return v && atoi(v) == 0;
+}
+
+bool plan_fwd(int T, int B, int H, bool weights_16B_aligned, int cus, SeqPlan& p) {
+  if (H % 8 != 0) return false;
+  const bool persist = !env_off("RE2E_LSTM_PERSIST") && T >= 2;      // RE2E_LSTM_PERSIST=0: the launch-per-step forms
+  // lstm_fwd2 (RE2E_LSTM_FWD2=0 keeps the round-1..3 kernels).  Where it runs: in the training step a chain is paid for in CUs x time (it owns
+  // its CUs; behind the forward half the step is bound by the sum of all streams' work): at H = 256 / B = 32 this form is faster alone (2.9
+  // against 3.2 us per step) on TWICE the CUs (128 against 64) and the step loses 1.7 ms with it (57.4 against 55.7, two A/B rounds); on as many
+  // CUs (64: 16 units per workgroup) it is slower than the round-1..3 kernel (3.7).  It is the better kernel where that one wastes its tile or is
+  // bound by its matrix work: <= 16 utterances (half of a 32-row tile empty: 2.5 against 3.2 us, same CUs) and wide layers (H = 512, B = 64:
+  // 5.2 against 6.2).
+  if (!env_off("RE2E_LSTM_FWD2") && weights_16B_aligned && H % 64 == 0 && (B <= 16 || H >= 384)) {
+    // units per workgroup = 4 x tiles: the smallest that keeps the grid within half of the chip (the rest stays with the filler streams), else
+    // within the chip; if neither fits only the launch-per-step twin can run it
+    const long per = (long)cdiv(B, 16) * 2;
+    int tiles = 0;
+    for (int lim : {cus / 2, cus})
+      for (int tl = 1; tl <= 4 && !tiles; tl *= 2)
+        if ((long)(H / (4 * tl)) * per <= lim) tiles = tl;
+    const bool resident = persist && tiles;
+    if (!tiles) tiles = 4;
+    if (is_built(kFwd2Persist, tiles, H / 64)) {
+      p = {resident ? kFwd2Persist : kFwd2Step, tiles, H / 64, dim3(H / (4 * tiles), cdiv(B, 16), 2), (size_t)tiles * 8192 + 16};
+      if (resident) p.lds = own_cu_lds((long)p.grid.x * p.grid.y * 2, cus, 0, p.lds);
+      return true;
+    }
+  }
+  // rounds 1-3: 8 hidden units x 32 utterances per workgroup; persistent where H / 8 = WAVES x QN is built and every workgroup is resident.
+  // (512-wide layers: 8 wavefronts x 8 k-groups (140 registers, 2 waves per SIMD = 288 of a SIMD's 512) rather than 16 x 4 (94 registers, 4 waves
+  // per SIMD = 384).  Its 256 workgroups sit on every CU of the chip for the whole sequence, and what they leave free decides which filler
+  // workgroups can be co-resident: 224 registers per SIMD admit a 4-wave engine tile (152), 128 admit none of the engine's tiles.  Alone 7.4
+  // instead of 7.0 us per step, in the training step 72.94 -> 72.69 ms.)
+  const dim3 grid(H / 8, cdiv(B, 32), 2);
+  if (persist && (long)grid.x * grid.y * 2 <= cus) {
+#define RE2E_FIT(W, Q) if ((int)grid.x == W * Q) { p = {kFwdPersist, W, Q, grid, own_cu_lds((long)grid.x * grid.y * 2, cus, 0, (size_t)W * 32 * 33 * sizeof(float) + 16)}; return true; }
+    RE2E_FWD_PERSIST_ALL(RE2E_FIT)
+#undef RE2E_FIT
+  }
+  const int w = fwd_step_waves(H);
+  p = {kFwdStep, w, 0, grid, (size_t)w * 32 * 33 * sizeof(float)};
+  return is_built(kFwdStep, w, 0);
+}
+
+bool plan_bwd(int T, int B, int H, int cus, SeqPlan& p) {
+  if (H % 8 != 0) return false;
+  const bool persist = !env_off("RE2E_LSTM_PERSIST_BWD") && T >= 2;   // RE2E_LSTM_PERSIST_BWD=0: the launch-per-step form
+  // lstm_bwd3, 16-utterance tiles (RE2E_LSTM_BWD3=0 keeps the round-1..3 kernel): 8 units per workgroup while that fits a quarter of the chip,
+  // else 16 (half the workgroups, half the slab traffic): at H = 256 / B = 32 the 128-workgroup form is faster alone (3.35 against 3.66 us per
+  // step) and costs the training step 1.1 ms (57.4 against 56.3: CUs x time, see plan_fwd)
+  if (persist && !env_off("RE2E_LSTM_BWD3") && H % 64 == 0) {
+    const long per = (long)cdiv(B, 16) * 2;
+    const int ue = exp_env("RE2E_LSTM_BWD3_UN") ? atoi(exp_env("RE2E_LSTM_BWD3_UN")) : 0;      // tools/lstm_stamps.py
+    int un = 0;
+    if (ue == 8 || ue == 16) un = (long)(H / ue) * per <= cus ? ue : 0;
+    else if ((long)(H / 8) * per <= cus / 4) un = 8;
+    else if ((long)(H / 16) * per <= cus) un = 16;
+    if (un && is_built(kBwd3, un, H / 64)) {
+      p = {kBwd3, un, H / 64, dim3(H / un, cdiv(B, 16), 2), 0};
+      p.lds = own_cu_lds((long)p.grid.x * p.grid.y * 2, cus, kBwdStaticLds, 0);
+      return true;
+    }
+  }
+  // rounds 1-3: 8 UW hidden units x 32 utterances per workgroup; wide layers are bound by the slab traffic: half as many, twice as wide
+  // workgroups (RE2E_LSTM_BWD_UW = 1 | 2 forces the width)
+  if (persist) {
+    const char* wv = getenv("RE2E_LSTM_BWD_UW");
+    const int uw = (wv ? atoi(wv) : (H >= 512 ? 2 : 1)) == 2 && H % 16 == 0 ? 2 : 1;
+    const int tpw = ((H + 31) / 32 + 3) / 4;
+    const dim3 grid(H / (8 * uw), cdiv(B, 32), 2);
+    if ((long)grid.x * grid.y * 2 <= cus && grid.x <= 128 && is_built(kBwdPersist, tpw, uw)) {      // every workgroup resident; a wave polls <= 64 flags
+      p = {kBwdPersist, tpw, uw, grid, own_cu_lds((long)grid.x * grid.y * 2, cus, kBwdStaticLds, 0)};
+      return true;
+    }
+  }
+  p = {kBwdStep, H / 32 >= 8 ? 2 : 1, 0, dim3(H / 8, cdiv(B, 32), 2), 0};
   return true;
 }
-#define RE2E_BWD3_ALL(M) M(8, 1) M(8, 2) M(8, 3) M(8, 4) M(8, 5) M(8, 6) M(8, 7) M(8, 8) M(16, 1) M(16, 2) M(16, 3) M(16, 4) M(16, 5) M(16, 6) M(16, 7) M(16, 8)
-bool try_bwd3(int un, hipStream_t st, float* g_f, float* g_r, const float* wb, const float* dy, const float* cbuf, float* dc, float* slabs, void* flagmem,
-              size_t flagbytes, const int* lens, int T, int B, int H, float* dbp) {
-#define RE2E_B3(U, TP) if (un == U && H == 64 * TP) return launch_bwd3<U, TP>(st, g_f, g_r, wb, dy, cbuf, dc, slabs, flagmem, flagbytes, lens, T, B, H, dbp);
-  RE2E_BWD3_ALL(RE2E_B3)
-#undef RE2E_B3
-  return false;
+
+// dynamic-LDS limit of one kernel instantiation (raised on first use, or all at once by re2e_warmup)
+template <auto Kernel>
+void ensure_lds(size_t bytes) {
+  static LdsLimit lim;
+  lim.ensure(reinterpret_cast<const void*>(Kernel), bytes);
 }
 
-// 0: launch per step; 1 / 2: persistent kernel with 8 / 16 hidden units per workgroup (the weights must be packed for that width)
-int bwd_persist_width(int T, int B, int H) {
-  const char* v = getenv("RE2E_LSTM_PERSIST_BWD");
-  const char* mh = exp_env("RE2E_LSTM_PERSIST_BWD_MAXH");
-  if ((v && atoi(v) == 0) || T < 2 || H > (mh ? atoi(mh) : 1024) || (H + 31) / 32 > 16) return 0;
-  const char* wv = getenv("RE2E_LSTM_BWD_UW");      // tuning override
-  int uw = wv ? atoi(wv) : (H >= 512 ? 2 : 1);     // wide layers are bound by the slab traffic: half as many, twice as wide workgroups
-  if (uw == 2 && H % 16 != 0) uw = 1;
-  if (uw != 1 && uw != 2) uw = 1;
-  if ((long)(H / (8 * uw)) * cdiv(B, 32) * 2 > cu_count() || H / (8 * uw) > 128) return 0;      // every workgroup must be resident
-  return uw;
+// ---- what a plan enqueues ------------------------------------------------------------------------------------------------------------
+struct FwdArgs {
+  float *xg_f, *xg_r;
+  const float *whh_f, *whh_r;
+  float *ybuf, *cbuf;
+  const int* lens;
+  int T, B, H;
+  float *wfrag, *hfrag;      // workspace: packed weights [2][4H * H] | lstm_fwd_step's recurrent state
+  void* hxmem;               // workspace: error word (16 B) | the persistent kernels' exchange buffer
+  size_t hxbytes;
+};
+struct BwdArgs {
+  float *g_f, *g_r;
+  const float *wb, *dy, *cbuf;
+  float *dc, *slabs;
+  const int* lens;
+  int T, B, H;
+  void* flagmem;             // workspace: error word (16 B) | the persistent kernels' flag lines
+  size_t flagbytes;
+  float* dbp;                // lstm_bwd3's partial bias sums (or null)
+};
+
+template <int W>
+void launch_fwd_step(const SeqPlan& p, const FwdArgs& a, hipStream_t st) {
+  ensure_lds<&lstm_fwd_step<W>>(p.lds);
+  const long hn = (long)2 * 2 * p.grid.y * a.H * 32;
+  hipLaunchKernelGGL(zero_kernel, dim3(cdiv(hn, 256) > 1024 ? 1024 : cdiv(hn, 256)), dim3(256), 0, st, a.hfrag, hn);
+  for (int s = 0; s < a.T; ++s)
+    hipLaunchKernelGGL((lstm_fwd_step<W>), p.grid, dim3(W * 64), p.lds, st, a.xg_f, a.xg_r, a.wfrag, a.ybuf, a.cbuf, a.hfrag, a.lens, a.T, a.B, a.H, s);
+}
+template <int W, int QN>
+void launch_fwd_persist(const SeqPlan& p, const FwdArgs& a, hipStream_t st) {
+  ensure_lds<&lstm_fwd_persist<W, QN, 1>>(p.lds);
+  lstm_stamps_arm();
+  (void)hipMemsetAsync(a.hxmem, 0, a.hxbytes, st);                         // tags and the error word start at zero, every call
+  hipLaunchKernelGGL((lstm_fwd_persist<W, QN, 1>), p.grid, dim3(W * 64), p.lds, st, a.xg_f, a.xg_r, a.wfrag, a.ybuf, a.cbuf, (u64*)((char*)a.hxmem + 16),
+                     (unsigned*)a.hxmem, a.lens, a.T, a.B, a.H);
+}
+template <int TILES, int NJ>
+void launch_fwd2_persist(const SeqPlan& p, const FwdArgs& a, hipStream_t st) {
+  ensure_lds<&lstm_fwd2<TILES, NJ, true>>(p.lds);
+  lstm_stamps_arm();
+  (void)hipMemsetAsync(a.hxmem, 0, a.hxbytes, st);                         // tags and the error word start at zero, every call
+  hipLaunchKernelGGL((lstm_fwd2<TILES, NJ, true>), p.grid, dim3(256), p.lds, st, a.xg_f, a.xg_r, a.whh_f, a.whh_r, a.ybuf, a.cbuf,
+                     (unsigned*)((char*)a.hxmem + 16), (unsigned*)a.hxmem, a.lens, a.T, a.B, a.H, 0);
+}
+template <int TILES, int NJ>
+void launch_fwd2_step(const SeqPlan& p, const FwdArgs& a, hipStream_t st) {
+  ensure_lds<&lstm_fwd2<TILES, NJ, false>>(p.lds);
+  for (int s = 0; s < a.T; ++s)
+    hipLaunchKernelGGL((lstm_fwd2<TILES, NJ, false>), p.grid, dim3(256), p.lds, st, a.xg_f, a.xg_r, a.whh_f, a.whh_r, a.ybuf, a.cbuf,
+                       (unsigned*)((char*)a.hxmem + 16), (unsigned*)a.hxmem, a.lens, a.T, a.B, a.H, s);
+}
+template <int JT>
+void launch_bwd_step(const SeqPlan& p, const BwdArgs& a, hipStream_t st) {
+  for (int s = 0; s < a.T; ++s)
+    hipLaunchKernelGGL((lstm_bwd_step<JT>), p.grid, dim3(256), 0, st, a.g_f, a.g_r, a.wb, a.dy, a.cbuf, a.dc, a.slabs, a.lens, a.T, a.B, a.H, s);
+}
+template <int TPW, int UW>
+void launch_bwd_persist(const SeqPlan& p, const BwdArgs& a, hipStream_t st) {
+  lstm_stamps_arm();
+  (void)hipMemsetAsync(a.flagmem, 0, a.flagbytes, st);
+  ensure_lds<&lstm_bwd_persist<TPW, UW>>(p.lds);
+  hipLaunchKernelGGL((lstm_bwd_persist<TPW, UW>), p.grid, dim3(256), p.lds, st, a.g_f, a.g_r, a.wb, a.dy, a.cbuf, a.dc, a.slabs,
+                     (unsigned*)((char*)a.flagmem + 16), (unsigned*)a.flagmem, a.lens, a.T, a.B, a.H);
+}
+template <int UN, int TPW>
+void launch_bwd3(const SeqPlan& p, const BwdArgs& a, hipStream_t st) {
+  lstm_stamps_arm();
+  (void)hipMemsetAsync(a.flagmem, 0, a.flagbytes, st);
+  ensure_lds<&lstm_bwd3<UN, TPW>>(p.lds);
+  hipLaunchKernelGGL((lstm_bwd3<UN, TPW>), p.grid, dim3(256), p.lds, st, a.g_f, a.g_r, a.wb, a.dy, a.cbuf, a.dc, a.slabs,
+                     (unsigned*)((char*)a.flagmem + 16), (unsigned*)a.flagmem, a.lens, a.T, a.B, a.H, a.dbp);
 }
 
-bool try_bwd_persist(int uw, hipStream_t st, float* g_f, float* g_r, const float* wb, const float* dy, const float* cbuf, float* dc, float* slabs,
-                     void* flagmem, size_t flagbytes, const int* lens, int T, int B, int H) {
-  const int njt = (H + 31) / 32, tpw = (njt + 3) / 4;
-#define RE2E_BWD(TP) \
-  case TP: return uw == 2 ? launch_bwd_persist<TP, 2>(st, g_f, g_r, wb, dy, cbuf, dc, slabs, flagmem, flagbytes, lens, T, B, H) \
-                          : launch_bwd_persist<TP, 1>(st, g_f, g_r, wb, dy, cbuf, dc, slabs, flagmem, flagbytes, lens, T, B, H);
-  switch (tpw) {
-    RE2E_BWD(1) RE2E_BWD(2) RE2E_BWD(3) RE2E_BWD(4)
-    default: return false;
+// the plan's table entry -> its instantiation (plan_* return table entries only: is_built expands the same tables; anything else is refused)
+int run_fwd(const SeqPlan& p, const FwdArgs& args, hipStream_t st) {
+  switch (p.family) {
+#define RE2E_F2P(A, B) if (p.a == A && p.b == B) return launch_fwd2_persist<A, B>(p, args, st), RE2E_OK;
+#define RE2E_F2S(A, B) if (p.a == A && p.b == B) return launch_fwd2_step<A, B>(p, args, st), RE2E_OK;
+#define RE2E_FP(A, B) if (p.a == A && p.b == B) return launch_fwd_persist<A, B>(p, args, st), RE2E_OK;
+#define RE2E_FS(A, B) if (p.a == A) return launch_fwd_step<A>(p, args, st), RE2E_OK;
+    case kFwd2Persist: RE2E_FWD2_ALL(RE2E_F2P) break;
+    case kFwd2Step: RE2E_FWD2_ALL(RE2E_F2S) break;
+    case kFwdPersist: RE2E_FWD_PERSIST_ALL(RE2E_FP) break;
+    case kFwdStep: RE2E_FWD_STEP_ALL(RE2E_FS) break;
+    default: break;
+#undef RE2E_F2P
+#undef RE2E_F2S
+#undef RE2E_FP
+#undef RE2E_FS
   }
-#undef RE2E_BWD
+  re2e_set_error("re2e_lstm_seq_fwd: plan %s(%d, %d) is not in the instantiation tables", kFamilyText[p.family].name, p.a, p.b);
+  return RE2E_EUNSUPPORTED;
 }
-
-// RE2E_LSTM_PERSIST=0 keeps the launch-per-step form (also used for shapes the persistent kernel does not cover)
-bool try_fwd_persist(hipStream_t st, float* xg_f, float* xg_r, const float* wfrag, float* ybuf, float* cbuf, void* hxmem, size_t hxbytes,
-                     const int* lens, int T, int B, int H) {
-  const char* v = getenv("RE2E_LSTM_PERSIST");
-  if ((v && atoi(v) == 0) || T < 2) return false;
-  const int NX = H / 8;
-  // 512-wide layers: RE2E_LSTM_FWD_UW=2 selects 16 units per workgroup (8 wavefronts x 8 k-groups: the 16-wavefront form of it
-  // needs 130 registers per lane, 2 more than 1024 threads leave)
-  static const int uw = exp_env("RE2E_LSTM_FWD_UW") ? atoi(exp_env("RE2E_LSTM_FWD_UW")) : 1;
-  if (NX == 64 && uw == 2) return launch_fwd_persist<8, 8, 2>(st, xg_f, xg_r, wfrag, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H);
-#ifdef RE2E_EXPERIMENTS
-  // 256-wide layers on HALF the workgroups (32 instead of 64 owned CUs for the enhancer's forward chains): RE2E_LSTM_FWD_UW256=2
-  static const int uw256 = exp_env("RE2E_LSTM_FWD_UW256") ? atoi(exp_env("RE2E_LSTM_FWD_UW256")) : 1;
-  if (NX == 32 && uw256 == 2) return launch_fwd_persist<8, 4, 2>(st, xg_f, xg_r, wfrag, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H);
-#endif
-  // 512-wide layers, 8 units per workgroup: 8 wavefronts x 8 k-groups (140 registers, 2 waves per SIMD = 288 of a SIMD's 512) rather than
-  // 16 x 4 (94 registers, 4 waves per SIMD = 384).  Its 256 workgroups sit on every CU of the chip for the whole sequence, and what
-  // they leave free decides which filler workgroups can be co-resident: 224 registers per SIMD admit a 4-wave engine tile (152),
-  // 128 admit none of the engine's tiles.  Alone 7.4 instead of 7.0 us per step, in the training step 72.94 -> 72.69 ms (3 + 3 runs,
-  // one GPU session; and again 71.73 against 71.97 with the chain owning its CUs, RE2E_LSTM_OWN_CU_FRAC = 1, where no engine workgroup
-  // is co-resident any more: half as many waves sweep and meet at the barrier).  RE2E_LSTM_FWD_W8=0 selects the 16-wave form.
-  static const int w8 = exp_env("RE2E_LSTM_FWD_W8") ? atoi(exp_env("RE2E_LSTM_FWD_W8")) : 1;
-  if (NX == 64 && w8) return launch_fwd_persist<8, 8, 1>(st, xg_f, xg_r, wfrag, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H);
-#define RE2E_TRY(W, Q) if (NX == (W) * (Q)) return launch_fwd_persist<W, Q>(st, xg_f, xg_r, wfrag, ybuf, cbuf, hxmem, hxbytes, lens, T, B, H)
-  RE2E_TRY(16, 4); RE2E_TRY(8, 5); RE2E_TRY(8, 4); RE2E_TRY(8, 3); RE2E_TRY(4, 4); RE2E_TRY(4, 2); RE2E_TRY(4, 1);
-#undef RE2E_TRY
-  return false;
+int run_bwd(const SeqPlan& p, const BwdArgs& args, hipStream_t st) {
+  switch (p.family) {
+#define RE2E_B3(A, B) if (p.a == A && p.b == B) return launch_bwd3<A, B>(p, args, st), RE2E_OK;
+#define RE2E_BP(A, B) if (p.a == A && p.b == B) return launch_bwd_persist<A, B>(p, args, st), RE2E_OK;
+#define RE2E_BS(A, B) if (p.a == A) return launch_bwd_step<A>(p, args, st), RE2E_OK;
+    case kBwd3: RE2E_BWD3_ALL(RE2E_B3) break;
+    case kBwdPersist: RE2E_BWD_PERSIST_ALL(RE2E_BP) break;
+    case kBwdStep: RE2E_BWD_STEP_ALL(RE2E_BS) break;
+    default: break;
+#undef RE2E_B3
+#undef RE2E_BP
+#undef RE2E_BS
+  }
+  re2e_set_error("re2e_lstm_seq_bwd: plan %s(%d, %d) is not in the instantiation tables", kFamilyText[p.family].name, p.a, p.b);
+  return RE2E_EUNSUPPORTED;
 }
 
 }  // namespace
@@ -1530,20 +1477,16 @@ extern "C" int re2e_debug_occupy(int workgroups, int lds_bytes, int usec, hipStr
 }
 
 extern "C" int re2e_warmup(void) {
-#define RE2E_WF(W, Q, U) fwd_lim<W, Q, U>().ensure(reinterpret_cast<const void*>(&lstm_fwd_persist<W, Q, U>), kOwnCuLds)
-  RE2E_WF(8, 8, 2); RE2E_WF(8, 8, 1); RE2E_WF(16, 4, 1); RE2E_WF(8, 5, 1); RE2E_WF(8, 4, 1); RE2E_WF(8, 3, 1); RE2E_WF(4, 4, 1); RE2E_WF(4, 2, 1);
-  RE2E_WF(4, 1, 1);
-#undef RE2E_WF
-#define RE2E_WB(T) bwd_lim<T, 1>().ensure(reinterpret_cast<const void*>(&lstm_bwd_persist<T, 1>), kOwnCuLds - 16 * 1024); \
-                   bwd_lim<T, 2>().ensure(reinterpret_cast<const void*>(&lstm_bwd_persist<T, 2>), kOwnCuLds - 16 * 1024)
-  RE2E_WB(1); RE2E_WB(2); RE2E_WB(3); RE2E_WB(4);
-#undef RE2E_WB
-#define RE2E_W3(U, TP) bwd3_lim<U, TP>().ensure(reinterpret_cast<const void*>(&lstm_bwd3<U, TP>), kOwnCuLds - 16 * 1024);
-  RE2E_BWD3_ALL(RE2E_W3)
-#undef RE2E_W3
-#define RE2E_W2(TL, NJV) fwd2_lim<TL, NJV, true>().ensure(reinterpret_cast<const void*>(&lstm_fwd2<TL, NJV, true>), kOwnCuLds);
-  RE2E_FWD2_ALL(RE2E_W2)
-#undef RE2E_W2
+  const size_t fwd_own = kCuLds, bwd_own = kCuLds - kBwdStaticLds;      // the largest requests own_cu_lds makes
+#define RE2E_WFP(W, Q) ensure_lds<&lstm_fwd_persist<W, Q, 1>>(fwd_own);
+#define RE2E_WF2(TL, NJV) ensure_lds<&lstm_fwd2<TL, NJV, true>>(fwd_own);
+#define RE2E_WBP(TP, U) ensure_lds<&lstm_bwd_persist<TP, U>>(bwd_own);
+#define RE2E_WB3(U, TP) ensure_lds<&lstm_bwd3<U, TP>>(bwd_own);
+  RE2E_FWD_PERSIST_ALL(RE2E_WFP) RE2E_FWD2_ALL(RE2E_WF2) RE2E_BWD_PERSIST_ALL(RE2E_WBP) RE2E_BWD3_ALL(RE2E_WB3)
+#undef RE2E_WFP
+#undef RE2E_WF2
+#undef RE2E_WBP
+#undef RE2E_WB3
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { re2e_set_error("re2e_warmup: %s", hipGetErrorString(e)); return RE2E_EHIP; }
   return RE2E_OK;
@@ -1602,6 +1545,22 @@ extern "C" int re2e_lstm_abort_count(void) {
   return d < 0 ? -1 : (int)n + d;
 }
 
+extern "C" int re2e_lstm_plan(int T, int B, int H, int backward, int cus, char* out, size_t out_bytes) {
+  RE2E_CHECK_ARG(T > 0 && B > 0 && H > 0 && cus >= 0 && out && out_bytes > 0, "bad argument");
+  if (cus == 0) cus = cu_count();
+  SeqPlan p;
+  if (!(backward ? plan_bwd(T, B, H, cus, p) : plan_fwd(T, B, H, true, cus, p))) {
+    re2e_set_error("re2e_lstm_plan: no recurrence kernel is built for hidden size %d", H);
+    return RE2E_EUNSUPPORTED;
+  }
+  const auto& f = kFamilyText[p.family];
+  int n = snprintf(out, out_bytes, "family=%s %s=%d", f.name, f.a, p.a);
+  if (f.b && n > 0 && (size_t)n < out_bytes) n += snprintf(out + n, out_bytes - n, " %s=%d", f.b, p.b);
+  if (n > 0 && (size_t)n < out_bytes) n += snprintf(out + n, out_bytes - n, " grid=%ux%ux%u lds=%zu", p.grid.x, p.grid.y, p.grid.z, p.lds);
+  RE2E_CHECK_ARG(n > 0 && (size_t)n < out_bytes, "out_bytes too small");
+  return RE2E_OK;
+}
+
 extern "C" int re2e_lstm_seq_fwd(float* xg_f, float* xg_r, const float* whh_f, const float* whh_r, float* ybuf, float* cbuf,
                                  const int* lens_dev, int T, int B, int H, void* workspace, size_t workspace_bytes,
                                  hipStream_t stream) {
@@ -1609,42 +1568,20 @@ extern "C" int re2e_lstm_seq_fwd(float* xg_f, float* xg_r, const float* whh_f, c
   RE2E_CHECK_ARG(T > 0 && B > 0 && H > 0, "bad shape");
   if (H % 8 != 0) { re2e_set_error("re2e_lstm_seq_fwd: hidden size must be a multiple of 8 (got %d)", H); return RE2E_EUNSUPPORTED; }
   RE2E_CHECK_ARG(workspace_bytes >= fwd_ws_floats(B, H) * sizeof(float) + fwd_hx_bytes(B, H), "workspace too small");
+  SeqPlan p;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(whh_f) | reinterpret_cast<uintptr_t>(whh_r)) & 15) == 0;
+  if (!plan_fwd(T, B, H, aligned, cu_count(), p)) { re2e_set_error("re2e_lstm_seq_fwd: no kernel is built for hidden size %d", H); return RE2E_EUNSUPPORTED; }
+  // test hook: only where a persistent kernel would have run
+  if (!env_off("RE2E_LSTM_PERSIST") && T >= 2 && forced_abort(stream, ybuf, T, B, H)) { RE2E_LAUNCH_CHECK(); return RE2E_OK; }
+  const long wn = (long)4 * H * H;
   float* wfrag = (float*)workspace;
-  float* hfrag = wfrag + (size_t)2 * 4 * H * H;
-  void* hxmem = (char*)workspace + fwd_ws_floats(B, H) * sizeof(float);
-  long wn = (long)4 * H * H, hn = (long)2 * 2 * cdiv(B, 32) * H * 32;
-  {
-    const char* pv0 = getenv("RE2E_LSTM_PERSIST");                   // test hook: only where a persistent kernel would have run
-    if (!(pv0 && atoi(pv0) == 0) && T >= 2 && forced_abort(stream, ybuf, T, B, H)) { RE2E_LAUNCH_CHECK(); return RE2E_OK; }
+  const FwdArgs args = {xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, lens_dev, T, B, H, wfrag, wfrag + 2 * wn,
+                        (char*)workspace + fwd_ws_floats(B, H) * sizeof(float), fwd_hx_bytes(B, H)};
+  if (p.family == kFwdPersist || p.family == kFwdStep) {      // (lstm_fwd2 reads W_hh as it is)
+    hipLaunchKernelGGL(pack_w_fwd_kernel, dim3(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256)), dim3(256), 0, stream, whh_f, wfrag, H);
+    hipLaunchKernelGGL(pack_w_fwd_kernel, dim3(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256)), dim3(256), 0, stream, whh_r, wfrag + wn, H);
   }
-  Fwd2Cfg f2;
-  if (fwd2_config(B, H, whh_f, whh_r, f2)) {
-    const char* pv = getenv("RE2E_LSTM_PERSIST");
-    const bool want_persist = !(pv && atoi(pv) == 0) && T >= 2;
-    if (want_persist && try_fwd2(f2, true, stream, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hxmem, fwd_hx_bytes(B, H), lens_dev, T, B, H)) {
-      RE2E_LAUNCH_CHECK();
-      return RE2E_OK;
-    }
-    if (try_fwd2(f2, false, stream, xg_f, xg_r, whh_f, whh_r, ybuf, cbuf, hxmem, fwd_hx_bytes(B, H), lens_dev, T, B, H)) {
-      RE2E_LAUNCH_CHECK();
-      return RE2E_OK;
-    }
-  }
-  hipLaunchKernelGGL(pack_w_fwd_kernel, dim3(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256)), dim3(256), 0, stream, whh_f, wfrag, H);
-  hipLaunchKernelGGL(pack_w_fwd_kernel, dim3(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256)), dim3(256), 0, stream, whh_r, wfrag + wn, H);
-  if (try_fwd_persist(stream, xg_f, xg_r, wfrag, ybuf, cbuf, hxmem, fwd_hx_bytes(B, H), lens_dev, T, B, H)) {
-    RE2E_LAUNCH_CHECK();
-    return RE2E_OK;
-  }
-  hipLaunchKernelGGL(zero_kernel, dim3(cdiv(hn, 256) > 1024 ? 1024 : cdiv(hn, 256)), dim3(256), 0, stream, hfrag, hn);
-  int w = pick_waves(H, 32, "RE2E_LSTM_WAVES_FWD");
-  switch (w) {
-    case 16: launch_fwd<16>(stream, xg_f, xg_r, wfrag, ybuf, cbuf, hfrag, lens_dev, T, B, H); break;
-    case 8: launch_fwd<8>(stream, xg_f, xg_r, wfrag, ybuf, cbuf, hfrag, lens_dev, T, B, H); break;
-    case 4: launch_fwd<4>(stream, xg_f, xg_r, wfrag, ybuf, cbuf, hfrag, lens_dev, T, B, H); break;
-    case 2: launch_fwd<2>(stream, xg_f, xg_r, wfrag, ybuf, cbuf, hfrag, lens_dev, T, B, H); break;
-    default: launch_fwd<1>(stream, xg_f, xg_r, wfrag, ybuf, cbuf, hfrag, lens_dev, T, B, H); break;
-  }
+  if (const int rc = run_fwd(p, args, stream)) return rc;
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }
@@ -1657,44 +1594,33 @@ extern "C" int re2e_lstm_seq_bwd(float* g_f, float* g_r, const float* whh_f, con
   RE2E_CHECK_ARG(T > 0 && B > 0 && H > 0, "bad shape");
   if (H % 8 != 0) { re2e_set_error("re2e_lstm_seq_bwd: hidden size must be a multiple of 8 (got %d)", H); return RE2E_EUNSUPPORTED; }
   RE2E_CHECK_ARG(workspace_bytes >= bwd_ws_floats(B, H) * sizeof(float) + bwd_flag_bytes(B, H) + (dbias ? bwd_dbp_bytes(B, H) : 0), "workspace too small");
-  // dbias (optional, [2][4H]): the column sums of d(gates) per direction = the gradient of b_ih and of b_hh.  The 16-utterance-tile kernel
-  // accumulates them beside the recurrence (per-tile partials behind the flag lines, summed here); the other paths take them in a pass over
-  // d(gates) behind the recurrence.
-  const long M_rows = (long)T * B;
-  auto dbias_fallback = [&]() {
-    if (dbias) hipLaunchKernelGGL(gates_colsum_kernel, dim3(cdiv(4 * H, 64), 2), dim3(256), 0, stream, g_f, g_r, M_rows, 4 * H, dbias);
-  };
-  long wn = (long)(H / 8) * ((H + 31) / 32) * 1024;
+  SeqPlan p;
+  if (!plan_bwd(T, B, H, cu_count(), p)) { re2e_set_error("re2e_lstm_seq_bwd: no kernel is built for hidden size %d", H); return RE2E_EUNSUPPORTED; }
+  // workspace: packed weights [2][wn] (each family's own layout, the same size) | partial slabs | error word + flag lines | lstm_bwd3's bias partials
+  const long wn = (long)(H / 8) * ((H + 31) / 32) * 1024;
   float* wb = (float*)workspace;
-  float* slabs = wb + 2 * wn;
-  if (const int un = bwd3_units(T, B, H)) {                     // round-4 form: 16-utterance tiles (same workspace regions, its own layouts)
-    const long w3 = (long)4 * H * H;                            // = wn: [x][H / 16][UN][64] floats per direction
-    hipLaunchKernelGGL(pack_w_bwd3_kernel, dim3(cdiv(w3, 256) > 2048 ? 2048 : cdiv(w3, 256)), dim3(256), 0, stream, whh_f, wb, H, un);
-    hipLaunchKernelGGL(pack_w_bwd3_kernel, dim3(cdiv(w3, 256) > 2048 ? 2048 : cdiv(w3, 256)), dim3(256), 0, stream, whh_r, wb + w3, H, un);
-    long nz3 = (long)B * 2 * H;
-    hipLaunchKernelGGL(zero_kernel, dim3(cdiv(nz3, 256)), dim3(256), 0, stream, dc_state, nz3);
-    void* flagmem3 = (char*)workspace + bwd_ws_floats(B, H) * sizeof(float);
-    float* dbp = dbias ? (float*)((char*)flagmem3 + bwd_flag_bytes(B, H)) : nullptr;
-    if (try_bwd3(un, stream, g_f, g_r, wb, dy, cbuf, dc_state, slabs, flagmem3, bwd_flag_bytes(B, H), lens_dev, T, B, H, dbp)) {
-      if (dbias) hipLaunchKernelGGL(lstm_dbias_reduce_kernel, dim3(cdiv(4 * H, 256), 2), dim3(256), 0, stream, dbp, cdiv(B, 16), 4 * H, dbias);
-      RE2E_LAUNCH_CHECK();
-      return RE2E_OK;
-    }
+  char* flagmem = (char*)workspace + bwd_ws_floats(B, H) * sizeof(float);
+  const BwdArgs args = {g_f, g_r, wb, dy, cbuf, dc_state, wb + 2 * wn, lens_dev, T, B, H, flagmem, bwd_flag_bytes(B, H),
+                        dbias && p.family == kBwd3 ? (float*)(flagmem + bwd_flag_bytes(B, H)) : nullptr};
+  const dim3 pack_grid(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256));
+  if (p.family == kBwd3) {
+    const int un = p.a;                                         // bwd3: a = units per workgroup
+    hipLaunchKernelGGL(pack_w_bwd3_kernel, pack_grid, dim3(256), 0, stream, whh_f, wb, H, un);
+    hipLaunchKernelGGL(pack_w_bwd3_kernel, pack_grid, dim3(256), 0, stream, whh_r, wb + wn, H, un);
+  } else {
+    const int uw = p.family == kBwdPersist ? p.b : 1;          // bwd_persist: b = 8-unit groups per workgroup; bwd_step: 1
+    hipLaunchKernelGGL(pack_w_bwd_kernel, pack_grid, dim3(256), 0, stream, whh_f, wb, H, uw);
+    hipLaunchKernelGGL(pack_w_bwd_kernel, pack_grid, dim3(256), 0, stream, whh_r, wb + wn, H, uw);
   }
-  const int uw = bwd_persist_width(T, B, H);
-  hipLaunchKernelGGL(pack_w_bwd_kernel, dim3(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256)), dim3(256), 0, stream, whh_f, wb, H, uw ? uw : 1);
-  hipLaunchKernelGGL(pack_w_bwd_kernel, dim3(cdiv(wn, 256) > 2048 ? 2048 : cdiv(wn, 256)), dim3(256), 0, stream, whh_r, wb + wn, H, uw ? uw : 1);
-  long nz = (long)B * 2 * H;
+  const long nz = (long)B * 2 * H;
   hipLaunchKernelGGL(zero_kernel, dim3(cdiv(nz, 256)), dim3(256), 0, stream, dc_state, nz);
-  void* flagmem = (char*)workspace + bwd_ws_floats(B, H) * sizeof(float);
-  if (uw && try_bwd_persist(uw, stream, g_f, g_r, wb, dy, cbuf, dc_state, slabs, flagmem, bwd_flag_bytes(B, H), lens_dev, T, B, H)) {
-    dbias_fallback();
-    RE2E_LAUNCH_CHECK();
-    return RE2E_OK;
-  }
-  if (H / 32 >= 8) launch_bwd<2>(stream, g_f, g_r, wb, dy, cbuf, dc_state, slabs, lens_dev, T, B, H);
-  else launch_bwd<1>(stream, g_f, g_r, wb, dy, cbuf, dc_state, slabs, lens_dev, T, B, H);
-  dbias_fallback();
+  if (const int rc = run_bwd(p, args, stream)) return rc;
+  // dbias (optional, [2][4H]): the column sums of d(gates) per direction = the gradient of b_ih and of b_hh.  lstm_bwd3 accumulates them beside
+  // the recurrence (per-tile partials, summed here); the other families take them in a pass over d(gates) behind the recurrence.
+  if (dbias && p.family == kBwd3)
+    hipLaunchKernelGGL(lstm_dbias_reduce_kernel, dim3(cdiv(4 * H, 256), 2), dim3(256), 0, stream, args.dbp, cdiv(B, 16), 4 * H, dbias);
+  else if (dbias)
+    hipLaunchKernelGGL(gates_colsum_kernel, dim3(cdiv(4 * H, 64), 2), dim3(256), 0, stream, g_f, g_r, (long)T * B, 4 * H, dbias);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }

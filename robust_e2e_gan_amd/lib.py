@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 320      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 321      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -98,6 +98,7 @@ SIGNATURES = {
     're2e_step_gate': (I, [P, I, P, P, P, P, P, P, P]),
     're2e_lstm_seq_fwd': (I, [P, P, P, P, P, P, P, I, I, I, P, Z, P]),
     're2e_lstm_seq_bwd': (I, [P, P, P, P, P, P, P, P, P, I, I, I, P, P, Z, P]),
+    're2e_lstm_plan': (I, [I, I, I, I, I, P, Z]),
     're2e_lstm_cell_fwd': (I, [P, P, P, P, I, I, P]),
     're2e_lstm_cell_bwd': (I, [P, P, P, P, P, P, P, I, I, P]),
     're2e_dec_gates_cell_fwd': (I, [P, P, P, L, P, P, P, P, P, I, I, I, P]),
@@ -241,6 +242,17 @@ def set_stream_role(torch_stream, filler=True):
 
 def query(name, *args):
     return getattr(load(), name)(*args)
+
+
+def lstm_plan(T, B, H, backward=False, cus=0):
+    """re2e_lstm_plan as a dict of strings: the kernel family, its parameters, grid and dynamic LDS the recurrence entry points would
+    run this shape with (cus > 0: on a chip of that many CUs, no device needed; 0: the current device)."""
+    buf = ctypes.create_string_buffer(160)
+    lib = load()
+    rc = lib.re2e_lstm_plan(T, B, H, int(backward), cus, buf, len(buf))
+    if rc != 0:
+        raise Re2eError('re2e_lstm_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    return dict(kv.split('=') for kv in buf.value.decode().split())
 
 
 _STEP_STREAMS = {}

@@ -68,6 +68,94 @@ def test_ctypes_table_matches_header():
             assert a is b, '%s: argument %d is %s in lib.SIGNATURES but %s in include/re2e.h' % (name, i, a.__name__, b.__name__)
 
 
+_LSTM_SWITCHES = ('RE2E_LSTM_PERSIST', 'RE2E_LSTM_PERSIST_BWD', 'RE2E_LSTM_FWD2', 'RE2E_LSTM_BWD3', 'RE2E_LSTM_BWD_UW')
+# (T, B, H, environment, family, parameters, grid, dynamic LDS bytes) on a 256-CU chip; None: not pinned
+_FWD_PLANS = [
+    (60, 32, 256, {}, 'fwd_persist', dict(waves=8, qn=4), '32x1x2', 163840),
+    (60, 40, 320, {}, 'fwd_persist', dict(waves=8, qn=5), '40x2x2', 33808),
+    (60, 70, 256, {}, 'fwd_persist', dict(waves=8, qn=4), '32x3x2', 33808),
+    (60, 40, 64, {}, 'fwd_persist', dict(waves=4, qn=2), '8x2x2', 163840),
+    (60, 3, 32, {}, 'fwd_persist', dict(waves=4, qn=1), '4x1x2', 163840),
+    (60, 64, 512, {}, 'fwd2_persist', dict(tiles=4, nj=8), '32x4x2', 32784),
+    (60, 24, 512, {}, 'fwd2_persist', dict(tiles=4, nj=8), '32x2x2', 163840),
+    (60, 16, 512, {}, 'fwd2_persist', dict(tiles=2, nj=8), '64x1x2', 163840),
+    (60, 8, 256, {}, 'fwd2_persist', dict(tiles=1, nj=4), '64x1x2', 163840),
+    (60, 12, 128, {}, 'fwd2_persist', dict(tiles=1, nj=2), '32x1x2', 163840),
+    (60, 9, 320, {}, 'fwd2_persist', dict(tiles=2, nj=5), '40x1x2', 163840),
+    (60, 128, 512, {}, 'fwd2_step', dict(tiles=4, nj=8), '32x8x2', 32784),
+    (60, 32, 384, {}, 'fwd_step', dict(waves=8), '48x1x2', 33792),
+    (60, 160, 256, {}, 'fwd_step', dict(waves=8), None, None),
+    (1, 8, 256, {}, 'fwd2_step', dict(tiles=1), None, None),
+    (1, 32, 256, {}, 'fwd_step', dict(waves=8), None, None),
+    (60, 64, 512, {'RE2E_LSTM_FWD2': '0'}, 'fwd_persist', dict(waves=8, qn=8), '64x2x2', 33808),
+    (60, 32, 256, {'RE2E_LSTM_PERSIST': '0'}, 'fwd_step', dict(waves=8), None, None),
+]
+_BWD_PLANS = [
+    (60, 32, 256, {}, 'bwd3', dict(un=16, tpw=4), '16x2x2', 147456),
+    (60, 40, 320, {}, 'bwd3', dict(un=16, tpw=5), '20x3x2', 147456),
+    (60, 8, 256, {}, 'bwd3', dict(un=8, tpw=4), '32x1x2', 147456),
+    (60, 64, 512, {}, 'bwd3', dict(un=16, tpw=8), '32x4x2', 0),
+    (60, 3, 32, {}, 'bwd_persist', dict(tpw=1, uw=1), '4x1x2', 147456),
+    (60, 128, 512, {}, 'bwd_persist', dict(tpw=4, uw=2), '32x4x2', 0),
+    (60, 256, 512, {}, 'bwd_step', dict(jt=2), None, None),
+    (1, 32, 256, {}, 'bwd_step', dict(jt=2), None, None),
+    (1, 3, 32, {}, 'bwd_step', dict(jt=1), None, None),
+    (60, 32, 256, {'RE2E_LSTM_BWD3': '0'}, 'bwd_persist', dict(tpw=2, uw=1), '32x1x2', 147456),
+    (60, 40, 320, {'RE2E_LSTM_BWD3': '0', 'RE2E_LSTM_BWD_UW': '2'}, 'bwd_persist', dict(tpw=3, uw=2), '20x2x2', None),
+    (60, 32, 256, {'RE2E_LSTM_PERSIST_BWD': '0'}, 'bwd_step', {}, None, None),
+]
+# what csrc/lstm.hip instantiates per family: (first, second) parameter.  A copy of its RE2E_*_ALL tables (the library's own is_built checks
+# every plan against those): it has to follow them when an instantiation is added or dropped.
+_LSTM_BUILT = {
+    'fwd2_persist': ('tiles', 'nj', {(t, n) for t in (1, 2, 4) for n in (1, 2, 4, 5, 8)}),
+    'fwd2_step': ('tiles', 'nj', {(t, n) for t in (1, 2, 4) for n in (1, 2, 4, 5, 8)}),
+    'fwd_persist': ('waves', 'qn', {(8, 8), (8, 5), (8, 4), (8, 3), (4, 4), (4, 2), (4, 1)}),
+    'fwd_step': ('waves', None, {(w, None) for w in (1, 2, 4, 8, 16)}),
+    'bwd3': ('un', 'tpw', {(u, t) for u in (8, 16) for t in range(1, 9)}),
+    'bwd_persist': ('tpw', 'uw', {(t, u) for t in (1, 2, 3, 4) for u in (1, 2)}),
+    'bwd_step': ('jt', None, {(1, None), (2, None)}),
+}
+
+
+def test_lstm_plan_table(monkeypatch):
+    """re2e_lstm_plan (the host functions re2e_lstm_seq_fwd / _bwd choose their kernel with) on a 256-CU chip: the kernel family, its
+    parameters, grid and dynamic LDS per shape and switch; then over a sweep of shapes and two chip sizes every persistent plan keeps its
+    whole grid resident and every plan names an instantiation that is built.  No device is touched (cus > 0)."""
+    from robust_e2e_gan_amd import lib
+    if not os.path.exists(lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    for backward, table in ((False, _FWD_PLANS), (True, _BWD_PLANS)):
+        for T, B, H, env, family, params, grid, lds in table:
+            for k in _LSTM_SWITCHES:
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            got = lib.lstm_plan(T, B, H, backward=backward, cus=256)
+            where = (T, B, H, env, got)
+            assert got['family'] == family, where
+            for k, v in params.items():
+                assert int(got[k]) == v, where
+            assert grid is None or got['grid'] == grid, where
+            assert lds is None or int(got['lds']) == lds, where
+    for k in _LSTM_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for cus in (64, 256):
+        for B in (1, 8, 16, 17, 32, 64, 128, 300):
+            for H in (8, 32, 64, 128, 256, 320, 384, 512, 1024):
+                for backward in (False, True):
+                    got = lib.lstm_plan(60, B, H, backward=backward, cus=cus)
+                    where = (cus, B, H, got)
+                    ka, kb, built = _LSTM_BUILT[got['family']]
+                    assert (int(got[ka]), int(got[kb]) if kb else None) in built, where
+                    gx, gy, gz = (int(v) for v in got['grid'].split('x'))
+                    assert gz == 2 and int(got['lds']) >= 0, where
+                    if got['family'] in ('fwd2_persist', 'fwd_persist', 'bwd3', 'bwd_persist'):
+                        assert gx * gy * gz <= cus, where
+    with pytest.raises(lib.Re2eError):          # no kernel for this width: an error code, not a plan
+        lib.lstm_plan(60, 8, 12, cus=256)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from robust_e2e_gan_amd import lib
     monkeypatch.setattr(lib, '_lib', None)

@@ -713,9 +713,20 @@ def test_vgg_conv_stack_row_limits(B, T, F_):
         close('grad %d' % i, a, b, tol=2e-5)
 
 
-def _fwd2_runs(B, H):
-    """csrc/lstm.hip fwd2_config: the round-4 forward serves <= 16 utterances and wide layers (multiples of 64 units)."""
-    return H % 64 == 0 and H // 64 in (1, 2, 4, 5, 8) and (B <= 16 or H >= 384)
+def _fwd2_pair(lib, T, B, H, monkeypatch):
+    """Does the library (re2e_lstm_plan, current environment) run this shape on lstm_fwd2 both persistent and launch-per-step?  That pair
+    is one instruction sequence, so its results are compared bit for bit."""
+    fam = {}
+    for mode in ('0', '1'):
+        monkeypatch.setenv('RE2E_LSTM_PERSIST', mode)
+        fam[mode] = lib.lstm_plan(T, B, H)['family']
+    assert fam['0'].endswith('_step') and (T < 2 or fam['1'].endswith('_persist')), fam
+    return fam['0'].startswith('fwd2') and fam['1'].startswith('fwd2')
+
+
+# the shapes below whose forward must be served by the lstm_fwd2 pair (with RE2E_LSTM_FWD2 unset or 1): a changed plan cannot silently turn the
+# bit-for-bit comparisons off
+_FWD2_BITWISE = {(64, 25, 512), (64, 11, 512), (8, 45, 256), (16, 33, 512), (12, 17, 128), (9, 14, 320), (24, 15, 512), (8, 12, 256), (64, 12, 512)}
 
 
 @pytest.mark.parametrize('B,T,H,uw,fwd2', [(32, 60, 256, None, '1'), (40, 37, 320, None, '1'), (64, 25, 512, None, '1'), (3, 21, 32, None, '1'),
@@ -741,6 +752,8 @@ def test_lstm_persistent_vs_stepwise(B, T, H, uw, fwd2, monkeypatch):
     lens[0] = T
     lens = lens.to(DEV)
     wsb = lib.query('re2e_lstm_workspace_bytes', B, H)
+    bitwise = _fwd2_pair(lib, T, B, H, monkeypatch)
+    assert bitwise == (fwd2 == '1' and (B, T, H) in _FWD2_BITWISE), lib.lstm_plan(T, B, H)
     outs = {}
     for mode in ('0', '1'):
         monkeypatch.setenv('RE2E_LSTM_PERSIST', mode)
@@ -757,7 +770,7 @@ def test_lstm_persistent_vs_stepwise(B, T, H, uw, fwd2, monkeypatch):
     for name, a, b in zip(('gates_f', 'gates_r', 'y', 'c'), outs['0'], outs['1']):
         assert torch.isfinite(b).all(), name
         close(name, b, a, tol=2e-6)
-        if fwd2 == '1' and _fwd2_runs(B, H):             # the round-4 pair runs one instruction sequence: bit for bit
+        if bitwise:                                      # the round-4 pair runs one instruction sequence: bit for bit
             assert torch.equal(a, b), name
     # backward: persistent (flagged write-through hand-off of the partial slabs) against launch-per-step, from the same forward state
     gf, gr, ybuf, cbuf = outs['0']
@@ -794,6 +807,8 @@ def test_lstm_forward_nan_poisons_what_nn_lstm_poisons(B, H, monkeypatch):
     whh = [(torch.randn(4 * H, H, generator=g) / H ** 0.5).to(DEV) for _ in range(2)]
     lens = torch.full((B,), T, dtype=torch.int32, device=DEV)
     wsb = lib.query('re2e_lstm_workspace_bytes', B, H)
+    bitwise = _fwd2_pair(lib, T, B, H, monkeypatch)
+    assert bitwise == ((B, T, H) in _FWD2_BITWISE), lib.lstm_plan(T, B, H)
     outs = {}
     for mode in ('0', '1'):
         monkeypatch.setenv('RE2E_LSTM_PERSIST', mode)
@@ -807,7 +822,7 @@ def test_lstm_forward_nan_poisons_what_nn_lstm_poisons(B, H, monkeypatch):
     y0, y1 = outs['0'], outs['1']
     assert torch.equal(torch.isnan(y0), torch.isnan(y1))
     nanmask = torch.isnan(y1)
-    if _fwd2_runs(B, H):
+    if bitwise:
         assert torch.equal(y0[~nanmask], y1[~nanmask])
     else:
         close('finite outputs', y1[~nanmask], y0[~nanmask], tol=2e-6)
