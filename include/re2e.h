@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 321
+#define RE2E_ABI_VERSION 322
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -76,6 +76,17 @@ int re2e_gemm(int transa, int transb, int M, int N, int K, const float* A, long 
               float* C, long ldc, const float* bias, const float* bias2, int act, float beta, const float* mul,
               float* mask_out, const int* lens_dev, int T, void* workspace, size_t workspace_bytes,
               re2e_stream_t stream);
+/* Which kernel re2e_gemm (rowmap != 0: re2e_gemm_nt_rows / re2e_gemm_tn_rows) would run for this product, as one line of space-separated
+ * key=value pairs in `out`; nothing is launched.  The same host function (csrc/igemm.hip plan_gemm) makes the choice for the entry points.
+ * a16 / b16: A / B is 16-byte aligned with a leading dimension that is a multiple of 4; c16: so are C and the biases, and every operand spans
+ * less than 2 GiB.  filler: the stream carries RE2E_STREAM_FILLER.
+ *   route=skinny_wg vec=..                                          the K split inside the workgroup (M <= 32)
+ *   route=pipeline vec=1 variant=.. tile=BMxBNxBK n_dp=.. g_sk=..   the LDS-DMA pipeline: n_dp whole tiles + g_sk workgroups of stream-K tail
+ *   route=engine vec=.. tile=BMxBNxBK splits=.. m1=..               the tiled engine; rows [m1, M) run as a second launch of 64x64 tiles
+ * followed by need=<workspace bytes the route uses> ws=<what re2e_gemm_workspace_bytes answers: the same on either stream role>.
+ * cus > 0: plan for a chip of that many CUs (no device is touched); cus == 0: the current device's count. */
+int re2e_gemm_plan(int transa, int transb, int M, int N, int K, int a16, int b16, int c16, int act, int rowmap, int filler, int cus, char* out,
+                   size_t out_bytes);
 /* x W^T over the VALID rows of a ragged time-major batch (the reference packs its sequences: e2e_encoder.py:129-131, enhance_model.py:120-123):
  *   C[map[r]][:] = act(A[map[r]][:] . B[N,K]^T + bias + bias2) + beta C[map[r]][:]   for r < Mv,
  * A (phys_rows x K, lda) and C (phys_rows x N, ldc) in the padded layout, rowmap[Mv] the physical rows with t < len_b.  Rows outside the map are

@@ -16,6 +16,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 void re2e_set_error(const char* fmt, ...);
 bool re2e_stream_is_filler(hipStream_t stream);     // core.hip: re2e_stream_role
+int re2e_cu_count();                                // core.hip: CUs of the current device; 256 without one
 
 #define RE2E_CHECK_ARG(cond, msg)                     \
   do {                                                \
@@ -43,10 +44,13 @@ bool re2e_stream_is_filler(hipStream_t stream);     // core.hip: re2e_stream_rol
 //                                                  decoder loop persistent vs stepwise, forward and backward)
 //   RE2E_IGEMM_LOG                                 one stderr line per engine call (tools/igemm_table.py), no effect on results
 //   RE2E_DEBUG_HOOKS = 1                           lets re2e_debug_force_abort / re2e_debug_occupy answer (tests/conftest.py sets it)
-// Everything else -- tile variants, occupancy probes, rejected forms kept for A/B measurements -- is compiled in only with
+// Everything else -- occupancy probes, choices between shipped forms and rejected forms kept for A/B measurements -- is compiled in only with
 // -DRE2E_EXPERIMENTS (make EXPERIMENTS=1 -> libre2e_hip_exp.so, used by tools/ through RE2E_LIB) and answers "unset" otherwise.  Of the
 // recurrences (lstm.hip) that is RE2E_LSTM_STAMPS (phase stamps), RE2E_LSTM_BWD3_UN (tools/lstm_stamps.py) and RE2E_LSTM_WAVES_FWD
-// (tools/bench_lstm.py); the switches of their rejected forms went with the forms.
+// (tools/bench_lstm.py); the switches of their rejected forms went with the forms.  Of the dense and implicit-GEMM
+// products it is nine switches that choose between SHIPPED forms, read in one place per file (igemm.hip engine_switches: RE2E_NO_SKINNY_GEMM,
+// RE2E_NO_ROW_TAIL, RE2E_NO_THIN, RE2E_TN_XCD_KSLICE, RE2E_IGEMM_NOMEM; gemm_nt.hip nt_switches: RE2E_NT2, RE2E_CONV_NT2, RE2E_NT2_TAILWG,
+// RE2E_NT2_LOG) and applied at the top of the plan (plan_gemm below); the rejected tile forms and their switches went likewise.
 #ifdef RE2E_EXPERIMENTS
 static inline const char* exp_env(const char* name) { return getenv(name); }
 #else
@@ -148,23 +152,42 @@ bool thin_conv_forward(const ConvGeom& g, const float* wg, int Cout, const OutMa
 int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows);
 void thin_wgrad(const ConvGeom& g, const float* dout, int Cout, float* slabs, int nslab, hipStream_t st);
 
-// 3x3 / stride-1 / pad-1 convolutions with C % 16 == 0 and Cout % 64 == 0 (conv3x3.hip: halo patch staged once per channel
-// chunk, taps walked in LDS).  Returns false when the geometry is not covered (the caller then uses the implicit GEMM).
+// K-sliced batches of products for wino44.hip (igemm.hip): out[z][M][N] over K / ns slices of the contraction, through plan_gemm below
 int gemm_kslices_tn(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog = 0);
-int gemm_kslices(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog = 0);   // igemm.hip
-// gemm_nt.hip: the x W^T product as an LDS-DMA pipelined kernel with a stream-K tail.  gemm_nt2 returns 1 when it launched the product,
-// 0 when the shape / alignment is left to igemm.hip's engine; gemm_nt2_workspace_bytes is what it needs for that shape (0: nothing).
-size_t gemm_nt2_workspace_bytes(int M, int N, int K);
-int gemm_nt2(int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias, const float* bias2,
-             int act, float beta, const float* mul, float* mask_out, const int* lens, int T, void* ws, size_t wsb, hipStream_t st,
-             const int* rowmap = nullptr, int phys_rows = 0, int ident_rows = 0);
-int gemm_nt2_kslices(int M, int N, int Ks, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog);
-size_t gemm_tn2_workspace_bytes(int M, int N, int K);      // the same kernel's dy^T x form (weight gradients)
-int gemm_tn2(int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias, const float* bias2,
-             int act, float beta, void* ws, size_t wsb, hipStream_t st);
-// ... and its implicit-GEMM convolution form (forward / data gradient; ncls = 4: the output parity classes of a stride-2 data gradient)
+int gemm_kslices(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog = 0);
+
+// ---- which kernel serves a dense product: the plan (igemm.hip plan_gemm; printed by re2e_gemm_plan) -----------------------------------------------
+// gemm_nt.hip's part: the x W^T product as an LDS-DMA pipelined kernel, whole tiles (n_dp workgroups) + a stream-K tail (g_sk workgroups sharing
+// the k-tiles of the tiles of the last partial round; bytes = the slabs of its cut tiles).  variant = 0: the pipeline does not serve the product.
+struct NtPlan { int variant; int wg_per_cu; int bm, bn, bk; int ntm, ntn, nkt, n_dp, g_sk; size_t bytes; double est; };
+NtPlan nt2_plan(int M, int N, int K, bool four_wave, int cus, bool stream_k);
+bool nt2_operands_ok(int rows, int N, int K, const float* A, long lda, const float* B, long ldb, const float* C, long ldc, const float* bias, const float* bias2);
+int* nt2_ticket_slice();      // zeroed arrival tickets for the cut tiles of one launch; nullptr: none to be had
+void gemm_nt2(const NtPlan& pl, int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias, const float* bias2,
+              int act, float beta, float* slabs, int* tickets, hipStream_t st, const int* rowmap, int phys_rows, int ident_rows, int kslices, int nolog);
+// Everything the choice depends on, and nothing else.  a16 / b16: base 16-byte aligned and leading dimension % 4 == 0 (the plan adds the shape's part:
+// no float4 may straddle a bound); pipe16: A, B, C and the biases are what nt2_operands_ok asks for.  kslices > 0: a K-sliced batch (K = all slices).
+struct GemmIn { int transa, transb, M, N, K, act; bool a16, b16, pipe16, rowmap, filler; int cus, kslices; };
+enum GemmRoute { kSkinnyWg, kPipeline, kEngine };
+struct GemmPlan {
+  // stream-independent: the same for a call on the main stream and on a filler stream (re2e_gemm_workspace_bytes sees no stream)
+  size_t ws_bytes;       // what re2e_gemm_workspace_bytes answers; filled only where asked for
+  int splits;            // engine: K slices (1: no slabs, no reduce)
+  size_t need_bytes;     // workspace the route uses: the engine's slabs or the pipeline's
+  // stream-dependent
+  GemmRoute route;
+  bool vec;              // skinny_wg, engine: the <.., VEC> instantiation (16-byte loads)
+  int tile;              // engine: row of igemm.hip's tile table
+  int m1;                // engine: rows [0, m1) run on `tile`, rows [m1, M) on the 64x64 row tail; M = no tail
+  NtPlan nt;             // pipeline
+};
+GemmPlan plan_gemm(const GemmIn& in, bool with_workspace = false);
+// ... and the pipeline's implicit-GEMM convolution form (forward / data gradient; ncls = 4: the output parity classes of a stride-2 data gradient).
+// Returns 1 when it launched the convolution, 0 when the geometry is left to igemm.hip's engine.
 int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, long ldc, const float* bias, int act, float beta, int ncls,
              const int* cls_oy0, const int* cls_ox0, long cls_wstride, int remap, int OHF, int OWF, int osy, int osx, const int* ooy, const int* oox,
              hipStream_t st);
+// 3x3 / stride-1 / pad-1 convolutions with C % 16 == 0 and Cout % 64 == 0 (conv3x3.hip: halo patch staged once per channel
+// chunk, taps walked in LDS).  Returns false when the geometry is not covered (the caller then uses the implicit GEMM).
 bool halo_conv3x3(const ConvGeom& g, const float* wg, int Cout, float* out, const float* bias, int act, float beta, const float* mask,
                   hipStream_t st, float* pool_out = nullptr, unsigned char* pool_idx = nullptr);

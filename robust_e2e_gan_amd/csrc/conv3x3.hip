@@ -380,9 +380,7 @@ void launch_halo(const HaloArgs& a, hipStream_t st) {
   lim.ensure(reinterpret_cast<const void*>(&conv3x3_halo_kernel<TH, TW, DIR, RELU>), lds);
   static const int slots = [] {          // two workgroups per CU (LDS and registers both allow exactly two)
     if (exp_env("RE2E_HALO_SLOTS")) return atoi(exp_env("RE2E_HALO_SLOTS"));   // occupancy experiments
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    return 2 * cus;
+    return 2 * re2e_cu_count();
   }();
   // items per workgroup: RE2E_HALO_IPW = 0 persistent, n > 0 fixed.  Default 1: since an item's set-up is a handful of scalar
   // instructions (lane-constant addresses), a fresh workgroup per item costs nothing measurable alone on the chip (conv1_2 0.851

@@ -33,7 +33,7 @@ extern "C" int re2e_device_ok(void) {
 // streams as FILLER streams.  The persistent recurrences keep a workgroup on every CU for a whole sequence, and what they leave
 // free of a SIMD's 512 registers (224 beside the forward, 272 beside the backward of the 512-wide layers) admits ONE 4-wave
 // engine workgroup (152 registers per wave) but not the 8-wave 256x128 tile (2 waves per SIMD = 304): on a filler stream the
-// engine therefore launches the 4-wave tiles (igemm.hip: launch_big).  Everywhere else -- single-stream trainers, benchmarks,
+// engine therefore launches the 4-wave tiles (igemm.hip: big_tile).  Everywhere else -- single-stream trainers, benchmarks,
 // the latency-critical main stream -- the 8-wave tile stays the default.
 namespace {
 std::mutex g_role_mu;
@@ -54,6 +54,11 @@ extern "C" int re2e_stream_role(hipStream_t stream, int role) {
     g_filler[at] = g_filler[--g_nfiller];
   }
   return RE2E_OK;
+}
+
+int re2e_cu_count() {
+  static const int n = [] { int dev = 0, v = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
+  return n;
 }
 
 bool re2e_stream_is_filler(hipStream_t stream) {

@@ -489,11 +489,6 @@ __global__ __launch_bounds__(NT) void dec_loop_fwd_kernel(DecFwdArgs a) {
 
 struct DecPlan { int NG, NS, NFC, TC, ES, esw, NA; size_t lds, ws; size_t o_z, o_e, o_c, o_eb, o_cx; };
 
-int cu_count() {
-  static const int n = [] { int dev = 0, v = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v; }();
-  return n;
-}
-
 bool dec_plan(int L1, int B, int T, int E, int D, int A, int C, int Fh, DecPlan& p) {
   if (L1 < 1 || B < 1 || B > 32 || T < 1 || T > 2048 || E < 4 || D < 4 || A < 4 || C < 1 || Fh < 0) return false;
   if (D > 8 * 4 * KGZ || E > 8 * 4 * KGC || (D + 3) / 4 > DQ || C > CP || (E & 3) || (D & 3) || (A & 3)) return false;
@@ -514,7 +509,7 @@ bool dec_plan(int L1, int B, int T, int E, int D, int A, int C, int Fh, DecPlan&
   }
   p.NA = B * p.NS * p.NFC;
   if (p.NS > NSMAX || p.NS * p.NFC > 64) return false;
-  if (p.NG + p.NA > cu_count()) return false;                    // every workgroup must be resident, one per CU
+  if (p.NG + p.NA > re2e_cu_count()) return false;                    // every workgroup must be resident, one per CU
   size_t o = 128;                                                // [err]
   p.o_z = o; o += (size_t)p.NG * 128;
   p.o_e = o; o += (size_t)p.NA * 128;
@@ -1164,7 +1159,7 @@ bool dec_bwd_plan(int L1, int B, int T, int E, int D, int A, int C, int Fh, DecB
   p.AP = 64 * cdiv(A, 64);
   p.ARW = 4 * cdiv(cdiv(p.AP, p.NFR), 4);
   if (2 * Fh + 1 > 255) return false;                             // (dwconv_all_kernel: one thread per tap)
-  if (p.NU + p.NC + p.NA > cu_count()) return false;
+  if (p.NU + p.NC + p.NA > re2e_cu_count()) return false;
   const AttBwdLds L(E, C, Fh);
   size_t fl = (size_t)L.total, gemm = 4 * 2 * 64 * 4 + (size_t)(4 * D / 16 + 1) * 256;
   p.lds = (fl > gemm ? fl : gemm) * 4 + 16;

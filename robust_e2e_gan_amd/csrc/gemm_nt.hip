@@ -94,7 +94,9 @@ __device__ __forceinline__ int xcd_chunk(int orig, int n) {
 }
 
 // TNF = false: C = A[M,K] . B[N,K]^T, both operands k-major (x W^T).
-// TNF = true:  C = A[K,M]^T . B[K,N], both operands ROW-major along the contraction (dy^T x, the weight gradient): a k-row of a tile is
+// TNF = true (MODE 1, NOT instantiated: measured and not shipped; its constexpr branches stay in the text because deleting them
+//   changed the register allocation of the MODE 0 / 2 instantiations, profiles/gemm_plan_ab.txt):
+//   C = A[K,M]^T . B[K,N], both operands ROW-major along the contraction (dy^T x, the weight gradient): a k-row of a tile is
 //   contiguous, so the LDS image [BK][BM] | [BK][BN] is the memory image (no swizzle, no transposing stage) and the matrix-core operands come
 //   straight out of it: the wave's TM x TN tiles are INTERLEAVED in both directions -- lane lr of the A operand stands for rows m = TM*lr + a,
 //   lane lr of the B operand for columns n = TN*lr + b -- so ONE ds_read of TM (TN) consecutive floats of k-row 2s + lh is the lane's operand for
@@ -501,50 +503,65 @@ __global__ __launch_bounds__(CF::THREADS, CF::WPS) void gemm_nt2_kernel(NtArgs p
   }
 }
 
-// ---- configurations ------------------------------------------------------------------------------------------------------
-using N256x128k32s3 = NtCfg<4, 2, 2, 2, 32, 3, 2>;    // 8 waves, 144 KB LDS: one workgroup per CU
+// ---- configurations: ONE table ------------------------------------------------------------------------------------------
 using N256x128k16s3 = NtCfg<4, 2, 2, 2, 16, 3, 4>;    // 8 waves, 72 KB, <= 128 registers: two workgroups per CU
-using N128x128k32s2 = NtCfg<2, 2, 2, 2, 32, 2, 2>;    // 4 waves, 64 KB: two per CU
 using N128x128k16s3 = NtCfg<2, 2, 2, 2, 16, 3, 3>;    // 4 waves, 48 KB: three per CU
 using N128x64k16s4 = NtCfg<2, 2, 2, 1, 16, 4, 3>;     // 4 waves of 64x32, 48 KB: three per CU (few-column products: 320 columns = 5 tiles, not 2.5)
-using N256x64k16s3 = NtCfg<4, 1, 2, 2, 16, 3, 2>;     // 4 waves of 64x64, 60 KB: two per CU
-using T128x128k16s3 = NtCfg<2, 2, 2, 2, 16, 3, 3>;    // dy^T x: 4 waves of 64x64
+// X(id, configuration, workgroups per CU, TFLOP/s).  id: the plan's `variant` (and RE2E_NT2's); TFLOP/s: what the variant sustains on a chip-filling
+// product with whole rounds (tools/bench_gemm2.py, MI355X), the cost model's rate.  The plan's candidates, the residency request of the launch and the
+// instantiations gemm_nt2_kernel<CF, 0 | 2> all expand this table; the rejected rows 1, 5, 9 are in DESIGN.md Appendix A.
+#define RE2E_NT_VARIANTS(X) X(3, N256x128k16s3, 2, 138.0) X(6, N128x128k16s3, 3, 137.0) X(8, N128x64k16s4, 3, 136.0)
 
 struct NtVariant { int id, bm, bn, bk, wg_per_cu; double tflops; };
-// tflops: what the variant sustains on a chip-filling product with whole rounds (tools/bench_gemm2.py, MI355X), the cost model's rate
-const NtVariant VARIANTS[] = {{1, 256, 128, 32, 1, 130.0}, {3, 256, 128, 16, 2, 138.0}, {5, 128, 128, 32, 2, 130.0},
-                              {6, 128, 128, 16, 3, 137.0}, {8, 128, 64, 16, 3, 136.0},  {9, 256, 64, 16, 2, 128.0}};
+#define RE2E_NT_ROW(ID, CF, PER_CU, RATE) {ID, CF::BM, CF::BN, CF::BK, PER_CU, RATE},
+const NtVariant VARIANTS[] = {RE2E_NT_VARIANTS(RE2E_NT_ROW)};
+#undef RE2E_NT_ROW
 
-struct NtPlan { int variant; int wg_per_cu; int bm, bn, bk; int ntm, ntn, nkt, n_dp, g_sk; size_t bytes; double est; };
-
-inline int num_cus() {
-  static const int cus = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
-  return cus;
+// Experiment switches of this file (experiments build; the shipped library answers "unset"), all read here, at every call so that one process can
+// compare forms:  RE2E_NT2 = "old" (igemm.hip's engine) | "<variant>[,<sk>]" (a row of the table, 0 = choose; sk = 0 whole tiles only, 1 stream-K tail
+// where the model says it pays (default), 2 wherever there is a partial round);  RE2E_CONV_NT2 = 0: convolutions stay on the gather engine;
+// RE2E_NT2_TAILWG: unit ranges per CU of an all-tail 4-wave product;  RE2E_NT2_LOG: one line per plan.
+struct NtSwitches { bool old, conv_off, log; int variant, sk, tailwg; };
+NtSwitches nt_switches() {
+  NtSwitches s = {false, false, exp_env("RE2E_NT2_LOG") != nullptr, 0, 1, 1};
+  if (const char* e = exp_env("RE2E_NT2")) {
+    s.old = e[0] == 'o';
+    s.variant = atoi(e);
+    if (const char* c = strchr(e, ',')) s.sk = atoi(c + 1);
+  }
+  if (const char* e = exp_env("RE2E_CONV_NT2")) s.conv_off = atoi(e) == 0;
+  if (const char* e = exp_env("RE2E_NT2_TAILWG")) s.tailwg = atoi(e);
+  return s;
 }
+
+// Ticket counters of cut tiles: slices of one zeroed pool per device, handed out round-robin; a slice is zero again when the launch that drew it
+// has finished (each tile's last arriver resets its counter), so no memset node sits in front of a product.  256 slices: more launches with a
+// stream-K tail than that would have to be in flight at once for two of them to share one.
+constexpr int POOL_SLICES = 256, POOL_SLICE_INTS = 4096;
 
 // Schedule of one variant: whole tiles (DP) + stream-K tail, and the model's time for it (calibrated on profiles/r05_gemm_nt_variants.txt).
 // Balance is per CU, whatever the residency: a CU's matrix pipe runs one tile per tile-time with one resident workgroup or with three
 // (768 tiles on 256 CUs x 2 resident = three tiles per CU: no tail).  So the tail is what T leaves over whole rounds of CUs: those R tiles
 // are cut along K into ONE unit range per CU (more parts only add slab traffic: 768 parts of a 128x128 tile ran 20 % SLOWER than whole tiles,
 // 256 parts of a 256x128 tile 14 % faster).
-NtPlan nt2_plan_variant(const NtVariant& v, int M, int N, int K, int sk) {
+NtPlan nt2_plan_variant(const NtVariant& v, int M, int N, int K, int sk, int tailwg, long cus) {
   NtPlan pl;
   memset(&pl, 0, sizeof(pl));
   pl.variant = v.id; pl.bm = v.bm; pl.bn = v.bn; pl.bk = v.bk; pl.wg_per_cu = v.wg_per_cu;
   pl.ntm = cdiv(M, pl.bm); pl.ntn = cdiv(N, pl.bn); pl.nkt = cdiv(K, pl.bk);
-  const long T = (long)pl.ntm * pl.ntn, cus = num_cus();
+  const long T = (long)pl.ntm * pl.ntn;
   const long R = T % cus;
   const double slab = (double)v.bm * v.bn * 4.0;
   const double t_tile = 2.0 * v.bm * v.bn * (double)K / (v.tflops * 1e12 / cus);      // one CU, one tile
   const double t_over = 1.0e-6 + slab / 25e9;                                          // a tile's fill + epilogue as its CU sees them
   pl.n_dp = (int)T; pl.g_sk = 0;
   pl.est = (double)cdiv(T, cus) * (t_tile + t_over);
-  if (sk && R != 0) {
+  if (sk && R != 0 && R <= POOL_SLICE_INTS) {              // (a ticket per cut tile, from one slice of the pool)
     const long U = R * pl.nkt;
-    // one unit range per CU -- except when the WHOLE product is the tail and the workgroup has 4 waves (RE2E_NT2_TAILWG, experiments: a lone
-    // 4-wave workgroup leaves three quarters of a CU's wave slots empty for the whole launch): then two per CU
+    // one unit range per CU -- except when the WHOLE product is the tail and the workgroup has 4 waves (a lone 4-wave workgroup leaves three
+    // quarters of a CU's wave slots empty for the whole launch): RE2E_NT2_TAILWG per CU there (experiments; 1 is what ships)
     long g = cus;
-    if (T == R && v.bm * v.bn <= 128 * 256) { const char* e = exp_env("RE2E_NT2_TAILWG"); g = cus * (e ? atoi(e) : 1); }
+    if (T == R && v.bm * v.bn <= 128 * 256) g = cus * tailwg;
     const long min_units = 128 / pl.bk;                  // a workgroup's share of the tail: at least 128 k
     if (U / g < min_units) g = U / min_units;
     if (g >= 8) g &= ~7L;                                // whole rounds of XCDs (the whole-tile workgroups behind keep blockIdx % 8 = XCD)
@@ -559,35 +576,61 @@ NtPlan nt2_plan_variant(const NtVariant& v, int M, int N, int K, int sk) {
   return pl;
 }
 
-// RE2E_NT2 (experiments build, read at every call so that one process can compare variants):
-//   "old" = the engine of igemm.hip;  "<variant>[,<sk>]": variant id of the table above (0 = choose), sk = 0 whole tiles only, 1 stream-K
-//   tail where the model says it pays (default), 2 stream-K tail wherever there is a partial round
-NtPlan nt2_plan(int M, int N, int K, bool filler, bool tn = false, int sk_override = -1) {
-  int variant = 0, sk = 1;
-  if (const char* e = exp_env(tn ? "RE2E_TN2" : "RE2E_NT2")) {
-    if (e[0] == 'o') { NtPlan none; memset(&none, 0, sizeof(none)); return none; }
-    variant = atoi(e);
-    if (const char* c = strchr(e, ',')) sk = atoi(c + 1);
+template <class CF, int MODE>
+void nt2_launch(const NtArgs& a, const NtPlan& pl, hipStream_t st) {
+  static LdsLimit lim;
+  // residency is set through the LDS request: exactly wg_per_cu workgroups fit a CU's 160 KB
+  size_t lds = CF::LDS_BYTES;
+  const size_t want = (size_t)(160 * 1024) / (pl.wg_per_cu + 1) + 1024;
+  if (lds < want) lds = want;
+  lim.ensure(reinterpret_cast<const void*>(&gemm_nt2_kernel<CF, MODE>), lds);
+  hipLaunchKernelGGL((gemm_nt2_kernel<CF, MODE>), dim3(pl.n_dp + pl.g_sk), dim3(CF::THREADS), lds, st, a);
+}
+
+// Enqueue what the plan names.  The one place of this file that prints RE2E_IGEMM_LOG's line (tools/igemm_table.py joins it with a kernel trace).
+template <int MODE>
+void nt2_run(const NtArgs& a, const NtPlan& pl, long log_M, long log_K, int log_splits, hipStream_t st) {
+  static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;
+  if (log_calls && log_splits)
+    fprintf(stderr, "[igemm] A=%s B=DenseK tile=%dx%dx%d vec=1 M=%ld N=%d K=%ld splits=%d\n", MODE == 2 ? "ConvK" : "DenseK", pl.bm, pl.bn, pl.bk, log_M, a.N, log_K,
+            log_splits);
+  switch (pl.variant) {
+#define RE2E_NT_CASE(ID, CF, PER_CU, RATE) case ID: nt2_launch<CF, MODE>(a, pl, st); break;
+    RE2E_NT_VARIANTS(RE2E_NT_CASE)
+#undef RE2E_NT_CASE
+    default: fprintf(stderr, "re2e: pipeline plan names variant %d, which is not in the table\n", pl.variant); abort();
   }
-  if (sk_override >= 0) sk = sk_override;
+}
+
+// what the pipeline asks of an operand: 16-byte aligned, a leading dimension of whole float4s, byte offsets of 31 bits (bit 31 is OOB)
+inline bool loadable16(const void* p, long rows, long ld, long cols) {
+  return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0 && ((rows - 1) * ld + cols) * 4 < 0x7FFFFFF0L;
+}
+
+}  // namespace
+
+bool nt2_operands_ok(int rows, int N, int K, const float* A, long lda, const float* B, long ldb, const float* C, long ldc, const float* bias, const float* bias2) {
+  return loadable16(A, rows, lda, K) && loadable16(B, N, ldb, K) && loadable16(C, rows, ldc, N) && loadable16(bias, 1, 0, N) && loadable16(bias2, 1, 0, N);
+}
+
+// The pipeline's plan for an M x N x K product: the best row of the table under the cost model.  four_wave: only the 4-wave tiles -- on a FILLER
+// stream (work that runs beside resident recurrences, core.hip re2e_stream_role) they fit the registers and LDS a recurrence workgroup leaves free
+// on its CU; and for mapped products, whose row counts are whatever the batch's lengths give: on such counts the cost model's 256x128 choices miss
+// (21760 x 1024 x 512 ran 236 us on the 8-wave tile with a stream-K tail it priced at 196, 182 on 128x128 tiles).  variant = 0: not served here.
+NtPlan nt2_plan(int M, int N, int K, bool four_wave, int cus, bool stream_k) {
+  const NtSwitches sw = nt_switches();
   NtPlan best;
   memset(&best, 0, sizeof(best));
+  if (sw.old) return best;
   for (const NtVariant& v : VARIANTS) {
-    if (variant ? v.id != variant : (tn ? v.id != 6 : (v.id == 1 || v.id == 5 || v.id == 9))) continue;      // candidates of the automatic choice: 3, 6, 8 (dy^T x: 6)
-    // on a FILLER stream (work that runs beside resident recurrences, core.hip re2e_stream_role) only 4-wave tiles: they fit the registers
-    // and LDS a recurrence workgroup leaves free on its CU
-    if (!variant && filler && v.id == 3) continue;
-    const NtPlan pl = nt2_plan_variant(v, M, N, K, sk);
+    if (sw.variant ? v.id != sw.variant : (four_wave && v.bm * v.bn > 128 * 128)) continue;
+    const NtPlan pl = nt2_plan_variant(v, M, N, K, stream_k ? sw.sk : 0, sw.tailwg, cus);
     if (!best.variant || pl.est < best.est) best = pl;
   }
   return best;
 }
 
-// Ticket counters of cut tiles: slices of one zeroed pool per device, handed out round-robin; a slice is zero again when the launch that drew it
-// has finished (each tile's last arriver resets its counter), so no memset node sits in front of a product.  256 slices: more launches with a
-// stream-K tail than that would have to be in flight at once for two of them to share one.
-constexpr int POOL_SLICES = 256, POOL_SLICE_INTS = 4096;
-int* ticket_slice() {
+int* nt2_ticket_slice() {
   static std::mutex mu;
   static int* pool[16] = {nullptr};
   static unsigned next[16] = {0};
@@ -602,34 +645,13 @@ int* ticket_slice() {
   return pool[dev] + (size_t)(next[dev]++ % POOL_SLICES) * POOL_SLICE_INTS;
 }
 
-template <class CF, int MODE>
-void nt2_launch(const NtArgs& a, const NtPlan& pl, hipStream_t st) {
-  static LdsLimit lim;
-  size_t lds = CF::LDS_BYTES;
-  // residency is set through the LDS request: exactly wg_per_cu workgroups fit a CU's 160 KB
-  // (RE2E_NT2_MAXWG, experiments build: fewer -- what a co-resident persistent recurrence workgroup needs is registers: 240 per SIMD for the 512-wide chains)
-  int per_cu = pl.wg_per_cu;
-  if (const char* e = exp_env("RE2E_NT2_MAXWG")) { const int m = atoi(e); if (m >= 1 && m < per_cu) per_cu = m; }
-  const size_t want = (size_t)(160 * 1024) / (per_cu + 1) + 1024;
-  if (lds < want) lds = want;
-  lim.ensure(reinterpret_cast<const void*>(&gemm_nt2_kernel<CF, MODE>), lds);
-  hipLaunchKernelGGL((gemm_nt2_kernel<CF, MODE>), dim3(pl.n_dp + pl.g_sk), dim3(CF::THREADS), lds, st, a);
-}
-
-}  // namespace
-
-size_t gemm_nt2_workspace_bytes(int M, int N, int K) {
-  if (K % 4) return 0;
-  const size_t a = nt2_plan(M, N, K, false).bytes, b = nt2_plan(M, N, K, true).bytes;      // the stream's role is not known here
-  return a > b ? a : b;
-}
-
 // Implicit-GEMM convolution forward / data gradient on the same pipeline (MODE 2).  g: geometry of ONE class (g.in = the image); ncls = 1, or 4 with
 // per-class offsets / weight sets / output positions (stride-2 data gradient).  Returns 1 when launched here, 0 when left to igemm.hip's gather engine.
 int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, long ldc, const float* bias, int act, float beta, int ncls,
              const int* cls_oy0, const int* cls_ox0, long cls_wstride, int remap, int OHF, int OWF, int osy, int osx, const int* ooy, const int* oox,
              hipStream_t st) {
-  if (const char* e = exp_env("RE2E_CONV_NT2")) { if (atoi(e) == 0) return 0; }      // (experiments build, read per call: same-session A/B against igemm.hip's gather engine)
+  const NtSwitches sw = nt_switches();
+  if (sw.conv_off) return 0;
   const int K = g.KH * g.KW * g.C;
   if (g.C % 16 || Cout % 4 || g.KH * g.KW > 32 || g.KH * g.KW < 2 || ncls < 1 || ncls > 4) return 0;
   if ((reinterpret_cast<uintptr_t>(g.in) & 15) || (reinterpret_cast<uintptr_t>(wg) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) || ldc % 4) return 0;
@@ -649,9 +671,9 @@ int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, lo
   if (in_bytes + shift + (long)(g.KH * g.W + g.KW) * g.C * 4 * 4 >= 0x7FFFFFF0L) return 0;
   if ((long)ncls * Cout * K * 4 >= 0x7FFFFFF0L) return 0;
   // whole tiles only (the convolution entry points carry no workspace for partial slabs; the step's shapes fill their rounds: 500 / 250 / 4000 tiles)
-  NtPlan q = nt2_plan(M, Cout, K, re2e_stream_is_filler(st), false, 0);
+  NtPlan q = nt2_plan(M, Cout, K, re2e_stream_is_filler(st), re2e_cu_count(), false);
   if (!q.variant || g.C % q.bk) return 0;
-  q.n_dp = ncls * q.ntm * q.ntn; q.g_sk = 0;
+  q.n_dp = ncls * q.ntm * q.ntn;
   NtArgs a;
   memset(&a, 0, sizeof(a));
   a.A = reinterpret_cast<const float*>(reinterpret_cast<const char*>(g.in) - shift); a.B = wg; a.C = out;
@@ -666,117 +688,31 @@ int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, lo
     a.ooy[c] = ooy ? ooy[c < ncls ? c : 0] : 0; a.oox[c] = oox ? oox[c < ncls ? c : 0] : 0;
   }
   a.a_shift = (unsigned)shift;
-  static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;
-  if (log_calls)
-    fprintf(stderr, "[igemm] A=ConvK B=DenseK tile=%dx%dx%d vec=1 M=%d N=%d K=%d splits=%d\n", q.bm, q.bn, q.bk, M * ncls, Cout, K, q.g_sk ? -q.g_sk : 1);
-  if (exp_env("RE2E_NT2_LOG")) fprintf(stderr, "[conv2] %dx%dx%d cls %d variant %d tiles %ld dp %d sk %d\n", M, Cout, K, ncls, q.variant, (long)ncls * q.ntm * q.ntn, q.n_dp, q.g_sk);
-  const NtPlan& pl2 = q;
-  switch (pl2.variant) {
-    case 1: nt2_launch<N256x128k32s3, 2>(a, pl2, st); break;
-    case 3: nt2_launch<N256x128k16s3, 2>(a, pl2, st); break;
-    case 5: nt2_launch<N128x128k32s2, 2>(a, pl2, st); break;
-    case 6: nt2_launch<N128x128k16s3, 2>(a, pl2, st); break;
-    case 8: nt2_launch<N128x64k16s4, 2>(a, pl2, st); break;
-    case 9: nt2_launch<N256x64k16s3, 2>(a, pl2, st); break;
-    default: return 0;
-  }
+  if (sw.log) fprintf(stderr, "[conv2] %dx%dx%d cls %d variant %d tiles %ld dp %d sk %d\n", M, Cout, K, ncls, q.variant, (long)ncls * q.ntm * q.ntn, q.n_dp, q.g_sk);
+  nt2_run<2>(a, q, (long)M * ncls, K, 1, st);
   return 1;
 }
 
-// K-sliced batch of x W^T products (igemm.hip gemm_kslices; wino44.hip's 25 positions): out[z][M][N] = A[:, z*Ks : (z+1)*Ks] . B[:, same]^T, whole tiles.
-int gemm_nt2_kslices(int M, int N, int Ks, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog) {
-  if (const char* e = exp_env("RE2E_NT2")) { if (e[0] == 'o') return 0; }
-  if (Ks % 16 || lda % 4 || ldb % 4 || N % 4 || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) return 0;
-  const long K = (long)Ks * ns;
-  if (((long)(M - 1) * lda + K) * 4 >= 0x7FFFFFF0L || ((long)(N - 1) * ldb + K) * 4 >= 0x7FFFFFF0L || (long)M * N * 4 >= 0x7FFFFFF0L || M < 256 || ns > 4096) return 0;
-  NtPlan q = nt2_plan(M, N, Ks, re2e_stream_is_filler(st), false, 0);
-  if (!q.variant) return 0;
-  q.n_dp = ns * q.ntm * q.ntn; q.g_sk = 0;
+// Enqueue a pipeline plan of plan_gemm (igemm.hip), which has checked the operands (nt2_operands_ok) and, for a stream-K tail, the workspace and
+// the ticket slice.  rowmap / phys_rows (optional): M logical rows, row r = physical row rowmap[r] < phys_rows of A and of C (see NtArgs).
+// kslices > 0: the K-sliced batch of igemm.hip's gemm_kslices (wino44.hip's 25 positions): C[z][M][N] = A[:, zK : (z+1)K] . B[:, same]^T, whole
+// tiles counted over the slices.
+void gemm_nt2(const NtPlan& pl, int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias, const float* bias2,
+              int act, float beta, float* slabs, int* tickets, hipStream_t st, const int* rowmap, int phys_rows, int ident_rows, int kslices, int nolog) {
+  const long Mp = rowmap ? phys_rows : M, Kall = kslices ? (long)K * kslices : K;
   NtArgs a;
   memset(&a, 0, sizeof(a));
-  a.A = A; a.B = B; a.C = out;
-  a.a_bytes = (unsigned)(((long)(M - 1) * lda + K) * 4); a.b_bytes = (unsigned)(((long)(N - 1) * ldb + K) * 4);
-  a.lda = (int)lda; a.ldb = (int)ldb; a.ldc = N; a.M = M; a.N = N; a.K = Ks;
-  a.act = RE2E_ACT_NONE;
-  a.ntm = q.ntm; a.ntn = q.ntn; a.n_dp = q.n_dp; a.g_sk = 0; a.nkt = q.nkt;
-  a.ncls = ns; a.batch_k = Ks; a.batch_c = (long)M * N;
-  static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;
-  if (log_calls && !nolog)
-    fprintf(stderr, "[igemm] A=DenseK B=DenseK tile=%dx%dx%d vec=1 M=%d N=%d K=%ld splits=%d\n", q.bm, q.bn, q.bk, M, N, K, ns);
-  switch (q.variant) {
-    case 1: nt2_launch<N256x128k32s3, 0>(a, q, st); break;
-    case 3: nt2_launch<N256x128k16s3, 0>(a, q, st); break;
-    case 5: nt2_launch<N128x128k32s2, 0>(a, q, st); break;
-    case 6: nt2_launch<N128x128k16s3, 0>(a, q, st); break;
-    case 8: nt2_launch<N128x64k16s4, 0>(a, q, st); break;
-    case 9: nt2_launch<N256x64k16s3, 0>(a, q, st); break;
-    default: return 0;
-  }
-  return 1;
-}
-
-// The dy^T x form (MODE 1) is NOT what the shipped library runs.  Measured against igemm.hip's transposing-stage kernel + split-K + reduce launch
-// (profiles/r05_gemm_tn_variants.txt: first form, a ds_read_b32 per B tile; profiles/r05_gemm_tn_variants_v2.txt: both operands one wide read):
-// 2048x2560x12800 128 vs 122 TFLOP/s, but 2048x512x12800 104 vs 110 and everything with fewer tiles far behind -- a weight gradient has few output
-// tiles and a long K, so the WHOLE product is the stream-K tail: 4 to 32 parts per tile, summed by one last arriver each, where the old path's
-// reduce launch spreads that sum over the chip.  Compiled only into the experiments build (RE2E_TN2 selects it there), 128x128 tile only: the
-// 128x256 tile (four interleaved column tiles per wave, 232 registers) reached 134 TFLOP/s on 2048x2560x12800 but returned wrong, non-repeatable
-// sums on products with many parts per tile (tools/stress_gemm_nt_tail.py, profiles/r05_stress_streamk_tail.txt: every x W^T variant and the
-// 128x128 dy^T x form pass it, bitwise repeatable, 1-3 unit ranges per CU beside an unevenly loaded chip) -- not run down, removed.
-#ifdef RE2E_EXPERIMENTS
-#include "experiments/gemm_tn2.hip"     // RE2E_TN2: the rejected dy^T x launcher, experiments build only
-#else
-size_t gemm_tn2_workspace_bytes(int, int, int) { return 0; }
-int gemm_tn2(int, int, int, const float*, long, const float*, long, float*, long, const float*, const float*, int, float, void*, size_t, hipStream_t) { return 0; }
-#endif
-
-// returns 1 when the product was launched here, 0 when the shape / alignment is left to igemm.hip
-// rowmap / phys_rows (optional): M logical rows, row r = physical row rowmap[r] < phys_rows of A and of C (see NtArgs)
-int gemm_nt2(int M, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias, const float* bias2,
-             int act, float beta, const float* mul, float* mask_out, const int* lens, int T, void* ws, size_t wsb, hipStream_t st,
-             const int* rowmap, int phys_rows, int ident_rows) {
-  const int Mp = rowmap ? phys_rows : M;           // rows the bounds are taken over
-  if (K % 4 || lda % 4 || ldb % 4 || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(B) & 15)) return 0;
-  if (((long)(Mp - 1) * lda + K) * 4 >= 0x7FFFFFF0L || ((long)(N - 1) * ldb + K) * 4 >= 0x7FFFFFF0L) return 0;     // 31-bit offsets: OOB is bit 31
-  if (M < 256 || Mp < M || act == RE2E_ACT_SIGMOID_MASK_MUL) return 0;
-  (void)mul; (void)mask_out; (void)lens; (void)T;
-  if (N % 4 || ldc % 4 || (reinterpret_cast<uintptr_t>(C) & 15) || ((long)(Mp - 1) * ldc + N) * 4 >= 0x7FFFFFF0L) return 0;      // 16-byte stores of 4 output columns
-  if ((bias && (reinterpret_cast<uintptr_t>(bias) & 15)) || (bias2 && (reinterpret_cast<uintptr_t>(bias2) & 15))) return 0;
-  // (mapped products: the 4-wave tiles only -- their row counts are whatever the batch's lengths give, and on such counts the cost model's
-  //  256x128 choices miss: 21760 x 1024 x 512 ran 236 us on the 8-wave tile with a stream-K tail it priced at 196, 182 on 128x128 tiles)
-  const NtPlan pl = nt2_plan(M, N, K, re2e_stream_is_filler(st) || rowmap != nullptr);
-  if (!pl.variant) return 0;
-  NtArgs a;
-  memset(&a, 0, sizeof(a));
-  if (pl.g_sk) {
-    if (!ws || wsb < pl.bytes || (long)pl.ntm * pl.ntn - pl.n_dp > POOL_SLICE_INTS) return 0;
-    a.counters = ticket_slice();
-    if (!a.counters) return 0;
-    a.slabs = (float*)ws;
-  }
-  a.A = A; a.B = B; a.C = C;
-  a.a_bytes = (unsigned)(((long)(Mp - 1) * lda + K) * 4); a.b_bytes = (unsigned)(((long)(N - 1) * ldb + K) * 4);
+  a.A = A; a.B = B; a.C = C; a.slabs = slabs; a.counters = tickets;
+  a.a_bytes = (unsigned)(((Mp - 1) * lda + Kall) * 4); a.b_bytes = (unsigned)(((long)(N - 1) * ldb + Kall) * 4);
   a.lda = (int)lda; a.ldb = (int)ldb; a.ldc = ldc; a.M = M; a.N = N; a.K = K;
   a.bias = bias; a.bias2 = bias2; a.act = act; a.beta = beta;
   a.ntm = pl.ntm; a.ntn = pl.ntn; a.n_dp = pl.n_dp; a.g_sk = pl.g_sk; a.nkt = pl.nkt;
   a.rowmap = rowmap; a.ident_rows = rowmap ? ident_rows : 0;
+  if (kslices) { a.ncls = kslices; a.batch_k = K; a.batch_c = (long)M * N; }
   static const bool nomem = exp_env("RE2E_IGEMM_NOMEM") != nullptr;
-  a.nomem = nomem ? 1 : 0;
-
-  static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;
-  if (log_calls)
-    fprintf(stderr, "[igemm] A=DenseK B=DenseK tile=%dx%dx%d vec=1 M=%d N=%d K=%d splits=%d\n", pl.bm, pl.bn, pl.bk, M, N, K, pl.g_sk ? -pl.g_sk : 1);
-  if (exp_env("RE2E_NT2_LOG")) fprintf(stderr, "[nt2] %dx%dx%d variant %d tiles %ld dp %d sk %d est %.1f us\n", M, N, K, pl.variant, (long)pl.ntm * pl.ntn, pl.n_dp, pl.g_sk, pl.est * 1e6);
-  switch (pl.variant) {
-    case 1: nt2_launch<N256x128k32s3, 0>(a, pl, st); break;
-    case 3: nt2_launch<N256x128k16s3, 0>(a, pl, st); break;
-    case 5: nt2_launch<N128x128k32s2, 0>(a, pl, st); break;
-    case 6: nt2_launch<N128x128k16s3, 0>(a, pl, st); break;
-    case 8: nt2_launch<N128x64k16s4, 0>(a, pl, st); break;
-    case 9: nt2_launch<N256x64k16s3, 0>(a, pl, st); break;
-    default: return 0;
-  }
-  return 1;
+  a.nomem = (nomem && !kslices) ? 1 : 0;
+  if (nt_switches().log) fprintf(stderr, "[nt2] %dx%dx%d variant %d tiles %ld dp %d sk %d est %.1f us\n", M, N, K, pl.variant, (long)pl.ntm * pl.ntn, pl.n_dp, pl.g_sk, pl.est * 1e6);
+  nt2_run<0>(a, pl, M, Kall, nolog ? 0 : (kslices ? kslices : (pl.g_sk ? -pl.g_sk : 1)), st);
 }
 
 // ---- x W^T over the VALID rows of a ragged time-major batch ------------------------------------------------------------------------------
@@ -785,7 +721,7 @@ int gemm_nt2(int M, int N, int K, const float* A, long lda, const float* B, long
 // (pack_padded_sequence, e2e_encoder.py:129-131, enhance_model.py:120-123) and never computes the padded (t, b) rows; in the padded (T, B, .)
 // layout the recurrences run on, those rows are 15 % of a config-4 batch (lengths 0.7 T .. T).  The per-lane row offsets of the LDS-DMA
 // pipeline make the gather free: a lane's offset is map[row] * lda instead of row * lda, once per tile.  Rows not in the map are not touched:
-// re2e_fill_rows puts zeros there where a consumer reads all rows.  RE2E_EUNSUPPORTED when the pipeline does not take the shape (the caller
+// re2e_fill_rows puts zeros there where a consumer reads all rows.  RE2E_EUNSUPPORTED when the plan's route is not the pipeline (the caller
 // then runs the product over all physical rows).
 extern "C" int re2e_gemm_nt_rows(int Mv, int N, int K, const float* A, long lda, const float* B, long ldb, float* C, long ldc, const float* bias,
                                  const float* bias2, int act, float beta, const int* rowmap, int ident_rows, int phys_rows, void* workspace,
@@ -794,11 +730,16 @@ extern "C" int re2e_gemm_nt_rows(int Mv, int N, int K, const float* A, long lda,
   RE2E_CHECK_ARG(A && B && C && rowmap, "null operand");
   RE2E_CHECK_ARG(beta == 0.f || beta == 1.f, "beta must be 0 or 1");
   RE2E_CHECK_ARG(act >= 0 && act < RE2E_ACT_SIGMOID_MASK_MUL, "bad activation");
-  if (!gemm_nt2(Mv, N, K, A, lda, B, ldb, C, ldc, bias, bias2, act, beta, nullptr, nullptr, nullptr, 0, workspace, workspace_bytes, stream, rowmap,
-                phys_rows, ident_rows)) {
+  const bool ok16 = nt2_operands_ok(phys_rows, N, K, A, lda, B, ldb, C, ldc, bias, bias2);
+  const GemmIn in = {0, 1, Mv, N, K, act, ok16, ok16, ok16, true, re2e_stream_is_filler(stream), re2e_cu_count(), 0};
+  const GemmPlan p = plan_gemm(in);
+  int* tickets = nullptr;
+  // (the run-time fallback: a stream-K tail needs the caller's workspace for its slabs and a slice of the ticket pool)
+  if (p.route != kPipeline || (p.nt.g_sk && (!workspace || workspace_bytes < p.nt.bytes || !(tickets = nt2_ticket_slice())))) {
     re2e_set_error("re2e_gemm_nt_rows: shape not taken by the pipeline (Mv=%d N=%d K=%d)", Mv, N, K);
     return RE2E_EUNSUPPORTED;
   }
+  gemm_nt2(p.nt, Mv, N, K, A, lda, B, ldb, C, ldc, bias, bias2, act, beta, (float*)workspace, tickets, stream, rowmap, phys_rows, ident_rows, 0, 0);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }

@@ -669,144 +669,6 @@ __global__ __launch_bounds__(1024) void splitk_reduce_wide_kernel(const float* w
   C[off] = s;
 }
 
-template <class LA, class LB, class CF, bool VEC>
-int launch_igemm(const LA& la, const LB& lb, Epi ep, int K, hipStream_t st) {
-  constexpr bool TS = VEC && !LA::KMAJ && !LB::KMAJ;      // see igemm_kernel
-  constexpr int ASZ = (LA::KMAJ || TS) ? CF::BM * CF::LDK : CF::BK * (CF::BM + 8);
-  constexpr int BSZ = (LB::KMAJ || TS) ? CF::BN * CF::LDK : CF::BK * (CF::BN + 8);
-  size_t lds = (size_t)2 * (ASZ + BSZ) * sizeof(float);
-  static const size_t lds_floor = exp_env("RE2E_IGEMM_LDS_FLOOR") ? (size_t)atol(exp_env("RE2E_IGEMM_LDS_FLOOR")) : 0;   // occupancy experiments
-  if (lds < lds_floor) lds = lds_floor;
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&igemm_kernel<LA, LB, CF, VEC>), lds);
-  dim3 grid(cdiv(ep.M, CF::BM), cdiv(ep.N, CF::BN), ep.ncls ? ep.ncls : ep.nsplit);
-  static const bool nomem = exp_env("RE2E_IGEMM_NOMEM") != nullptr;
-  ep.nomem = nomem ? 1 : 0;
-  {
-    const char* zx = exp_env("RE2E_TN_XCD_KSLICE");      // experiments build: 0 = tiles keep their XCD for all slices (rounds 1-4)
-    ep.zx = (ep.nsplit > 1 && (ep.nsplit & 7) == 0 && !ep.ncls && !(zx && atoi(zx) == 0)) ? 1 : 0;
-  }
-  static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;   // tools/igemm_table.py joins this with a kernel trace
-  if (log_calls && !ep.nolog)
-    fprintf(stderr, "[igemm] A=%s B=%s tile=%dx%dx%d vec=%d M=%d N=%d K=%d splits=%d\n", LA::NAME, LB::NAME, CF::BM, CF::BN,
-            CF::BK, (int)VEC, ep.ncls ? ep.M * ep.ncls : ep.M, ep.N, K, ep.nsplit);   // M = rows of ALL parity classes of the launch
-  hipLaunchKernelGGL((igemm_kernel<LA, LB, CF, VEC>), grid, dim3(CF::THREADS), lds, st, la, lb, ep, K);
-  return 0;
-}
-
-constexpr int BKD = 16;              // k-tile: 16 keeps LDS <= 46 KB per block => 2-3 blocks per CU
-using C128 = Cfg<2, 2, 2, 2, BKD>;    // 128 x 128
-using C256x64 = Cfg<4, 1, 2, 2, BKD>;
-using C192x64 = Cfg<2, 2, 3, 1, BKD>;   // 576-row weight gradients (9 taps x 64 channels): 3 exact tiles instead of 2.25 of 256
-using C256x32 = Cfg<4, 1, 2, 1, 32>;   // BN=32 needs BK=32 to give every thread a B item
-using C32x128 = Cfg<1, 4, 1, 1, 32>;   // skinny (M<=32) GEMMs of the decoder loop, always split-K
-// tuning variants (tools/bench_gemm.py, env RE2E_IGEMM_VARIANT): 1 = BK 32, 2 = 8-wave 256x128 tile
-using C128b = Cfg<2, 2, 2, 2, 32>;
-using C256x64b = Cfg<4, 1, 2, 2, 32>;
-using C256x128 = Cfg<4, 2, 2, 2, 16>;
-using C64 = Cfg<2, 2, 1, 1, BKD>;      // 64 x 64: the row tail of a Linear forward whose last round of 256x128 tiles would be mostly empty
-
-inline int igemm_variant() {
-  static const int v = exp_env("RE2E_IGEMM_VARIANT") ? atoi(exp_env("RE2E_IGEMM_VARIANT")) : 0;
-  return v;
-}
-
-// big-tile launch.  WIDE = the 8-wave 256x128 tile is the measured default for this operand combination
-// (tools/bench_gemm.py on MI355X: +5..35 % for Linear-forward / weight-gradient GEMMs and conv forward /
-// data-gradient with Cout >= 128; the 4-wave 128x128 tile stays better for NN and conv weight-gradient).
-// RE2E_IGEMM_VARIANT = 1 (BK 32) / 2 (force wide) / 3 (force 128x128) override for tuning.  On a FILLER stream the 4-wave tile is
-// used whatever its stand-alone rate: training step 72.61 -> 72.32 ms (3 + 3 runs, one GPU session).
-// the 8-wave tile everywhere but on streams marked as fillers (core.hip: re2e_stream_role)
-inline bool wide_allowed(hipStream_t st) { return !re2e_stream_is_filler(st); }
-
-template <class LA, class LB, bool V, bool WIDE>
-void launch_big(const LA& la, const LB& lb, Epi& ep, int K, hipStream_t st) {
-  if constexpr (V) {
-    int v = igemm_variant();
-    if constexpr (!std::is_same<LA, DenseMG>::value && !std::is_same<LB, DenseMG>::value) {      // (DenseMG looks one 16-row k-tile ahead: BK 16 only)
-      if (v == 1) { launch_igemm<LA, LB, C128b, V>(la, lb, ep, K, st); return; }
-    }
-    bool wide = v == 2 ? true : (v == 3 ? false : (WIDE && ep.M >= 2048 && wide_allowed(st)));
-    if (wide) { launch_igemm<LA, LB, C256x128, V>(la, lb, ep, K, st); return; }
-  }
-  launch_igemm<LA, LB, C128, V>(la, lb, ep, K, st);
-}
-template <class LA, class LB, bool V>
-void launch_n64(const LA& la, const LB& lb, Epi& ep, int K, hipStream_t st) {
-  if constexpr (V) {
-    if (igemm_variant() == 1) { launch_igemm<LA, LB, C256x64b, V>(la, lb, ep, K, st); return; }
-  }
-  launch_igemm<LA, LB, C256x64, V>(la, lb, ep, K, st);
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// Workgroups of one tile shape that are resident at once: (workgroups per CU the register file admits -- 146 VGPRs => 3 waves per
-// SIMD for the 8-wave 256x128 tile, i.e. ONE workgroup; 2 x 4 waves for 128x128 and 256x64; 3 x 4 for the 112-register
-// 192x64 and the 256x32 tiles: csrc/build/igemm.resources) x CUs.  A device query would be exact, but the split count must be
-// the same in re2e_*_workspace_bytes and in the launch, so it is this table.
-inline long tile_slots(int bm, int bn) {
-  static const int cus = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
-  const int per_cu = (bm == 256 && bn == 128) ? 1 : ((bm == 192 && bn == 64) || (bm == 256 && bn == 32)) ? 3 : 2;
-  return (long)per_cu * cus;
-}
-
-// Split-K count of a product with few output tiles: the number of K slices (each >= 16 k-tiles) that minimises
-//   compute time / (fill of the resident slots over the rounds of workgroups)  +  slab traffic (one write + one read per slice)
-// -- not "about 768 workgroups": 9 tiles x 86 slices = 774 workgroups on 512 slots ran two rounds with the second 51 % empty
-// (conv2_2 weight gradient 3.0 -> 2.5 ms), 160 x 5 = 800 on 256 slots 3.1 rounds (BLSTMP layer-0 weight gradient 1.36 -> 1.14 ms).
-int pick_splits(int M, int N, int K, int bm, int bn) {
-  const long tiles = (long)cdiv(M, bm) * cdiv(N, bn);
-  const int nkt = cdiv(K, BKD);
-  const long slots = tile_slots(bm, bn);
-  if (tiles >= slots * 3 / 4 || nkt < 32) return 1;
-  long maxs = nkt / 16;          // >= 16 k-tiles (256 k) per split
-  if (maxs > 512) maxs = 512;
-  if (maxs < 1) maxs = 1;
-  const double compute = 2.0 * M * N * (double)K / 110e12;            // seconds at the engine's typical rate
-  long best_s = 1;
-  double best = 1e30;
-  for (long sp = 1; sp <= maxs; ++sp) {
-    const long w = tiles * sp, rounds = (w + slots - 1) / slots;
-    const double eff = (double)w / (double)(rounds * slots);
-    const double t = compute / eff + (sp > 1 ? (double)sp * M * N * 8.0 / 3e12 : 0.0);
-    if (t < best - 1e-12) { best = t; best_s = sp; }
-  }
-  static const int cap_kt = exp_env("RE2E_SPLIT_MAXKT") ? atoi(exp_env("RE2E_SPLIT_MAXKT")) : 0;   // experiment: bound a workgroup's lifetime
-  if (cap_kt > 0 && nkt / best_s > cap_kt) {
-    const long rounds = (nkt / best_s + cap_kt - 1) / cap_kt;         // keep the fill of the best choice: whole multiples of its workgroup count
-    long sp = best_s * rounds;
-    if (sp > maxs) sp = maxs;
-    best_s = sp;
-  }
-  return (int)best_s;
-}
-
-// skinny path (M <= 32): latency-bound, so spread K over many workgroups (>= 2 k-tiles of 32 each)
-int pick_splits_skinny(int N, int K) {
-  long tiles = cdiv(N, 128);
-  int nkt = cdiv(K, 32);
-  long want = (192 + tiles - 1) / tiles;
-  long maxs = nkt / 2;
-  long s = want < maxs ? want : maxs;
-  if (s < 1) s = 1;
-  if (s > 64) s = 64;
-  return (int)s;
-}
-
-inline bool use_skinny(int transa, int M, int N, int K) { return !transa && M <= 32 && K >= 128; }
-
-int gemm_splits(int transa, int transb, int M, int N, int K) {
-  if (use_skinny(transa, M, N, K)) return pick_splits_skinny(N, K);
-  if (transa && !transb) return pick_splits(M, N, K, M >= 2048 ? 256 : 128, 128);
-  // x W^T / dy W with few output tiles and a long K (decoder output layer gradient: 1312 x 300 x 4233)
-  if ((long)cdiv(M, 128) * cdiv(N, 128) <= 64) return pick_splits(M, N, K, 128, 128);
-  // many rows, few columns, long K (round 4: the CTC projection's input gradient 6400 x 512 x 4240 is 100 tiles of 256x128 on 256 CUs -- 39 % of
-  // the chip at 51 TFLOP/s, 0.55 ms on the path the main stream waits for at the encoder output): K slices fill the round
-  if (M >= 2048 && K >= 1024 && (long)cdiv(M, 256) * cdiv(N, 128) * 20 <= tile_slots(256, 128) * 11) return pick_splits(M, N, K, 256, 128);
-  return 1;
-}
-
 // ---- skinny GEMM (M <= 32) with the K split INSIDE the workgroup -------------------------------------------------------
 // The decoder loop's GEMMs (32 x 1200 x 512, 32 x 512 x 1200, ...) are latency-bound: the tiled engine ran them as split-K over
 // workgroups plus a reduce launch (6 + 1.7 + 6 us per product, 205 products per training step).  Here one workgroup owns a
@@ -944,7 +806,230 @@ __global__ __launch_bounds__(512) void skinny_gemm2_kernel(const float* __restri
   }
 }
 
+// ---- the engine's tiles: ONE table -----------------------------------------------------------------------------------------
+constexpr int BKD = 16;              // k-tile: 16 keeps LDS <= 46 KB per block => 2-3 blocks per CU
+using C128 = Cfg<2, 2, 2, 2, BKD>;      // 128 x 128, 4 waves
+using C256x128 = Cfg<4, 2, 2, 2, BKD>;  // 8 waves: the measured default of Linear-forward / weight-gradient GEMMs and conv forward / data gradient from 2048 rows
+using C256x64 = Cfg<4, 1, 2, 2, BKD>;
+using C192x64 = Cfg<2, 2, 3, 1, BKD>;   // 576-row weight gradients (9 taps x 64 channels): 3 exact tiles instead of 2.25 of 256
+using C256x32 = Cfg<4, 1, 2, 1, 32>;    // BN=32 needs BK=32 to give every thread a B item
+using C32x128 = Cfg<1, 4, 1, 1, 32>;    // skinny (M<=32) GEMMs with an epilogue the in-workgroup kernel lacks, always split-K
+using C64 = Cfg<2, 2, 1, 1, BKD>;       // 64 x 64: the row tail of a Linear forward whose last round of 256x128 tiles would be mostly empty
+// X(id, configuration, workgroups resident per CU).  Residency is what the register file admits (csrc/build/igemm.resources): 146 VGPRs => 3 waves
+// per SIMD for the 8-wave tile, i.e. ONE workgroup; 2 x 4 waves for 128x128 and 256x64; 3 x 4 for the 112-register 192x64 and 256x32 tiles; >= 4
+// of the 64x64 tail.  A device query would be exact, but the split count must be the same in re2e_*_workspace_bytes and in the launch, so it
+// is this table.  The plans name a row; launch_tile expands the rows that are instantiated for an operand pair.  (Rejected rows -- BK 32 forms
+// of 128x128 and 256x64 -- are in DESIGN.md Appendix A.)
+#define RE2E_ENGINE_TILES(X) X(kT128, C128, 2) X(kT256x128, C256x128, 1) X(kT256x64, C256x64, 2) X(kT192x64, C192x64, 3) X(kT256x32, C256x32, 3) X(kT32x128, C32x128, 2) X(kT64, C64, 4)
+#define RE2E_TILE_ID(ID, CF, PER_CU) ID,
+enum EngineTile { RE2E_ENGINE_TILES(RE2E_TILE_ID) };
+#undef RE2E_TILE_ID
+struct TileRow { int bm, bn, bk, per_cu; };
+#define RE2E_TILE_ROW(ID, CF, PER_CU) {CF::BM, CF::BN, CF::BK, PER_CU},
+constexpr TileRow kTiles[] = {RE2E_ENGINE_TILES(RE2E_TILE_ROW)};
+#undef RE2E_TILE_ROW
+constexpr unsigned bit(EngineTile t) { return 1u << t; }
+
+// Experiment switches of this file (experiments build; the shipped library answers "unset"), all read here.  They choose between SHIPPED forms for
+// same-session A/B runs: RE2E_NO_SKINNY_GEMM (M <= 32 products on the 32x128 engine tile), RE2E_NO_ROW_TAIL, RE2E_NO_THIN (Cin == 1 / Cout == 1
+// convolutions through the implicit GEMM), RE2E_TN_XCD_KSLICE = 0 (tiles keep their XCD for all K slices, rounds 1-4), RE2E_IGEMM_NOMEM.
+struct EngineSwitches { bool no_skinny_wg, no_row_tail, no_thin, no_xcd_kslice, nomem; };
+EngineSwitches engine_switches() {      // (read at every call: tools/bench_tn_xcd.py flips one between calls)
+  const char* zx = exp_env("RE2E_TN_XCD_KSLICE");
+  return {exp_env("RE2E_NO_SKINNY_GEMM") != nullptr, exp_env("RE2E_NO_ROW_TAIL") != nullptr, exp_env("RE2E_NO_THIN") != nullptr, zx && atoi(zx) == 0,
+          exp_env("RE2E_IGEMM_NOMEM") != nullptr};
+}
+
+template <class LA, class LB, class CF, bool VEC>
+void launch_igemm(const LA& la, const LB& lb, Epi ep, int K, hipStream_t st) {
+  constexpr bool TS = VEC && !LA::KMAJ && !LB::KMAJ;      // see igemm_kernel
+  constexpr int ASZ = (LA::KMAJ || TS) ? CF::BM * CF::LDK : CF::BK * (CF::BM + 8);
+  constexpr int BSZ = (LB::KMAJ || TS) ? CF::BN * CF::LDK : CF::BK * (CF::BN + 8);
+  const size_t lds = (size_t)2 * (ASZ + BSZ) * sizeof(float);
+  static LdsLimit lim;
+  lim.ensure(reinterpret_cast<const void*>(&igemm_kernel<LA, LB, CF, VEC>), lds);
+  dim3 grid(cdiv(ep.M, CF::BM), cdiv(ep.N, CF::BN), ep.ncls ? ep.ncls : ep.nsplit);
+  const EngineSwitches sw = engine_switches();
+  ep.nomem = sw.nomem ? 1 : 0;
+  ep.zx = (ep.nsplit > 1 && (ep.nsplit & 7) == 0 && !ep.ncls && !sw.no_xcd_kslice) ? 1 : 0;
+  static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;   // tools/igemm_table.py joins this with a kernel trace
+  if (log_calls && !ep.nolog)
+    fprintf(stderr, "[igemm] A=%s B=%s tile=%dx%dx%d vec=%d M=%d N=%d K=%d splits=%d\n", LA::NAME, LB::NAME, CF::BM, CF::BN,
+            CF::BK, (int)VEC, ep.ncls ? ep.M * ep.ncls : ep.M, ep.N, K, ep.nsplit);   // M = rows of ALL parity classes of the launch
+  hipLaunchKernelGGL((igemm_kernel<LA, LB, CF, VEC>), grid, dim3(CF::THREADS), lds, st, la, lb, ep, K);
+}
+
+// Enqueue the row of the tile table a plan names.  BUILT: the rows instantiated for this operand pair; a plan that names another one is a bug.
+template <class LA, class LB, bool V, unsigned BUILT>
+void launch_tile(int tile, const LA& la, const LB& lb, const Epi& ep, int K, hipStream_t st) {
+#define RE2E_TILE_CASE(ID, CF, PER_CU) \
+  if constexpr ((BUILT >> ID) & 1) { if (tile == ID) { launch_igemm<LA, LB, CF, V>(la, lb, ep, K, st); return; } }
+  RE2E_ENGINE_TILES(RE2E_TILE_CASE)
+#undef RE2E_TILE_CASE
+  fprintf(stderr, "re2e: engine plan names tile %d, which is not built for A=%s B=%s vec=%d\n", tile, LA::NAME, LB::NAME, (int)V);
+  abort();
+}
+
+// The big tile of a product.  wide_form: the 8-wave 256x128 tile is the measured default for this operand combination (tools/bench_gemm.py on
+// MI355X: +5..35 % for Linear-forward / weight-gradient GEMMs and conv forward / data-gradient with Cout >= 128; the 4-wave 128x128 tile stays
+// better for NN and conv weight-gradient).  It needs 16-byte loads and 2048 rows.  On a FILLER stream (core.hip: re2e_stream_role) the 4-wave tile
+// is used whatever its stand-alone rate: training step 72.61 -> 72.32 ms (3 + 3 runs, one GPU session).
+inline EngineTile big_tile(bool wide_form, bool vec, int M, bool filler) { return wide_form && vec && M >= 2048 && !filler ? kT256x128 : kT128; }
+template <bool V>
+constexpr unsigned big_built(bool wide_form) { return bit(kT128) | (V && wide_form ? bit(kT256x128) : 0u); }
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool ld16(const void* p, long ld) { return aligned16(p) && ld % 4 == 0; }      // a 16-byte loadable operand: aligned base, leading dimension of whole float4s
+
+inline long tile_slots(EngineTile t, int cus) { return (long)kTiles[t].per_cu * cus; }      // workgroups of one tile shape that are resident at once
+
+// Split-K count of a product with few output tiles: the number of K slices (each >= 16 k-tiles) that minimises
+//   compute time / (fill of the resident slots over the rounds of workgroups)  +  slab traffic (one write + one read per slice)
+// -- not "about 768 workgroups": 9 tiles x 86 slices = 774 workgroups on 512 slots ran two rounds with the second 51 % empty
+// (conv2_2 weight gradient 3.0 -> 2.5 ms), 160 x 5 = 800 on 256 slots 3.1 rounds (BLSTMP layer-0 weight gradient 1.36 -> 1.14 ms).
+int pick_splits(int M, int N, int K, EngineTile t, int cus) {
+  const long tiles = (long)cdiv(M, kTiles[t].bm) * cdiv(N, kTiles[t].bn);
+  const int nkt = cdiv(K, BKD);
+  const long slots = tile_slots(t, cus);
+  if (tiles >= slots * 3 / 4 || nkt < 32) return 1;
+  long maxs = nkt / 16;          // >= 16 k-tiles (256 k) per split
+  if (maxs > 512) maxs = 512;
+  if (maxs < 1) maxs = 1;
+  const double compute = 2.0 * M * N * (double)K / 110e12;            // seconds at the engine's typical rate
+  long best_s = 1;
+  double best = 1e30;
+  for (long sp = 1; sp <= maxs; ++sp) {
+    const long w = tiles * sp, rounds = (w + slots - 1) / slots;
+    const double eff = (double)w / (double)(rounds * slots);
+    const double t = compute / eff + (sp > 1 ? (double)sp * M * N * 8.0 / 3e12 : 0.0);
+    if (t < best - 1e-12) { best = t; best_s = sp; }
+  }
+  return (int)best_s;
+}
+
+// skinny path (M <= 32): latency-bound, so spread K over many workgroups (>= 2 k-tiles of 32 each)
+int pick_splits_skinny(int N, int K) {
+  long tiles = cdiv(N, 128);
+  int nkt = cdiv(K, 32);
+  long want = (192 + tiles - 1) / tiles;
+  long maxs = nkt / 2;
+  long s = want < maxs ? want : maxs;
+  if (s < 1) s = 1;
+  if (s > 64) s = 64;
+  return (int)s;
+}
+
+inline bool use_skinny(int transa, int M, int K) { return !transa && M <= 32 && K >= 128; }
+
+// Split count of a dense product: a function of the form, the shape and the chip, NOT of the stream -- re2e_gemm_workspace_bytes has no stream.  So
+// dy^T x from 2048 rows is sized for the 256x128 tile also where a filler stream then runs 128x128 tiles with that count.
+int gemm_splits(int transa, int transb, int M, int N, int K, int cus) {
+  if (use_skinny(transa, M, K)) return pick_splits_skinny(N, K);
+  if (transa && !transb) return pick_splits(M, N, K, M >= 2048 ? kT256x128 : kT128, cus);
+  // x W^T / dy W with few output tiles and a long K (decoder output layer gradient: 1312 x 300 x 4233)
+  if ((long)cdiv(M, 128) * cdiv(N, 128) <= 64) return pick_splits(M, N, K, kT128, cus);
+  // many rows, few columns, long K (round 4: the CTC projection's input gradient 6400 x 512 x 4240 is 100 tiles of 256x128 on 256 CUs -- 39 % of
+  // the chip at 51 TFLOP/s, 0.55 ms on the path the main stream waits for at the encoder output): K slices fill the round
+  if (M >= 2048 && K >= 1024 && (long)cdiv(M, 256) * cdiv(N, 128) * 20 <= tile_slots(kT256x128, cus) * 11) return pick_splits(M, N, K, kT256x128, cus);
+  return 1;
+}
+
+// Round-filling row split of a Linear forward: 12800 x 2048 is 800 tiles of 256x128 on 256 resident workgroups -- 3.1 rounds, the 4th one 12 %
+// full.  The rows of the last, mostly empty round go to a second launch of 64x64 tiles instead (256 small workgroups: every CU gets one), the
+// launch of the big tiles ends on a full round.  Returns the rows that stay with the 256x128 tiles; M = no split.
+int row_tail_split(int M, int N, int cus) {
+  if (M < 2048) return M;                                   // big_tile uses the wide tile from 2048 rows
+  const long tn = cdiv(N, 128), tm = cdiv(M, 256), slots = tile_slots(kT256x128, cus);
+  const long total = tm * tn, full = total / slots, rem = total % slots;
+  if (full < 1 || rem == 0 || rem * 2 >= slots) return M;
+  const long tm_main = full * slots / tn;                   // whole tile rows inside the full rounds
+  if (tm_main * 256 < 2048 || tm_main >= tm) return M;     // (big_tile keeps the wide tile from 2048 rows)
+  const long m1 = tm_main * 256, tail_wgs = (long)cdiv(M - (int)m1, 64) * cdiv(N, 64);
+  // a 64x64 workgroup does 1/8 of a big tile's work at about half its rate: a round of them costs ~0.25 big rounds
+  const double t_split = (double)cdiv((int)(tm_main * tn), (int)slots) + 0.25 * (double)cdiv((int)tail_wgs, (int)tile_slots(kT64, cus));
+  return t_split + 0.2 < (double)(full + 1) ? (int)m1 : M;
+}
+
+// The engine's part of a dense plan: split count (a K-sliced batch: the caller's slices, whose slabs are the result), tile, row tail.
+void plan_engine(const GemmIn& in, GemmPlan& p) {
+  const bool nt = !in.transa && in.transb, tn = in.transa && !in.transb, mask = in.act == RE2E_ACT_SIGMOID_MASK_MUL;
+  p.route = kEngine;
+  p.splits = in.kslices ? in.kslices : (mask ? 1 : gemm_splits(in.transa, in.transb, in.M, in.N, in.K, in.cus));      // mask epilogue: never split
+  p.need_bytes = (!in.kslices && p.splits > 1) ? (size_t)p.splits * in.M * in.N * sizeof(float) : 0;
+  // 16-byte vector loads need aligned bases, leading dimensions that are multiples of 4 and no
+  // float4 straddling a bound (k-contiguous operands: K % 4; row-contiguous operands: rows % 4)
+  p.vec = in.a16 && (in.transa ? in.M % 4 == 0 : in.K % 4 == 0) && in.b16 && (in.transb ? in.K % 4 == 0 : in.N % 4 == 0);
+  p.m1 = in.M;
+  if (!in.kslices && use_skinny(in.transa, in.M, in.K)) { p.tile = kT32x128; return; }
+  if (nt && p.vec && !engine_switches().no_row_tail && p.splits == 1 && !mask && !in.filler) p.m1 = row_tail_split(in.M, in.N, in.cus);
+  p.tile = big_tile(nt || tn, p.vec, p.m1, in.filler);
+}
+
 }  // namespace
+
+// ---- which kernel serves a dense product: ONE plan per call, made before anything is enqueued ------------------------------------------------
+// plan_gemm is a pure host function of GemmIn (common.h): form, shape, which operands are 16-byte loadable, activation, row map, the stream's
+// role and the chip's CU count.  re2e_gemm_workspace_bytes, re2e_gemm, re2e_gemm_nt_rows, re2e_gemm_tn_rows, gemm_kslices and gemm_kslices_tn
+// enqueue exactly what it names; re2e_gemm_plan prints it (tests/test_abi.py holds the table of expected plans).  In order:
+//   skinny_wg  M <= 32 rows, 64 <= K <= 8192, no activation: skinny_gemm_kernel, the K split inside the workgroup
+//   pipeline   x W^T from 256 rows with operands gemm_nt.hip's LDS-DMA kernel can load: a row of its variant table, whole tiles + stream-K tail
+//   engine     everything else: a row of the tile table above, split-K + reduce where few tiles meet a long K, the 64x64 row tail
+GemmPlan plan_gemm(const GemmIn& in, bool with_workspace) {
+  GemmPlan p;
+  memset(&p, 0, sizeof(p));
+  const bool nt = !in.transa && in.transb;
+  // the stream-independent part: what re2e_gemm_workspace_bytes answers (the launches do not ask for it).  Slabs of the engine's split (which the
+  // pipeline's run-time fallback may need) or of the pipeline's stream-K tail on either stream role, whichever is larger.
+  if (with_workspace && !in.kslices) {
+    const int s = gemm_splits(in.transa, in.transb, in.M, in.N, in.K, in.cus);
+    p.ws_bytes = s > 1 ? (size_t)s * in.M * in.N * sizeof(float) : 0;
+    if (nt && in.K % 4 == 0)
+      for (int four_wave = 0; four_wave < 2; ++four_wave) {
+        const size_t b = nt2_plan(in.M, in.N, in.K, four_wave != 0, in.cus, true).bytes;
+        if (b > p.ws_bytes) p.ws_bytes = b;
+      }
+  }
+  // the stream-dependent part: route and tile
+  const int Ks = in.kslices ? in.K / in.kslices : in.K;
+  if (!engine_switches().no_skinny_wg && !in.kslices && !in.rowmap && !in.transa && in.M <= 32 && in.K >= 64 && in.K <= 8192 && in.act == RE2E_ACT_NONE) {
+    p.route = kSkinnyWg;
+    p.vec = in.K % 4 == 0 && in.a16 && (!in.transb || in.b16);
+    p.m1 = in.M;
+    return p;
+  }
+  if (nt && in.pipe16 && Ks % 4 == 0 && in.N % 4 == 0 && in.M >= 256 && in.act != RE2E_ACT_SIGMOID_MASK_MUL && in.kslices <= 4096) {
+    p.nt = nt2_plan(in.M, in.N, Ks, in.filler || in.rowmap, in.cus, !in.kslices);
+    if (p.nt.variant) {
+      p.route = kPipeline;
+      p.vec = true;
+      p.m1 = in.M;
+      if (in.kslices) p.nt.n_dp *= in.kslices;      // whole tiles, counted over the slices
+      p.need_bytes = p.nt.bytes;
+      return p;
+    }
+  }
+  plan_engine(in, p);
+  return p;
+}
+
+static const char* const kRouteText[] = {"skinny_wg", "pipeline", "engine"};
+
+extern "C" int re2e_gemm_plan(int transa, int transb, int M, int N, int K, int a16, int b16, int c16, int act, int rowmap, int filler, int cus,
+                              char* out, size_t out_bytes) {
+  RE2E_CHECK_ARG(M > 0 && N > 0 && K > 0 && cus >= 0 && out && out_bytes > 0 && !(transa && transb), "bad argument");
+  RE2E_CHECK_ARG(act >= 0 && act <= RE2E_ACT_SIGMOID_MASK_MUL, "bad activation");
+  if (cus == 0) cus = re2e_cu_count();
+  const GemmIn in = {transa, transb, M, N, K, act, a16 != 0, b16 != 0, a16 && b16 && c16, rowmap != 0, filler != 0, cus, 0};
+  const GemmPlan p = plan_gemm(in, true);
+  int n = snprintf(out, out_bytes, "route=%s vec=%d", kRouteText[p.route], (int)p.vec);
+  if (p.route == kPipeline && n > 0 && (size_t)n < out_bytes)
+    n += snprintf(out + n, out_bytes - n, " variant=%d tile=%dx%dx%d n_dp=%d g_sk=%d", p.nt.variant, p.nt.bm, p.nt.bn, p.nt.bk, p.nt.n_dp, p.nt.g_sk);
+  if (p.route == kEngine && n > 0 && (size_t)n < out_bytes)
+    n += snprintf(out + n, out_bytes - n, " tile=%dx%dx%d splits=%d m1=%d", kTiles[p.tile].bm, kTiles[p.tile].bn, kTiles[p.tile].bk, p.splits, p.m1);
+  if (n > 0 && (size_t)n < out_bytes) n += snprintf(out + n, out_bytes - n, " need=%zu ws=%zu", p.need_bytes, p.ws_bytes);
+  RE2E_CHECK_ARG(n > 0 && (size_t)n < out_bytes, "out_bytes too small");
+  return RE2E_OK;
+}
 
 // ============================================================================================
 // C ABI
@@ -961,99 +1046,82 @@ extern "C" int re2e_gemm_skinny2(int M, int K, const float* A, long lda, const f
 
 extern "C" size_t re2e_gemm_workspace_bytes(int transa, int transb, int M, int N, int K) {
   if (transa && transb) return 0;
-  int s = gemm_splits(transa, transb, M, N, K);
-  size_t b = s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
-  if (!transa && transb) { const size_t b2 = gemm_nt2_workspace_bytes(M, N, K); if (b2 > b) b = b2; }
-  if (transa && !transb) { const size_t b2 = gemm_tn2_workspace_bytes(M, N, K); if (b2 > b) b = b2; }
-  return b;
+  const GemmIn in = {transa, transb, M, N, K, RE2E_ACT_NONE, true, true, true, false, false, re2e_cu_count(), 0};
+  return plan_gemm(in, true).ws_bytes;
 }
 
 // bytes spanned by a (outer x inner) row-major view with leading dimension ld
 static inline unsigned kbytes(long outer, long ld, long inner) { return (unsigned)(((outer - 1) * ld + inner) * 4); }
 static inline bool fits32(long outer, long ld, long inner) { return ((outer - 1) * ld + inner) * 4 < 0xFFFFFFF0L; }
 
-// Rows that stay with the 256x128 tiles of a Linear forward (see gemm_dispatch); M = no split.
-static int row_tail_split(int M, int N) {
-  if (M < 2048) return M;                                   // launch_big uses the wide tile from 2048 rows
-  const long tn = cdiv(N, 128), tm = cdiv(M, 256), slots = tile_slots(256, 128);
-  const long total = tm * tn, full = total / slots, rem = total % slots;
-  if (full < 1 || rem == 0 || rem * 2 >= slots) return M;
-  const long tm_main = full * slots / tn;                   // whole tile rows inside the full rounds
-  if (tm_main * 256 < 2048 || tm_main >= tm) return M;     // (launch_big keeps the wide tile from 2048 rows)
-  const long m1 = tm_main * 256, tail_wgs = (long)cdiv(M - (int)m1, 64) * cdiv(N, 64);
-  // a 64x64 workgroup does 1/8 of a big tile's work at about half its rate: a round of them costs ~0.25 big rounds
-  const double t_split = (double)cdiv((int)(tm_main * tn), (int)slots) + 0.25 * (double)cdiv((int)tail_wgs, 4 * (int)slots);   // >= 4 of them per CU
-  return t_split + 0.2 < (double)(full + 1) ? (int)m1 : M;
+// Enqueue an engine plan: the tile launch (two with a row tail) and, for a split product, the reduce that applies bias and activation.
+// LA / LB are built by the caller's form; slabs: the workspace of a split product (a K-sliced batch passes its output and gets no reduce).
+template <class LA, class LB, bool V, unsigned BUILT>
+static void run_engine(const GemmPlan& p, const LA& la, const LB& lb, Epi& ep, int K, float* slabs, bool reduce, hipStream_t st) {
+  ep.nsplit = p.splits;
+  if (p.splits > 1) ep.ws = slabs;
+  launch_tile<LA, LB, V, BUILT>(p.tile, la, lb, ep, K, st);
+  if (reduce && p.splits > 1)
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv((long)ep.M * ep.N, 256)), dim3(256), 0, st, (const float*)slabs, p.splits, ep.M, ep.N, ep.C, ep.ldc,
+                       ep.beta, 0, 0, 0, ep.bias, ep.bias2, ep.act);
 }
 
 template <bool V>
-static void gemm_dispatch(int transa, int transb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, Epi& ep,
-                          hipStream_t st) {
-  const bool skinny = use_skinny(transa, M, N, K);
+static void gemm_engine(const GemmPlan& p, int transa, int transb, int M, int N, int K, const float* A, long lda, const float* B, long ldb, Epi& ep,
+                        float* slabs, bool reduce, hipStream_t st) {
   if (!transa && transb) {          // C = A[M,K] * B[N,K]^T   (Linear forward)
-    DenseK la{A, kbytes(M, lda, K), lda, M, K};
+    constexpr unsigned BUILT = big_built<V>(true) | bit(kT32x128);
     DenseK lb{B, kbytes(N, ldb, K), ldb, N, K};
-    if (skinny) launch_igemm<DenseK, DenseK, C32x128, V>(la, lb, ep, K, st);
-    else {
-      // Round-filling row split: 12800 x 2048 is 800 tiles of 256x128 on 256 resident workgroups -- 3.1 rounds, the 4th one
-      // 12 % full.  The rows of the last, mostly empty round go to a second launch of 64x64 tiles instead (256 small
-      // workgroups: every CU gets one), the launch of the big tiles ends on a full round.
-      static const bool no_tail = exp_env("RE2E_NO_ROW_TAIL") != nullptr;
-      const int m1 = (V && !no_tail && igemm_variant() == 0 && ep.nsplit == 1 && ep.act != RE2E_ACT_SIGMOID_MASK_MUL && wide_allowed(st)) ? row_tail_split(M, N) : M;
-      if (m1 < M) {
-        Epi e1 = ep, e2 = ep;
-        e1.M = m1;
-        DenseK la1{A, kbytes(m1, lda, K), lda, m1, K};
-        launch_big<DenseK, DenseK, V, true>(la1, lb, e1, K, st);
-        e2.M = M - m1; e2.C = ep.C + (long)m1 * ep.ldc;
-        DenseK la2{A + (long)m1 * lda, kbytes(M - m1, lda, K), lda, M - m1, K};
-        launch_igemm<DenseK, DenseK, C64, V>(la2, lb, e2, K, st);
-      } else launch_big<DenseK, DenseK, V, true>(la, lb, ep, K, st);
+    DenseK la{A, kbytes(p.m1, lda, K), lda, p.m1, K};
+    ep.M = p.m1;
+    run_engine<DenseK, DenseK, V, BUILT>(p, la, lb, ep, K, slabs, reduce, st);
+    if constexpr (V) {
+      if (p.m1 < M) {                 // the row tail (plans with a tail have one split)
+        Epi e2 = ep;
+        e2.M = M - p.m1; e2.C = ep.C + (long)p.m1 * ep.ldc;
+        DenseK la2{A + (long)p.m1 * lda, kbytes(M - p.m1, lda, K), lda, M - p.m1, K};
+        launch_tile<DenseK, DenseK, V, bit(kT64)>(kT64, la2, lb, e2, K, st);
+      }
     }
   } else if (!transa && !transb) {  // C = A[M,K] * B[K,N]     (input gradient)
     DenseK la{A, kbytes(M, lda, K), lda, M, K};
     DenseM lb{B, kbytes(K, ldb, N), ldb, N, K};
-    if (skinny) launch_igemm<DenseK, DenseM, C32x128, V>(la, lb, ep, K, st);
-    else launch_big<DenseK, DenseM, V, false>(la, lb, ep, K, st);
+    run_engine<DenseK, DenseM, V, big_built<V>(false) | bit(kT32x128)>(p, la, lb, ep, K, slabs, reduce, st);
   } else {                          // C = A[K,M]^T * B[K,N]   (weight gradient)
     DenseM la{A, kbytes(K, lda, M), lda, M, K};
     DenseM lb{B, kbytes(K, ldb, N), ldb, N, K};
-    launch_big<DenseM, DenseM, V, true>(la, lb, ep, K, st);
+    run_engine<DenseM, DenseM, V, big_built<V>(true)>(p, la, lb, ep, K, slabs, reduce, st);
   }
 }
 
-// K-sliced x W^T product: out[z][M][N] = A[:, z*K/ns : (z+1)*K/ns] . B[:, same]^T for z < ns -- the engine's split-K launch with the
-// caller's slice count and WITHOUT the reduce pass: the slabs are the result (a batch of ns products whose operands are interleaved
-// along K; wino44.hip).  K / ns must be a multiple of the k-tile.
+// K-sliced product: out[z][M][N] = A[:, z*K/ns : (z+1)*K/ns] . B[:, same]^T for z < ns -- a batch of ns products whose operands are interleaved
+// along K (wino44.hip): the pipeline with its tiles counted over the slices, or the engine's split-K launch with the caller's slice count and
+// WITHOUT the reduce pass: the slabs are the result.  K / ns must be a multiple of the k-tile.  transa: the same for A^T B (weight-gradient
+// form): out[z][M][N] = A[zK/ns : (z+1)K/ns, :M]^T . B[same rows, :N]; A (K, M), B (K, N) row-major.
+static int gemm_kslices_impl(int transa, int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog) {
+  const bool ok = transa ? (M % 4 == 0 && N % 4 == 0 && fits32(K, lda, M) && fits32(K, ldb, N)) : (fits32(M, lda, K) && fits32(N, ldb, K));
+  if (ns < 2 || K % ns || (K / ns) % BKD || !ld16(A, lda) || !ld16(B, ldb) || !ok) {
+    re2e_set_error("gemm_kslices%s: unsupported slicing (M=%d N=%d K=%d ns=%d)", transa ? "_tn" : "", M, N, K, ns);
+    return RE2E_EUNSUPPORTED;
+  }
+  const GemmIn in = {transa, !transa, M, N, K, RE2E_ACT_NONE, true, true, !transa && nt2_operands_ok(M, N, K, A, lda, B, ldb, out, N, nullptr, nullptr),
+                     false, re2e_stream_is_filler(st), re2e_cu_count(), ns};
+  const GemmPlan p = plan_gemm(in);
+  if (p.route == kPipeline) {
+    gemm_nt2(p.nt, M, N, K / ns, A, lda, B, ldb, out, N, nullptr, nullptr, RE2E_ACT_NONE, 0.f, nullptr, nullptr, st, nullptr, 0, 0, ns, nolog);
+    return RE2E_OK;
+  }
+  Epi ep;
+  memset(&ep, 0, sizeof(ep));
+  ep.C = out; ep.ldc = N; ep.M = M; ep.N = N; ep.act = RE2E_ACT_NONE; ep.nolog = nolog;
+  gemm_engine<true>(p, transa, !transa, M, N, K, A, lda, B, ldb, ep, out, false, st);
+  return RE2E_OK;
+}
 int gemm_kslices(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog) {
-  if (ns < 2 || K % ns || (K / ns) % BKD || !aligned16(A) || !aligned16(B) || lda % 4 || ldb % 4 || !fits32(M, lda, K) || !fits32(N, ldb, K)) {
-    re2e_set_error("gemm_kslices: unsupported slicing (M=%d N=%d K=%d ns=%d)", M, N, K, ns);
-    return RE2E_EUNSUPPORTED;
-  }
-  if (gemm_nt2_kslices(M, N, K / ns, ns, A, lda, B, ldb, out, st, nolog)) return RE2E_OK;      // gemm_nt.hip: the LDS-DMA pipeline, tiles counted over the slices
-  Epi ep;
-  memset(&ep, 0, sizeof(ep));
-  ep.C = out; ep.ldc = N; ep.M = M; ep.N = N; ep.act = RE2E_ACT_NONE; ep.ws = out; ep.nsplit = ns; ep.nolog = nolog;
-  DenseK la{A, kbytes(M, lda, K), lda, M, K};
-  DenseK lb{B, kbytes(N, ldb, K), ldb, N, K};
-  launch_big<DenseK, DenseK, true, true>(la, lb, ep, K, st);
-  return RE2E_OK;
+  return gemm_kslices_impl(0, M, N, K, ns, A, lda, B, ldb, out, st, nolog);
 }
-
-// The same for A^T B (weight-gradient form): out[z][M][N] = A[zK/ns : (z+1)K/ns, :M]^T . B[same rows, :N]; A (K, M), B (K, N) row-major.
 int gemm_kslices_tn(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog) {
-  if (ns < 2 || K % ns || (K / ns) % BKD || M % 4 || N % 4 || !aligned16(A) || !aligned16(B) || lda % 4 || ldb % 4 || !fits32(K, lda, M) ||
-      !fits32(K, ldb, N)) {
-    re2e_set_error("gemm_kslices_tn: unsupported slicing (M=%d N=%d K=%d ns=%d)", M, N, K, ns);
-    return RE2E_EUNSUPPORTED;
-  }
-  Epi ep;
-  memset(&ep, 0, sizeof(ep));
-  ep.C = out; ep.ldc = N; ep.M = M; ep.N = N; ep.act = RE2E_ACT_NONE; ep.ws = out; ep.nsplit = ns; ep.nolog = nolog;
-  DenseM la{A, kbytes(K, lda, M), lda, M, K};
-  DenseM lb{B, kbytes(K, ldb, N), ldb, N, K};
-  launch_big<DenseM, DenseM, true, true>(la, lb, ep, K, st);
-  return RE2E_OK;
+  return gemm_kslices_impl(1, M, N, K, ns, A, lda, B, ldb, out, st, nolog);
 }
 
 extern "C" int re2e_gemm(int transa, int transb, int M, int N, int K, const float* A, long lda, const float* B,
@@ -1070,44 +1138,29 @@ extern "C" int re2e_gemm(int transa, int transb, int M, int N, int K, const floa
     return RE2E_EUNSUPPORTED;
   }
   RE2E_CHECK_ARG(fits32(transa ? K : M, lda, transa ? M : K) && fits32(transb ? N : K, ldb, transb ? K : N), "operand larger than 4 GiB");
-  static const bool no_skinny_kernel = exp_env("RE2E_NO_SKINNY_GEMM") != nullptr;
-  if (!no_skinny_kernel && !transa && M <= 32 && K >= 64 && K <= 8192 && act == RE2E_ACT_NONE) {
-    const bool v = K % 4 == 0 && aligned16(A) && lda % 4 == 0 && (!transb || (aligned16(B) && ldb % 4 == 0));
+  const GemmIn in = {transa, transb, M, N, K, act, ld16(A, lda), ld16(B, ldb),
+                     !transa && transb && nt2_operands_ok(M, N, K, A, lda, B, ldb, C, ldc, bias, bias2), false, re2e_stream_is_filler(stream), re2e_cu_count(), 0};
+  GemmPlan p = plan_gemm(in);
+  int* tickets = nullptr;
+  // The one run-time fallback: a stream-K tail needs the caller's workspace for its slabs and a slice of the ticket pool; without them the
+  // product runs on the engine's plan.
+  if (p.route == kPipeline && p.nt.g_sk && (!workspace || workspace_bytes < p.nt.bytes || !(tickets = nt2_ticket_slice()))) plan_engine(in, p);
+  if (p.route == kSkinnyWg) {
     const dim3 g(cdiv(N, 32)), t(512);
-    if (transb && v) hipLaunchKernelGGL((skinny_gemm_kernel<true, true>), g, t, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, bias, bias2, beta);
+    if (transb && p.vec) hipLaunchKernelGGL((skinny_gemm_kernel<true, true>), g, t, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, bias, bias2, beta);
     else if (transb) hipLaunchKernelGGL((skinny_gemm_kernel<true, false>), g, t, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, bias, bias2, beta);
-    else if (v) hipLaunchKernelGGL((skinny_gemm_kernel<false, true>), g, t, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, bias, bias2, beta);
+    else if (p.vec) hipLaunchKernelGGL((skinny_gemm_kernel<false, true>), g, t, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, bias, bias2, beta);
     else hipLaunchKernelGGL((skinny_gemm_kernel<false, false>), g, t, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, bias, bias2, beta);
-    RE2E_LAUNCH_CHECK();
-    return RE2E_OK;
-  }
-  if (!transa && transb && gemm_nt2(M, N, K, A, lda, B, ldb, C, ldc, bias, bias2, act, beta, mul, mask_out, lens_dev, T, workspace, workspace_bytes, stream)) {
-    RE2E_LAUNCH_CHECK();
-    return RE2E_OK;
-  }
-  if (transa && !transb && gemm_tn2(M, N, K, A, lda, B, ldb, C, ldc, bias, bias2, act, beta, workspace, workspace_bytes, stream)) {
-    RE2E_LAUNCH_CHECK();
-    return RE2E_OK;
-  }
-  Epi ep;
-  memset(&ep, 0, sizeof(ep));
-  ep.C = C; ep.ldc = ldc; ep.M = M; ep.N = N; ep.bias = bias; ep.bias2 = bias2; ep.act = act; ep.beta = beta;
-  ep.mul = mul; ep.mask_out = mask_out; ep.lens = lens_dev; ep.T = T; ep.nsplit = 1;
-  const int s = act == RE2E_ACT_SIGMOID_MASK_MUL ? 1 : gemm_splits(transa, transb, M, N, K);   // mask epilogue: never split
-  if (s > 1) {
-    RE2E_CHECK_ARG(workspace && workspace_bytes >= (size_t)s * M * N * sizeof(float), "workspace too small");
-    ep.ws = (float*)workspace; ep.nsplit = s;
-  }
-  // 16-byte vector loads need aligned bases, leading dimensions that are multiples of 4 and no
-  // float4 straddling a bound (k-contiguous operands: K % 4; row-contiguous operands: rows % 4)
-  bool va = aligned16(A) && lda % 4 == 0 && (transa ? M % 4 == 0 : K % 4 == 0);
-  bool vb = aligned16(B) && ldb % 4 == 0 && (transb ? K % 4 == 0 : N % 4 == 0);
-  if (va && vb) gemm_dispatch<true>(transa, transb, M, N, K, A, lda, B, ldb, ep, stream);
-  else gemm_dispatch<false>(transa, transb, M, N, K, A, lda, B, ldb, ep, stream);
-  if (s > 1) {
-    long tot = (long)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, stream, (const float*)workspace, s,
-                       M, N, C, ldc, beta, 0, 0, 0, bias, bias2, act);
+  } else if (p.route == kPipeline) {
+    gemm_nt2(p.nt, M, N, K, A, lda, B, ldb, C, ldc, bias, bias2, act, beta, (float*)workspace, tickets, stream, nullptr, 0, 0, 0, 0);
+  } else {
+    RE2E_CHECK_ARG(p.splits == 1 || (workspace && workspace_bytes >= p.need_bytes), "workspace too small");
+    Epi ep;
+    memset(&ep, 0, sizeof(ep));
+    ep.C = C; ep.ldc = ldc; ep.M = M; ep.N = N; ep.bias = bias; ep.bias2 = bias2; ep.act = act; ep.beta = beta;
+    ep.mul = mul; ep.mask_out = mask_out; ep.lens = lens_dev; ep.T = T;
+    if (p.vec) gemm_engine<true>(p, transa, transb, M, N, K, A, lda, B, ldb, ep, (float*)workspace, true, stream);
+    else gemm_engine<false>(p, transa, transb, M, N, K, A, lda, B, ldb, ep, (float*)workspace, true, stream);
   }
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
@@ -1124,26 +1177,19 @@ extern "C" int re2e_gemm_tn_rows(int M, int N, int Kv, const float* A, long lda,
   RE2E_CHECK_ARG(A && B && C && rowmap, "null operand");
   RE2E_CHECK_ARG(beta == 0.f || beta == 1.f, "beta must be 0 or 1");
   RE2E_CHECK_ARG(fits32(phys_rows, lda, M) && fits32(phys_rows, ldb, N), "operand larger than 4 GiB");
-  if (!(aligned16(A) && lda % 4 == 0 && M % 4 == 0 && aligned16(B) && ldb % 4 == 0 && N % 4 == 0) || Kv < 64) {
+  const GemmIn in = {1, 0, M, N, Kv, RE2E_ACT_NONE, ld16(A, lda), ld16(B, ldb), false, true, re2e_stream_is_filler(stream), re2e_cu_count(), 0};
+  const GemmPlan p = plan_gemm(in);
+  if (!p.vec || Kv < 64) {
     re2e_set_error("re2e_gemm_tn_rows: operands not 16-byte loadable (M=%d N=%d Kv=%d)", M, N, Kv);
     return RE2E_EUNSUPPORTED;
   }
+  RE2E_CHECK_ARG(p.splits == 1 || (workspace && workspace_bytes >= p.need_bytes), "workspace too small");
   Epi ep;
   memset(&ep, 0, sizeof(ep));
-  ep.C = C; ep.ldc = ldc; ep.M = M; ep.N = N; ep.act = RE2E_ACT_NONE; ep.beta = beta; ep.nsplit = 1;
-  const int s = gemm_splits(1, 0, M, N, Kv);
-  if (s > 1) {
-    RE2E_CHECK_ARG(workspace && workspace_bytes >= (size_t)s * M * N * sizeof(float), "workspace too small");
-    ep.ws = (float*)workspace; ep.nsplit = s;
-  }
+  ep.C = C; ep.ldc = ldc; ep.M = M; ep.N = N; ep.act = RE2E_ACT_NONE; ep.beta = beta;
   DenseMG la{A, kbytes(phys_rows, lda, M), lda, M, Kv, rowmap, ident_rows};
   DenseMG lb{B, kbytes(phys_rows, ldb, N), ldb, N, Kv, rowmap, ident_rows};
-  launch_big<DenseMG, DenseMG, true, true>(la, lb, ep, Kv, stream);
-  if (s > 1) {
-    const long tot = (long)M * N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, stream, (const float*)workspace, s, M, N, C, ldc, beta, 0, 0, 0,
-                       (const float*)nullptr, (const float*)nullptr, (int)RE2E_ACT_NONE);
-  }
+  run_engine<DenseMG, DenseMG, true, big_built<true>(true)>(p, la, lb, ep, Kv, (float*)workspace, true, stream);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }
@@ -1169,19 +1215,28 @@ __global__ void weight_gather_kernel(const float* W, float* dst, int Cout, int C
   dst[i] = W[(((long)co * Cin + ci) * KH + kh) * KW + kw];
 }
 
-// RE2E_NO_THIN=1 routes the Cin == 1 / Cout == 1 convolutions through the implicit GEMM (A/B measurements)
-static bool thin_enabled() {
-  static const bool v = exp_env("RE2E_NO_THIN") == nullptr;
-  return v;
+// The engine's tile of a convolution forward / data gradient: the column count picks the narrow tiles, else the big tile of its form
+static EngineTile conv_tile(int Cout, int M, bool vec, bool filler) {
+  return Cout <= 32 ? kT256x32 : Cout <= 64 ? kT256x64 : big_tile(true, vec, M, filler);
 }
 
 template <bool V>
-static void conv_dispatch(const ConvGeom& g, int M, int K, const float* wg, int Cout, Epi& ep, hipStream_t st) {
+static void conv_engine(const ConvGeom& g, int M, int K, const float* wg, int Cout, const Epi& ep, hipStream_t st) {
   ConvK la{g, g.in, (unsigned)((long)g.NI * g.H * g.W * g.C * 4), M, K};
   DenseK lb{wg, kbytes(Cout, K, K), (long)K, Cout, K};
-  if (ep.N <= 32) launch_igemm<ConvK, DenseK, C256x32, V>(la, lb, ep, K, st);
-  else if (ep.N <= 64) launch_n64<ConvK, DenseK, V>(la, lb, ep, K, st);
-  else launch_big<ConvK, DenseK, V, true>(la, lb, ep, K, st);
+  launch_tile<ConvK, DenseK, V, big_built<V>(true) | bit(kT256x64) | bit(kT256x32)>(conv_tile(Cout, M, V, re2e_stream_is_filler(st)), la, lb, ep, K, st);
+}
+
+// The shared tail of the forward / data-gradient entry points, behind the thin and the halo-patch kernels: gemm_nt.hip's pipeline where it takes
+// the geometry (ncls classes with their input offsets oy0 / ox0 and output positions ooy / oox; not with a ReLU mask), else the gather engine.
+static void conv_pipeline_or_engine(const ConvGeom& g, const float* wg, int Cout, Epi& ep, int ncls, const int* oy0, const int* ox0, const int* ooy,
+                                    const int* oox, bool mask, hipStream_t st) {
+  const int K = g.KH * g.KW * g.C;
+  if (!mask && conv_nt2(g, ep.M, wg, Cout, ep.C, Cout, ep.bias, ep.act, ep.beta, ncls, oy0, ox0, ep.cls_wstride, ep.remap, ep.OHF, ep.OWF, ep.osy, ep.osx, ooy,
+                        oox, st))
+    return;
+  if (g.C % 4 == 0 && aligned16(g.in) && aligned16(wg)) conv_engine<true>(g, ep.M, K, wg, Cout, ep, st);
+  else conv_engine<false>(g, ep.M, K, wg, Cout, ep, st);
 }
 
 // Forward / data-gradient implicit GEMM:
@@ -1203,13 +1258,12 @@ static int conv_igemm_impl(const float* in, int NI, int H, int W, int C, const f
   RE2E_CHECK_ARG((long)NI * PH * PW < 2147483647L, "too many pixels");
   RE2E_CHECK_ARG((long)NI * H * W * C * 4 < 0xFFFFFFF0L, "input tensor larger than 4 GiB");
   ConvGeom g{in, NI, H, W, C, PH, PW, KH, KW, SY, SX, DY, DX, OY0, OX0};
-  int M = NI * PH * PW, K = KH * KW * C;
   Epi ep;
   memset(&ep, 0, sizeof(ep));
-  ep.C = out; ep.ldc = Cout; ep.M = M; ep.N = Cout; ep.bias = bias; ep.act = act; ep.beta = beta; ep.nsplit = 1;
+  ep.C = out; ep.ldc = Cout; ep.M = NI * PH * PW; ep.N = Cout; ep.bias = bias; ep.act = act; ep.beta = beta; ep.nsplit = 1;
   ep.remap = 1; ep.PH = PH; ep.PW = PW; ep.OHF = OHF; ep.OWF = OWF; ep.osy = osy; ep.osx = osx; ep.ooy = ooy; ep.oox = oox;
   if (osy == 1 && osx == 1 && ooy == 0 && oox == 0 && OHF == PH && OWF == PW) ep.remap = 0;
-  if ((Cout == 1 || C == 1) && thin_enabled() && !mask) {
+  if ((Cout == 1 || C == 1) && !engine_switches().no_thin && !mask) {
     OutMap om{out, (long)Cout, ep.remap, PH, PW, OHF, OWF, osy, osx, ooy, oox};
     if (thin_conv_forward(g, wg, Cout, om, bias, act, beta, stream)) {
       RE2E_LAUNCH_CHECK();
@@ -1220,15 +1274,7 @@ static int conv_igemm_impl(const float* in, int NI, int H, int W, int C, const f
     RE2E_LAUNCH_CHECK();
     return RE2E_OK;
   }
-  if (!mask) {
-    const int oy0[1] = {OY0}, ox0[1] = {OX0}, oo_y[1] = {ooy}, oo_x[1] = {oox};
-    if (conv_nt2(g, M, wg, Cout, out, Cout, bias, act, beta, 1, oy0, ox0, 0, ep.remap, OHF, OWF, osy, osx, oo_y, oo_x, stream)) {
-      RE2E_LAUNCH_CHECK();
-      return RE2E_OK;
-    }
-  }
-  if (C % 4 == 0 && aligned16(in) && aligned16(wg)) conv_dispatch<true>(g, M, K, wg, Cout, ep, stream);
-  else conv_dispatch<false>(g, M, K, wg, Cout, ep, stream);
+  conv_pipeline_or_engine(g, wg, Cout, ep, 1, &OY0, &OX0, &ooy, &oox, mask != nullptr, stream);
   if (mask) {
     const long n = (long)NI * OHF * OWF * Cout;
     const long nb = (n + 255) / 256;
@@ -1283,70 +1329,47 @@ extern "C" int re2e_conv_dgrad_s2(const float* dz, int N, int OH, int OW, int Co
   hipLaunchKernelGGL(weight_gather_kernel, dim3(cdiv(wtot, 256), 4), dim3(256), 0, stream, W, wt_ws, Cout, Cin, KH, KW, 1, TA, TB,
                      0, 0, 2, pad);
   ConvGeom g{dz, N, OH, OW, Cout, PH, PW, TA, TB, 1, 1, -1, -1, 0, 0};
-  const int M = N * PH * PW, K = TA * TB * Cout;
   Epi ep;
   memset(&ep, 0, sizeof(ep));
-  ep.C = dx; ep.ldc = Cin; ep.M = M; ep.N = Cin; ep.act = RE2E_ACT_NONE; ep.nsplit = 1;
+  ep.C = dx; ep.ldc = Cin; ep.M = N * PH * PW; ep.N = Cin; ep.act = RE2E_ACT_NONE; ep.nsplit = 1;
   ep.remap = 1; ep.PH = PH; ep.PW = PW; ep.OHF = H; ep.OWF = Wd; ep.osy = 2; ep.osx = 2;
   ep.ncls = 4; ep.cls_wstride = wtot;
   for (int p = 0; p < 2; ++p) {   // oh = (2i + p + pad - kh)/2 = i + (p + pad - kh0)/2 - a
     const int k0 = (p + pad) & 1;
     ep.cls_oy0[p] = (p + pad - k0) / 2; ep.cls_ox0[p] = ep.cls_oy0[p];
   }
-  {
-    // class (ph, pw) = cls >> 1, cls & 1: input offsets cls_oy0[ph] / cls_ox0[pw], output positions (2i + ph, 2j + pw)
-    int oy0[4], ox0[4], oo_y[4], oo_x[4];
-    for (int c = 0; c < 4; ++c) { oy0[c] = ep.cls_oy0[c >> 1]; ox0[c] = ep.cls_ox0[c & 1]; oo_y[c] = c >> 1; oo_x[c] = c & 1; }
-    if (conv_nt2(g, M, wt_ws, Cin, dx, Cin, nullptr, RE2E_ACT_NONE, 0.f, 4, oy0, ox0, wtot, 1, H, Wd, 2, 2, oo_y, oo_x, stream)) {
-      RE2E_LAUNCH_CHECK();
-      return RE2E_OK;
-    }
-  }
-  if (Cout % 4 == 0 && aligned16(dz) && aligned16(wt_ws)) conv_dispatch<true>(g, M, K, wt_ws, Cin, ep, stream);
-  else conv_dispatch<false>(g, M, K, wt_ws, Cin, ep, stream);
+  // class (ph, pw) = cls >> 1, cls & 1: input offsets cls_oy0[ph] / cls_ox0[pw], output positions (2i + ph, 2j + pw)
+  int oy0[4], ox0[4], oo_y[4], oo_x[4];
+  for (int c = 0; c < 4; ++c) { oy0[c] = ep.cls_oy0[c >> 1]; ox0[c] = ep.cls_ox0[c & 1]; oo_y[c] = c >> 1; oo_x[c] = c & 1; }
+  conv_pipeline_or_engine(g, wt_ws, Cin, ep, 4, oy0, ox0, oo_y, oo_x, false, stream);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }
 
-static int wgrad_splits_mfma(int Mrows, int Cout, long P) {
-  int bm, bn;
-  if (Cout <= 32) { bm = 256; bn = 32; } else if (Cout <= 64) { bm = (Mrows % 192 == 0 && Mrows % 256 != 0) ? 192 : 256; bn = 64; } else if (Mrows % 192 == 0 && Mrows % 128 != 0) { bm = 192; bn = 64; } else { bm = 128; bn = 128; }
-  return pick_splits(Mrows, Cout, (int)P, bm, bn);
+// The plan of a convolution weight gradient: the kernel, its K slices (= slabs: the reduce always runs, it applies the weight-layout permute)
+// and the reduce.  The slice count is a function of the shape alone -- the ladder for 16-byte loadable operands -- so that
+// re2e_conv_wgrad_workspace_bytes, which sees no pointers, sizes what the launch uses; `vec` then only picks between tiles that are built.
+struct WgradPlan { bool thin; EngineTile tile; int splits; bool wide_reduce; };
+static EngineTile wgrad_tile(int Mrows, int Cout, bool vec) {
+  if (Cout <= 32) return kT256x32;
+  if (Cout <= 64) return vec && Mrows % 192 == 0 && Mrows % 256 != 0 ? kT192x64 : kT256x64;
+  return vec && Mrows % 192 == 0 && Mrows % 128 != 0 ? kT192x64 : kT128;      // conv2_1: 576 x 128; else the 4-wave big tile (see big_tile)
 }
-
-static int wgrad_splits(int Mrows, int Cout, long P, long rows, int C, int KH, int KW, bool* thin = nullptr) {
-  if (thin) *thin = false;
-  if ((C == 1 || Cout == 1) && thin_enabled()) {
-    int s = thin_wgrad_slabs(C, Cout, KH, KW, P, rows);
-    if (s > 0) { if (thin) *thin = true; return s; }
+static WgradPlan plan_wgrad(int Mrows, int Cout, long P, long rows, int C, int KH, int KW, bool aligned, bool vec, int cus) {
+  WgradPlan w = {false, wgrad_tile(Mrows, Cout, vec), 0, false};
+  if ((C == 1 || Cout == 1) && !engine_switches().no_thin && aligned) {
+    w.splits = thin_wgrad_slabs(C, Cout, KH, KW, P, rows);
+    w.thin = w.splits > 0;
   }
-  return wgrad_splits_mfma(Mrows, Cout, P);
-}
-
-template <bool V>
-static void wgrad_dispatch(const ConvGeom& g, int Mrows, int P, const float* dout, int Cout, Epi& ep, hipStream_t st) {
-  ConvM la{g, g.in, (unsigned)((long)g.NI * g.H * g.W * g.C * 4), Mrows, P};
-  DenseM lb{dout, kbytes(P, Cout, Cout), (long)Cout, Cout, P};
-  if (Cout <= 32) launch_igemm<ConvM, DenseM, C256x32, V>(la, lb, ep, P, st);
-  else if (Cout <= 64) {
-    if constexpr (V) {
-      if (Mrows % 192 == 0 && Mrows % 256 != 0) { launch_igemm<ConvM, DenseM, C192x64, V>(la, lb, ep, P, st); return; }
-    }
-    launch_n64<ConvM, DenseM, V>(la, lb, ep, P, st);
-  }
-  else {
-    if constexpr (V) {
-      if (Mrows % 192 == 0 && Mrows % 128 != 0) { launch_igemm<ConvM, DenseM, C192x64, V>(la, lb, ep, P, st); return; }   // conv2_1: 576 x 128
-    }
-    launch_big<ConvM, DenseM, V, false>(la, lb, ep, P, st);
-  }
+  if (!w.thin) w.splits = pick_splits(Mrows, Cout, (int)P, wgrad_tile(Mrows, Cout, true), cus);
+  w.wide_reduce = w.splits >= 64 && (long)Mrows * Cout <= 65536;
+  return w;
 }
 
 extern "C" size_t re2e_conv_wgrad_workspace_bytes(int NI, int PH, int PW, int C, int Cout, int KH, int KW) {
-  int Mrows = KH * KW * C;
-  long P = (long)NI * PH * PW;
-  int s = wgrad_splits(Mrows, Cout, P, (long)NI * PH, C, KH, KW);
-  return (size_t)s * Mrows * Cout * sizeof(float);   // always reduce through the workspace (layout permute)
+  const int Mrows = KH * KW * C;
+  const long P = (long)NI * PH * PW;
+  return (size_t)plan_wgrad(Mrows, Cout, P, (long)NI * PH, C, KH, KW, true, true, re2e_cu_count()).splits * Mrows * Cout * sizeof(float);
 }
 
 // Weight gradient: dW[co][ci][kh][kw] (+)= sum_pix dout[pix][co] * in[n][py*SY+kh+OY0][px*SX+kw+OX0][ci]
@@ -1355,29 +1378,31 @@ extern "C" int re2e_conv_wgrad(const float* in, int NI, int H, int W, int C, con
                                void* workspace, size_t workspace_bytes, hipStream_t stream) {
   RE2E_CHECK_ARG(in && dout && dW && workspace, "null operand");
   ConvGeom g{in, NI, H, W, C, PH, PW, KH, KW, SY, SX, 1, 1, OY0, OX0};
-  int Mrows = KH * KW * C;
-  long P = (long)NI * PH * PW;
+  const int Mrows = KH * KW * C;
+  const long P = (long)NI * PH * PW;
   RE2E_CHECK_ARG(P < 2147483647L, "too many pixels");
   RE2E_CHECK_ARG((long)NI * H * W * C * 4 < 0xFFFFFFF0L && P * Cout * 4 < 0xFFFFFFF0L, "tensor larger than 4 GiB");
-  bool thin = false;
-  int s = wgrad_splits(Mrows, Cout, P, (long)NI * PH, C, KH, KW, &thin);
-  if (thin && !(aligned16(in) && aligned16(dout))) { thin = false; s = wgrad_splits_mfma(Mrows, Cout, P); }
-  RE2E_CHECK_ARG(workspace_bytes >= (size_t)s * Mrows * Cout * sizeof(float), "workspace too small");
-  Epi ep;
-  memset(&ep, 0, sizeof(ep));
-  ep.M = Mrows; ep.N = Cout; ep.nsplit = s; ep.ws = (float*)workspace;
-  if (s == 1) {   // still go through the slab so that the reduce kernel applies the layout permute
-    ep.C = (float*)workspace; ep.ldc = Cout;
+  const bool aligned = aligned16(in) && aligned16(dout), vec = aligned && C % 4 == 0 && Cout % 4 == 0;
+  const WgradPlan w = plan_wgrad(Mrows, Cout, P, (long)NI * PH, C, KH, KW, aligned, vec, re2e_cu_count());
+  RE2E_CHECK_ARG(workspace_bytes >= (size_t)w.splits * Mrows * Cout * sizeof(float), "workspace too small");
+  if (w.thin) thin_wgrad(g, dout, Cout, (float*)workspace, w.splits, stream);
+  else {
+    Epi ep;
+    memset(&ep, 0, sizeof(ep));
+    ep.M = Mrows; ep.N = Cout; ep.nsplit = w.splits; ep.ws = (float*)workspace;
+    if (w.splits == 1) { ep.C = (float*)workspace; ep.ldc = Cout; }      // still through the slab: the reduce kernel applies the layout permute
+    ConvM la{g, g.in, (unsigned)((long)g.NI * g.H * g.W * g.C * 4), Mrows, (int)P};
+    DenseM lb{dout, kbytes(P, Cout, Cout), (long)Cout, Cout, (int)P};
+    constexpr unsigned BUILT = bit(kT128) | bit(kT256x64) | bit(kT256x32);
+    if (vec) launch_tile<ConvM, DenseM, true, BUILT | bit(kT192x64)>(w.tile, la, lb, ep, (int)P, stream);
+    else launch_tile<ConvM, DenseM, false, BUILT>(w.tile, la, lb, ep, (int)P, stream);
   }
-  if (thin) thin_wgrad(g, dout, Cout, (float*)workspace, s, stream);
-  else if (C % 4 == 0 && Cout % 4 == 0 && aligned16(in) && aligned16(dout)) wgrad_dispatch<true>(g, Mrows, (int)P, dout, Cout, ep, stream);
-  else wgrad_dispatch<false>(g, Mrows, (int)P, dout, Cout, ep, stream);
-  long tot = (long)Mrows * Cout;
-  if (s >= 64 && tot <= 65536)
-    hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(cdiv(tot, 64)), dim3(1024), 0, stream, (const float*)workspace, s, Mrows,
+  const long tot = (long)Mrows * Cout;
+  if (w.wide_reduce)
+    hipLaunchKernelGGL(splitk_reduce_wide_kernel, dim3(cdiv(tot, 64)), dim3(1024), 0, stream, (const float*)workspace, w.splits, Mrows,
                        Cout, dW, (long)Cout, beta, 1, C, KH * KW);
   else
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, stream, (const float*)workspace, s, Mrows,
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(cdiv(tot, 256)), dim3(256), 0, stream, (const float*)workspace, w.splits, Mrows,
                        Cout, dW, (long)Cout, beta, 1, C, KH * KW, (const float*)nullptr, (const float*)nullptr, RE2E_ACT_NONE);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;

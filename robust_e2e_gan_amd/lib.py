@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 321      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 322      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -32,6 +32,7 @@ SIGNATURES = {
     're2e_stream_role': (I, [P, I]),
     're2e_gemm_workspace_bytes': (Z, [I, I, I, I, I]),
     're2e_gemm': (I, [I, I, I, I, I, P, L, P, L, P, L, P, P, I, F, P, P, P, I, P, Z, P]),
+    're2e_gemm_plan': (I, [I, I, I, I, I, I, I, I, I, I, I, I, P, Z]),
     're2e_gemm_nt_rows': (I, [I, I, I, P, L, P, L, P, L, P, P, I, F, P, I, I, P, Z, P]),
     're2e_gemm_tn_rows': (I, [I, I, I, P, L, P, L, P, L, F, P, I, I, P, Z, P]),
     're2e_fill_rows': (I, [P, L, I, P, I, F, P, I, P]),
@@ -252,6 +253,19 @@ def lstm_plan(T, B, H, backward=False, cus=0):
     rc = lib.re2e_lstm_plan(T, B, H, int(backward), cus, buf, len(buf))
     if rc != 0:
         raise Re2eError('re2e_lstm_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    return dict(kv.split('=') for kv in buf.value.decode().split())
+
+
+def gemm_plan(transa, transb, M, N, K, act=ACT_NONE, aligned=(True, True, True), rowmap=False, filler=False, cus=0):
+    """re2e_gemm_plan as a dict of strings: the route (skinny_wg / pipeline / engine), its tile or variant, splits, row-tail boundary and
+    workspace bytes the dense entry points would run this product with.  aligned: (A, B, C and biases) 16-byte loadable (cus > 0: on a chip
+    of that many CUs, no device needed; 0: the current device)."""
+    buf = ctypes.create_string_buffer(256)
+    lib = load()
+    rc = lib.re2e_gemm_plan(int(transa), int(transb), M, N, K, int(aligned[0]), int(aligned[1]), int(aligned[2]), act, int(rowmap), int(filler), cus,
+                            buf, len(buf))
+    if rc != 0:
+        raise Re2eError('re2e_gemm_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
     return dict(kv.split('=') for kv in buf.value.decode().split())
 
 

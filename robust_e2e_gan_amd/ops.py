@@ -60,9 +60,10 @@ FUSED_DBIAS = lib.exp_env('RE2E_NO_FUSED_DBIAS') is None
 
 def gemm_input_grad(dz, W, dx, M, K, N, beta=0.0):
     """dx[M,K] = dz[M,N] W[N,K] (+ beta dx): the input gradient of y = x W^T.  For many rows the weight is transposed first (one
-    small gather, N*K elements) and the product runs as dz (W^T)^T on the engine's k-major path -- 256x128 tiles with the
-    interleaved k-step and the round-filling row tail -- instead of the row-major-B path (MI355X, 12800 x 2560 x 2048:
-    113 -> 128 TFLOP/s; RE2E_NO_NT_INPUT_GRAD=1 keeps the direct form)."""
+    small gather, N*K elements) and the product runs as dz (W^T)^T, an x W^T product with both operands k-major, which with K and N
+    multiples of 4 is one the plan (csrc/igemm.hip plan_gemm) gives to the LDS-DMA pipeline of csrc/gemm_nt.hip -- instead of the
+    row-major-B path of the engine (when introduced, then on the engine's 256x128 tiles: MI355X, 12800 x 2560 x 2048: 113 -> 128
+    TFLOP/s; RE2E_NO_NT_INPUT_GRAD=1 keeps the direct form)."""
     if NT_INPUT_GRAD and M >= 2048 and K % 4 == 0 and N % 4 == 0 and W.is_contiguous():
         wt = empty((K, N), dz)
         call('re2e_conv_weight_gather', W.data_ptr(), wt.data_ptr(), N, K, 1, 1, 1, 1, 1, 0, 0, 1)       # wt[k][n] = W[n][k]

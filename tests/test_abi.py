@@ -156,6 +156,85 @@ def test_lstm_plan_table(monkeypatch):
         lib.lstm_plan(60, 8, 12, cus=256)
 
 
+_NT, _NN, _TN = (0, 1), (0, 0), (1, 0)
+_NONE, _TANH, _RELU, _MASK = 0, 1, 2, 5          # RE2E_ACT_*
+# (form, M, N, K, activation, row map, filler stream) -> the plan on a 256-CU chip, all operands 16-byte aligned with natural leading
+# dimensions.  Dumped from the commit BEFORE plan_gemm existed, by a reader over its try-and-fall-through functions: a row that changes is a
+# change of behaviour.  need: workspace bytes the route uses; ws: what re2e_gemm_workspace_bytes answers (either stream role, the pipeline's
+# run-time fallback included).
+_GEMM_PLANS = [
+    (_NT, 5, 3, 7, _NONE, 0, 0, dict(route='engine', tile='128x128x16', vec=0, splits=1, m1=5, need=0, ws=0)),
+    (_NT, 17, 33, 72, _NONE, 0, 0, dict(route='skinny_wg', vec=1, ws=0)),
+    (_NT, 32, 20, 66, _NONE, 0, 0, dict(route='skinny_wg', vec=0, ws=0)),
+    (_NT, 8, 130, 512, _TANH, 0, 0, dict(route='engine', tile='32x128x32', vec=1, splits=8, m1=8, need=33280, ws=524288)),
+    (_NT, 8, 36, 8196, _NONE, 0, 0, dict(route='engine', tile='32x128x32', vec=1, splits=64, m1=8, need=73728, ws=4194304)),
+    (_NT, 4352, 2046, 16, _NONE, 0, 0, dict(route='engine', tile='256x128x16', vec=1, splits=1, m1=4096, need=0, ws=0)),      # + 64x64 tail
+    (_NT, 4352, 2046, 16, _NONE, 0, 1, dict(route='engine', tile='128x128x16', vec=1, splits=1, m1=4352, need=0, ws=0)),
+    (_NT, 12288, 2048, 64, _NONE, 0, 0, dict(route='pipeline', variant=3, tile='256x128x16', n_dp=768, g_sk=0, need=0, ws=0)),
+    (_NT, 12288, 2048, 64, _NONE, 0, 1, dict(route='pipeline', variant=6, tile='128x128x16', n_dp=1536, g_sk=0, need=0, ws=0)),
+    (_NT, 12800, 512, 260, _NONE, 0, 0, dict(route='pipeline', variant=3, tile='256x128x16', n_dp=200, g_sk=0, need=0, ws=33554432)),
+    (_NT, 6400, 512, 4240, _NONE, 0, 0, dict(route='pipeline', variant=8, tile='128x64x16', n_dp=256, g_sk=256, need=16777216, ws=65536000)),
+    (_NT, 6400, 512, 4240, _NONE, 1, 0, dict(route='pipeline', variant=8, tile='128x64x16', n_dp=256, g_sk=256, need=16777216, ws=65536000)),
+    (_NT, 300, 516, 200, _NONE, 0, 0, dict(route='pipeline', variant=8, tile='128x64x16', n_dp=27, g_sk=0, need=0, ws=0)),
+    (_NT, 255, 516, 200, _NONE, 0, 0, dict(route='engine', tile='128x128x16', vec=1, splits=1, m1=255, need=0, ws=0)),
+    (_NT, 12800, 260, 512, _MASK, 0, 0, dict(route='engine', tile='256x128x16', vec=1, splits=1, m1=12800, need=0, ws=0)),
+    (_NN, 130, 64, 257, _RELU, 0, 0, dict(route='engine', tile='128x128x16', vec=0, splits=1, m1=130, need=0, ws=0)),
+    (_NN, 32, 512, 1200, _NONE, 0, 0, dict(route='skinny_wg', vec=1, ws=1245184)),
+    (_TN, 1200, 812, 1312, _NONE, 0, 0, dict(route='engine', tile='128x128x16', vec=1, splits=5, m1=1200, need=19488000, ws=19488000)),
+    (_TN, 2048, 512, 12800, _NONE, 0, 0, dict(route='engine', tile='256x128x16', vec=1, splits=8, m1=2048, need=33554432, ws=33554432)),
+    (_TN, 2048, 512, 12800, _NONE, 0, 1, dict(route='engine', tile='128x128x16', vec=1, splits=8, m1=2048, need=33554432, ws=33554432)),
+    (_TN, 8, 4, 40000, _NONE, 0, 0, dict(route='engine', tile='128x128x16', vec=1, splits=156, m1=8, need=19968, ws=19968)),
+]
+# what the dense entry points instantiate.  A copy of csrc/igemm.hip's tile table as run_engine's BUILT masks admit it per form and VEC, and of
+# csrc/gemm_nt.hip's variant table: it has to follow them when an instantiation is added or dropped.
+_ENGINE_BUILT = {
+    (_NT, 1): {'128x128x16', '256x128x16', '32x128x32'}, (_NT, 0): {'128x128x16', '32x128x32'},
+    (_NN, 1): {'128x128x16', '32x128x32'}, (_NN, 0): {'128x128x16', '32x128x32'},
+    (_TN, 1): {'128x128x16', '256x128x16'}, (_TN, 0): {'128x128x16'},
+}
+_PIPELINE_BUILT = {3: '256x128x16', 6: '128x128x16', 8: '128x64x16'}
+
+
+def test_gemm_plan_table():
+    """re2e_gemm_plan (csrc/igemm.hip plan_gemm, which re2e_gemm, re2e_gemm_nt_rows, re2e_gemm_tn_rows and the K-sliced batches choose
+    their kernel with) on a 256-CU chip against the table above; then over a sweep of shapes, forms, stream roles and two chip sizes every
+    plan names something that is built, its workspace does not depend on the stream role, and a stream-K tail has at least two workgroups.
+    No device is touched where cus > 0."""
+    from robust_e2e_gan_amd import lib
+    if not os.path.exists(lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    for form, M, N, K, act, rowmap, filler, want in _GEMM_PLANS:
+        got = lib.gemm_plan(form[0], form[1], M, N, K, act=act, rowmap=bool(rowmap), filler=bool(filler), cus=256)
+        where = (form, M, N, K, act, rowmap, filler, got)
+        for k, v in want.items():
+            assert got[k] == str(v), (k, where)
+    so = lib.load()
+    for cus in (64, 256, 0):          # 0: the chip re2e_gemm_workspace_bytes itself plans for (256 CUs without a device)
+        for form in (_NT, _NN, _TN):
+            for M in (1, 31, 32, 33, 255, 256, 2047, 2048, 12800):
+                for N in (4, 64, 130, 2046, 2048):
+                    for K in (16, 63, 64, 128, 8192, 8196):
+                        plans = [lib.gemm_plan(form[0], form[1], M, N, K, filler=f, cus=cus) for f in (False, True)]
+                        for got, other in (plans, plans[::-1]):
+                            where = (cus, form, M, N, K, got)
+                            if got['route'] == 'engine':
+                                assert got['tile'] in _ENGINE_BUILT[form, int(got['vec'])], where
+                                assert int(got['splits']) >= 1 and int(got['vec']) in (0, 1), where
+                                m1 = int(got['m1'])
+                                assert m1 == M or (form == _NT and got['vec'] == '1' and got['tile'] == '256x128x16' and 2048 <= m1 < M), where
+                            elif got['route'] == 'pipeline':
+                                assert _PIPELINE_BUILT.get(int(got['variant'])) == got['tile'], where
+                                n_dp, g_sk = int(got['n_dp']), int(got['g_sk'])
+                                assert n_dp + g_sk >= 1 and (g_sk == 0 or g_sk >= 2), where
+                            else:
+                                assert got['route'] == 'skinny_wg' and M <= 32 and form != _TN, where
+                            assert int(got['ws']) >= int(got['need']), where
+                            assert int(got['ws']) >= int(other['ws']), where          # i.e. equal: the workspace is sized without a stream
+                            if cus == 0:
+                                assert int(got['ws']) == so.re2e_gemm_workspace_bytes(form[0], form[1], M, N, K), where
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from robust_e2e_gan_amd import lib
     monkeypatch.setattr(lib, '_lib', None)

@@ -38,7 +38,8 @@ def rnd(*shape, seed=0, scale=1.0):
 
 
 # ---------------------------------------------------------------------------------------------
-# the last two: 800 / 801 x 16 tiles of 256x128 on 256 workgroup slots -> the rows of the mostly empty 4th round run as 64x64 tiles
+# small, ragged and one-k-tile shapes on the engine; the last two (K and N multiples of 4, many rows) run on csrc/gemm_nt.hip's pipeline in the
+# x W^T form and on the engine's 128x128 tiles in the NN form.  The engine's row tail and 32x128 tile: test_gemm_routes_no_other_shape_reaches.
 @pytest.mark.parametrize('M,N,K', [(77, 257, 130), (256, 128, 64), (5, 3, 7), (300, 4233, 512), (130, 64, 257), (12800, 2048, 48),
                                    (12803, 2040, 36)])
 def test_gemm_nt_nn(M, N, K):
@@ -92,6 +93,77 @@ def test_gemm_nt_pipeline_and_stream_k(M, N, K):
     finally:
         lib.set_stream_role(st, False)
     close('nt2 filler stream', c, want.float(), tol=2e-5)
+
+
+# Routes of plan_gemm (csrc/igemm.hip) that no other shape of this file reaches; each case asserts the plan, so it cannot drift onto another kernel.
+#   row tail: x W^T whose N is no multiple of 4 (the pipeline declines) from 2048 rows: 256x128 tiles on rows [0, 4096) + a launch of 64x64 tiles
+#   32x128:   M <= 32 with an activation, or K > 8192 (the in-workgroup skinny kernel declines): split-K, then the reduce applies bias + activation
+#   dy^T x:   the same split count on the main stream (256x128 tiles) and on a filler stream (128x128)
+@pytest.mark.parametrize('case,M,N,K,plan', [
+    ('row_tail', 4352, 2046, 16, dict(route='engine', tile='256x128x16', vec='1', splits='1', m1='4096')),
+    ('row_tail_beta', 4352, 2046, 16, dict(route='engine', tile='256x128x16', vec='1', splits='1', m1='4096')),
+    ('t32x128_tanh', 8, 130, 512, dict(route='engine', tile='32x128x32', splits='8')),
+    ('t32x128_beta', 8, 36, 8196, dict(route='engine', tile='32x128x32', splits='64')),
+    ('tn_stream_roles', 2048, 64, 512, dict(route='engine', tile='256x128x16', vec='1')),
+])
+def test_gemm_routes_no_other_shape_reaches(case, M, N, K, plan):
+    ops, lib = _ops()
+    tn = case == 'tn_stream_roles'
+    act = {'row_tail': lib.ACT_RELU, 't32x128_tanh': lib.ACT_TANH}.get(case, lib.ACT_NONE)
+    got = lib.gemm_plan(int(tn), int(not tn), M, N, K, act=act)
+    for k, v in plan.items():
+        assert got[k] == v, (k, got)
+    if tn:
+        A, Bm = rnd(K, M).to(DEV), rnd(K, N, seed=1).to(DEV)
+        want = A.double().t() @ Bm.double()
+        filler = lib.gemm_plan(1, 0, M, N, K, filler=True)
+        assert filler['tile'] == '128x128x16' and filler['splits'] == got['splits'] and filler['ws'] == got['ws'], (got, filler)
+        c_main = torch.full((M, N), float('nan'), device=DEV)
+        ops.gemm(A, Bm, c_main, M, N, K, transa=True)
+        st = torch.cuda.Stream()
+        lib.set_stream_role(st, True)
+        try:
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                c_fill = torch.full((M, N), float('nan'), device=DEV)
+                ops.gemm(A, Bm, c_fill, M, N, K, transa=True)
+            st.synchronize()
+        finally:
+            lib.set_stream_role(st, False)
+        bound = 2e-5 * want.abs().max().item()
+        print('%s: splits %s, max err main %.3e filler %.3e (bound %.3e), bitwise equal %s' % (
+            case, got['splits'], (c_main.double() - want).abs().max().item(), (c_fill.double() - want).abs().max().item(), bound, torch.equal(c_main, c_fill)))
+        assert (c_main.double() - want).abs().max().item() <= bound
+        assert torch.equal(c_main, c_fill), 'same K slices, same k order inside a slice: only the tile differs between the stream roles'
+        return
+    A, Bm, b1, b2 = rnd(M, K), rnd(N, K, seed=1), rnd(N, seed=2), rnd(N, seed=3)
+    if M > 4096:
+        A[4096:] = A[4096:] * 0.5 + 0.25          # the two sides of the tail boundary carry different values
+    ldc = N + 2                                     # two canary columns behind every row
+    C0 = rnd(M, ldc, seed=4)
+    pre = A.double() @ Bm.double().t()
+    bound = 2e-5 * pre.abs().max().item()
+    kw, ref = {}, pre
+    if case in ('row_tail', 't32x128_tanh'):
+        kw['bias'] = b1.to(DEV)
+        ref = ref + b1.double()
+    if case == 't32x128_tanh':
+        kw['bias2'] = b2.to(DEV)
+        ref = torch.tanh(ref + b2.double())
+    if case == 'row_tail':
+        ref = torch.relu(ref)
+    if case in ('row_tail_beta', 't32x128_beta'):
+        kw['beta'] = 1.0
+        ref = ref + C0[:, :N].double()
+    c = C0.to(DEV).clone()
+    ops.gemm(A.to(DEV), Bm.to(DEV), c, M, N, K, transb=True, ldc=ldc, act=act, **kw)
+    err = (c[:, :N].double().cpu() - ref).abs()
+    print('%s: max err %.3e (bound %.3e)' % (case, err.max().item(), bound))
+    assert err.max().item() <= bound
+    if M > 4096:
+        assert err[4095].max().item() <= bound and err[4096].max().item() <= bound, 'the rows on the two sides of the tail boundary'
+        assert not torch.equal(c[4095, :N], c[4096, :N])
+    assert torch.equal(c[:, N:].cpu(), C0[:, N:]), 'wrote beyond the N columns'
 
 
 @pytest.mark.parametrize('M,N,K', [(512, 1024, 12800), (300, 1312, 4232), (2048, 512, 12800), (6400, 512, 4240), (1024, 256, 25600)])

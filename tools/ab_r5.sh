@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-session A/B of the training step (experiments build): each argument is one arm = a comma-separated list of VAR=value (or "base")
-#   bash tools/ab_r5.sh base RE2E_NT2_MAXWG=2 RE2E_TN2=6,,1+RE2E_NT2_MAXWG=2      ('+' separates assignments, ',,' is a literal comma)
+#   bash tools/ab_r5.sh base RE2E_NO_ROW_TAIL=1 RE2E_NT2=6,,1+RE2E_CONV_NT2=0      ('+' separates assignments, ',,' is a literal comma)
 export RE2E_EXPERIMENTS=1 RE2E_LIB=$PWD/robust_e2e_gan_amd/libre2e_hip_exp.so
 REPS=${REPS:-2}
 for r in $(seq $REPS); do

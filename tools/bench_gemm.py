@@ -55,7 +55,6 @@ def gemm_case(M, N, K):
 
 
 if __name__ == '__main__':
-    print('variant', os.environ.get('RE2E_IGEMM_VARIANT', '0'))
     for name, cfg in (('vgg conv1_2 64x800x80 64->64', (64, 800, 80, 64, 64, 3, 1, 1)), ('vgg conv2_1 64x400x40 64->128', (64, 400, 40, 64, 128, 3, 1, 1)),
                       ('vgg conv2_2 64x400x40 128->128', (64, 400, 40, 128, 128, 3, 1, 1)), ('D conv2 32x400x40 64->128 s2', (32, 400, 40, 64, 128, 4, 2, 1)),
                       ('D conv4 32x100x10 256->512 s1', (32, 100, 10, 256, 512, 4, 1, 1))):

@@ -23,10 +23,6 @@ SHAPES = [
 ]
 
 
-# (M, N, K) of the step's dy^T x products; the last two are ragged (K tail, M / N edges)
-TN_SHAPES = [(2048, 512, 12800), (2048, 2560, 12800), (1024, 256, 25600), (1024, 512, 25600), (512, 1024, 12800), (1024, 260, 25600),
-             (4240, 512, 6400), (512, 512, 5452), (256, 512, 25600), (260, 256, 25600), (320, 512, 6400), (300, 1312, 4232), (516, 132, 1003)]
-
 
 def timeit(fn, iters, groups=3):
     best = 1e9
@@ -44,12 +40,11 @@ def timeit(fn, iters, groups=3):
 
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith('--')]
-    variants = args[0].split(':') if args else ['0', '3,0', '3,2', '6,0', '6,2', '8,0', '8,2', '9,0', '1,2']
+    variants = args[0].split(':') if args else ['0', '3,0', '3,2', '6,0', '6,2', '8,0', '8,2']
     check_only = '--check-only' in sys.argv
-    skip_nt = '--tn-only' in sys.argv
     torch.manual_seed(0)
     print('%-22s %8s | %s' % ('M x N x K', 'engine', '  '.join('%9s' % v for v in variants)), flush=True)
-    for (M, N, K) in ([] if skip_nt else SHAPES):
+    for (M, N, K) in SHAPES:
         A = torch.randn(M, K, device=DEV)
         B = torch.randn(N, K, device=DEV)
         bias = torch.randn(N, device=DEV)
@@ -100,7 +95,7 @@ def main():
                 cells.append('ERR %s' % str(e)[:40])
         print('%-22s %8.1f | %s' % ('%dx%dx%d' % (M, N, K), fl / best[0] / 1e12 if not check_only else 0.0, '  '.join('%9s' % c for c in cells)), flush=True)
     # accumulate / plain epilogues and a ragged everything case
-    for (M, N, K, act, beta) in [] if skip_nt else ((3000, 516, 200, lib.ACT_NONE, 1.0), (2049, 260, 36, lib.ACT_RELU, 0.0), (7777, 1028, 1000, lib.ACT_LRELU, 0.0),
+    for (M, N, K, act, beta) in ((3000, 516, 200, lib.ACT_NONE, 1.0), (2049, 260, 36, lib.ACT_RELU, 0.0), (7777, 1028, 1000, lib.ACT_LRELU, 0.0),
                                  (4100, 132, 2052, lib.ACT_SIGMOID, 0.0)):
         A = torch.randn(M, K, device=DEV); B = torch.randn(N, K, device=DEV); b1 = torch.randn(N, device=DEV); b2 = torch.randn(N, device=DEV)
         Cinit = torch.randn(M, N, device=DEV)
@@ -115,55 +110,8 @@ def main():
             torch.cuda.synchronize()
             out.append('%.1e' % ((C1 - C0).abs().max().item() / C0.abs().max().item()) if bool(torch.isfinite(C1).all()) else 'NAN')
         print('edge %dx%dx%d act %d beta %.0f: rel err %s' % (M, N, K, act, beta, ' '.join(out)), flush=True)
-    # ---- dy^T x (weight gradients): C[M,N] += A[K,M]^T B[K,N] ----
-    tn_variants = [v for v in (args[1].split(':') if len(args) > 1 else ['0', '6,0', '6,2'])]
-    print('%-22s %8s | %s' % ('TN  M x N x K', 'engine', '  '.join('%9s' % v for v in tn_variants)), flush=True)
-    for (M, N, K) in TN_SHAPES:
-        A = torch.randn(K, M, device=DEV)
-        B = torch.randn(K, N, device=DEV)
-        Cinit = torch.randn(M, N, device=DEV)
-        C0, C1 = Cinit.clone(), Cinit.clone()
-        fl = 2.0 * M * N * K
-        iters = max(3, min(40, int(3e-3 / (fl / 100e12))))
-
-        def runner(v, C, beta):
-            def run():
-                os.environ['RE2E_TN2'] = v
-                ops.gemm(A, B, C, M, N, K, transa=True, beta=beta)
-            return run
-        cfgs = ['old'] + tn_variants
-        best = [1e9] * len(cfgs)
-        runs = [runner(v, C0 if v == 'old' else C1, 0.0) for v in cfgs]
-        if not check_only:
-            for r in runs:
-                r()
-            for _ in range(3):
-                for i, r in enumerate(runs):
-                    r()
-                    best[i] = min(best[i], timeit(r, iters, groups=1))
-        truth = A.double().t() @ B.double() + Cinit.double()
-        C0.copy_(Cinit)
-        runner('old', C0, 1.0)()
-        e0 = (C0.double() - truth).abs().max().item()
-        cells = []
-        for i, v in enumerate(tn_variants):
-            C1.copy_(Cinit)
-            if i == 0:
-                os.environ['RE2E_NT2_LOG'] = '1'
-            runner(v, C1, 1.0)()
-            os.environ.pop('RE2E_NT2_LOG', None)
-            torch.cuda.synchronize()
-            err = (C1.double() - truth).abs().max().item()
-            bad = not (err <= 2.0 * e0 + 1e-6) or not bool(torch.isfinite(C1).all())
-            C2 = C1.clone()
-            C1.copy_(Cinit)
-            runner(v, C1, 1.0)()
-            torch.cuda.synchronize()
-            same = torch.equal(C1, C2)
-            cells.append('%6.1f%s%s' % (fl / best[i + 1] / 1e12 if not check_only else 0.0, '!' if bad else ' ', ' ' if same else '~') + ('(%.0e/%.0e)' % (err, e0) if bad else ''))
-        print('%-22s %8.1f | %s' % ('%dx%dx%d' % (M, N, K), fl / best[0] / 1e12 if not check_only else 0.0, '  '.join('%9s' % c for c in cells)), flush=True)
     # ---- implicit-GEMM convolutions (MODE 2 of the same kernel) against igemm.hip's gather engine: forward and stride-2 data gradient ----
-    print('conv: N x H x W x C -> K, k s p   TFLOP/s of: old engine | new auto | variants 1 3 5 6 8 9 (whole tiles)   (max |new - old| / max |old|)', flush=True)
+    print('conv: N x H x W x C -> K, k s p   TFLOP/s of: old engine | new auto | variants 3 6 8 (whole tiles)   (max |new - old| / max |old|)', flush=True)
     for (Nb, H, W, C, Kc, k, st, pd) in ((32, 400, 40, 64, 128, 4, 2, 1), (32, 200, 20, 128, 256, 4, 2, 1), (3, 37, 21, 16, 20, 4, 2, 1), (2, 33, 18, 32, 24, 3, 1, 1),
                                           (5, 64, 32, 16, 64, 4, 2, 1)):
         x = torch.randn(Nb, H, W, C, device=DEV)
@@ -175,7 +123,7 @@ def main():
         dy = torch.randn(Nb, OH, OW, Kc, device=DEV)
         fl = 2.0 * k * k * C * Kc * Nb * OH * OW
         ys, ds, tf, td = [], [], [], []
-        modes = [('0', 'old')] + [('1', v) for v in ('0', '1,0', '3,0', '5,0', '6,0', '8,0', '9,0')]
+        modes = [('0', 'old')] + [('1', v) for v in ('0', '3,0', '6,0', '8,0')]
         for mode, var in modes:
             os.environ['RE2E_CONV_NT2'] = mode
             os.environ['RE2E_NT2'] = var
