@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 322
+#define RE2E_ABI_VERSION 323
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -183,6 +183,28 @@ size_t re2e_conv_wgrad_workspace_bytes(int NI, int PH, int PW, int C, int Cout, 
 int re2e_conv_wgrad(const float* in, int NI, int H, int W, int C, const float* dout, int Cout, int KH, int KW, int PH,
                     int PW, int SY, int SX, int OY0, int OX0, float* dW, float beta, void* workspace,
                     size_t workspace_bytes, re2e_stream_t stream);
+/* Which kernels serve one convolution of a layer (N,H,W,Cin) -> Cout channels, KH x KW, stride, pad: the host function the convolution entry
+ * points and ops.py choose with (csrc/igemm.hip plan_conv / plan_conv_layer), as text "key=value ...".  dir: 0 forward, 1 data gradient, 2 weight
+ * gradient; OH / OW: the output map (0: derived); act: the forward's activation; flags: RE2E_CONV_*.  family=wino3x3 (images=<per launch>),
+ * wino4x4 or direct, ws=<workspace bytes of that family's entry point>; for direct wino_note=<a Winograd layer declined for an image of 2 GiB
+ * or more> fused_pool=<re2e_conv3x3_relu_pool applies> and the plan of the entry point the layer calls:
+ *   route=cin1_fwd taps= grid= | cout1_rows grid= lds= | cout1 L= kh= kw= ch= grid= lds= | halo patch= dir= relu= items= grid= lds= |
+ *         pipeline variant= tile= n_dp= | engine tile= vec=          ... mask_pass=<the separate ReLU-mask pass follows> note=<the 2 GiB note>
+ *   route=wgrad_cin1 slabs= | wgrad_cout1 slabs= | wgrad_engine tile= vec= splits=          ... wide_reduce= need=<bytes the call uses>
+ * (a stride-2 data gradient into one channel: the plan of parity class (0,0) of its four calls).  cus > 0: plan for a chip of that many CUs (no
+ * device is touched); cus == 0: the current device's count.  RE2E_EUNSUPPORTED: a data gradient ops.conv_dgrad does not cover. */
+#define RE2E_CONV_BIAS 1
+#define RE2E_CONV_POOL 2
+#define RE2E_CONV_MASK 4
+#define RE2E_CONV_W_STRIDED 8          /* the weight / input / output-gradient tensor is not contiguous */
+#define RE2E_CONV_X_STRIDED 16
+#define RE2E_CONV_DZ_STRIDED 32
+#define RE2E_CONV_NO_WINOGRAD 64       /* the direct kernels whatever the layer (ops.py: RE2E_NO_WINOGRAD, experiments); also: the plan of the entry point itself */
+#define RE2E_CONV_NO_WINO_WGRAD 128
+#define RE2E_CONV_UNALIGNED 256        /* operands are not 16-byte aligned */
+#define RE2E_CONV_FILLER 512           /* the call runs on a filler stream (re2e_stream_role) */
+int re2e_conv_plan(int dir, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int act, int flags, int cus,
+                   char* out, size_t out_bytes);
 /* dst[r][a][b][c] <- W[Cout][Cin][KH][KW] at tap (kh0+a*kstep, kw0+b*kstep); transpose=0: r=co,c=ci; 1: r=ci,c=co */
 /* Stride-2 data gradient in one launch (all four output parity classes): dx[N][H][Wd][Cin] from
  * dz[N][OH][OW][Cout] and the PyTorch-layout weight W[Cout][Cin][KH][KW] (KH, KW even).

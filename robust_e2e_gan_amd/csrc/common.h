@@ -48,9 +48,11 @@ int re2e_cu_count();                                // core.hip: CUs of the curr
 // -DRE2E_EXPERIMENTS (make EXPERIMENTS=1 -> libre2e_hip_exp.so, used by tools/ through RE2E_LIB) and answers "unset" otherwise.  Of the
 // recurrences (lstm.hip) that is RE2E_LSTM_STAMPS (phase stamps), RE2E_LSTM_BWD3_UN (tools/lstm_stamps.py) and RE2E_LSTM_WAVES_FWD
 // (tools/bench_lstm.py); the switches of their rejected forms went with the forms.  Of the dense and implicit-GEMM
-// products it is nine switches that choose between SHIPPED forms, read in one place per file (igemm.hip engine_switches: RE2E_NO_SKINNY_GEMM,
-// RE2E_NO_ROW_TAIL, RE2E_NO_THIN, RE2E_TN_XCD_KSLICE, RE2E_IGEMM_NOMEM; gemm_nt.hip nt_switches: RE2E_NT2, RE2E_CONV_NT2, RE2E_NT2_TAILWG,
-// RE2E_NT2_LOG) and applied at the top of the plan (plan_gemm below); the rejected tile forms and their switches went likewise.
+// products it is seven switches that choose between SHIPPED forms, read in one place per file (igemm.hip engine_switches: RE2E_NO_SKINNY_GEMM,
+// RE2E_NO_ROW_TAIL, RE2E_TN_XCD_KSLICE, RE2E_IGEMM_NOMEM; gemm_nt.hip nt_switches: RE2E_NT2, RE2E_NT2_TAILWG, RE2E_NT2_LOG) and applied at the top
+// of the plan (plan_gemm below); of the convolutions four (igemm.hip conv_switches: RE2E_NO_THIN, RE2E_NO_COUT1_ROWS, RE2E_NO_HALO, RE2E_CONV_NT2),
+// read at the top of plan_conv, beside the Winograd kernels' probes (RE2E_WINO_LDS_KB / _LDSIN / _DBG / _STAMPS, RE2E_WW_DBG / _FLAT).  The
+// rejected forms and their switches went with their measurements kept in DESIGN.md Appendix A.
 #ifdef RE2E_EXPERIMENTS
 static inline const char* exp_env(const char* name) { return getenv(name); }
 #else
@@ -144,14 +146,6 @@ struct OutMap {
   }
 };
 
-// Thin-channel convolutions (thinconv.hip): direct kernels for Cout == 1 (forward) and Cin == 1 / Cout == 1 (weight gradient), where an MFMA tile
-// would be >= 97 % padding.  thin_conv_forward returns false / thin_wgrad_slabs returns 0 when the shape is
-// not covered (the caller then uses the implicit GEMM).
-bool thin_conv_forward(const ConvGeom& g, const float* wg, int Cout, const OutMap& o, const float* bias, int act,
-                       float beta, hipStream_t st);
-int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows);
-void thin_wgrad(const ConvGeom& g, const float* dout, int Cout, float* slabs, int nslab, hipStream_t st);
-
 // K-sliced batches of products for wino44.hip (igemm.hip): out[z][M][N] over K / ns slices of the contraction, through plan_gemm below
 int gemm_kslices_tn(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog = 0);
 int gemm_kslices(int M, int N, int K, int ns, const float* A, long lda, const float* B, long ldb, float* out, hipStream_t st, int nolog = 0);
@@ -182,12 +176,57 @@ struct GemmPlan {
   NtPlan nt;             // pipeline
 };
 GemmPlan plan_gemm(const GemmIn& in, bool with_workspace = false);
-// ... and the pipeline's implicit-GEMM convolution form (forward / data gradient; ncls = 4: the output parity classes of a stride-2 data gradient).
-// Returns 1 when it launched the convolution, 0 when the geometry is left to igemm.hip's engine.
-int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, long ldc, const float* bias, int act, float beta, int ncls,
-             const int* cls_oy0, const int* cls_ox0, long cls_wstride, int remap, int OHF, int OWF, int osy, int osx, const int* ooy, const int* oox,
-             hipStream_t st);
-// 3x3 / stride-1 / pad-1 convolutions with C % 16 == 0 and Cout % 64 == 0 (conv3x3.hip: halo patch staged once per channel
-// chunk, taps walked in LDS).  Returns false when the geometry is not covered (the caller then uses the implicit GEMM).
-bool halo_conv3x3(const ConvGeom& g, const float* wg, int Cout, float* out, const float* bias, int act, float beta, const float* mask,
+// ---- which kernel serves a convolution: the plan (igemm.hip plan_conv; printed by re2e_conv_plan) --------------------------------------------------
+// Everything the choice depends on, and nothing else: the call kind, the ConvGeom-level geometry without its pointer, the output map, the epilogue,
+// what is asked for beside the product (ReLU mask, fused pool), which operands are 16-byte aligned (absent ones count as aligned), the stream's
+// role and the chip's CU count.  kConvIgemm: re2e_conv_igemm / _masked / re2e_conv3x3_relu_pool -- a forward (D = 1), a stride-1 data gradient
+// (D = -1) or ONE parity class of a stride-2 data gradient (remap); kConvDgradS2: re2e_conv_dgrad_s2, the four parity classes in one launch (the
+// geometry of one class, cls_o0[p] = input offset of parity p); kConvWgrad: re2e_conv_wgrad (wg16: the output gradient).
+enum ConvKind { kConvIgemm, kConvDgradS2, kConvWgrad };
+struct ConvIn {
+  ConvKind kind;
+  int NI, H, W, C, PH, PW, KH, KW, SY, SX, DY, DX, OY0, OX0, cls_o0[2];
+  int Cout, act; float beta;
+  bool remap, mask, pool;
+  bool in16, wg16, out16, bias16, mask16, pool16, idx4;
+  bool filler; int cus;
+};
+enum ConvRoute { kCin1Fwd, kCout1Rows, kCout1, kHalo, kConvPipeline, kConvEngine, kWgradCin1, kWgradCout1, kWgradEngine, kConvNone };
+struct ConvPlan {
+  ConvRoute route;       // kConvNone: a fused pool was asked for on a geometry the halo-patch kernel does not take (RE2E_EUNSUPPORTED)
+  bool mask_pass;        // the separate relu_mask_kernel pass follows (a ReLU mask on the engine)
+  bool note_2gib;        // a halo-patch geometry left to the pipeline / engine for a tensor of 2 GiB or more: the entry point says so, once per process
+  int grid; size_t lds;  // thin and halo kernels
+  int L, kh, kw, ch;     // thin: cin1_fwd<kh, kw>; cout1<L, kh, kw, ch> (0: the run-time loops)
+  int th, tw, dir, nitems; bool relu;      // halo: patch, direction, ReLU instantiation, work items (one per workgroup)
+  NtPlan nt; long shift; // pipeline: whole tiles only, n_dp = classes x tiles; bytes the descriptor starts in front of the tensor
+  int tile; bool vec;    // engine (forward, data gradient and weight gradient): row of igemm.hip's tile table, 16-byte loads
+  int splits; bool wide_reduce; size_t need_bytes, ws_bytes;      // weight gradient: slabs (thin: their count), the reduce, the workspace the call uses
+  //                                                                  and what re2e_conv_wgrad_workspace_bytes answers (it sees no pointers and no stream)
+};
+ConvPlan plan_conv(const ConvIn& in);
+// The parts of the plan the kernels' own files state (pure: eligibility and launch geometry, nothing enqueued), and the functions that enqueue a
+// plan -- they cannot decline.  thinconv.hip: direct kernels for Cout == 1 (forward) and Cin == 1 / Cout == 1 (weight gradient), where an MFMA tile
+// would be >= 97 % padding; thin_wgrad_slabs returns 0 when the shape is not covered.
+bool thin_fwd_plan(const ConvIn& in, bool no_rows, ConvPlan& p);
+void thin_conv_forward(const ConvPlan& p, const ConvGeom& g, const float* wg, int Cout, const OutMap& o, const float* bias, int act, float beta, hipStream_t st);
+int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows);
+void thin_wgrad(const ConvGeom& g, const float* dout, int Cout, float* slabs, int nslab, hipStream_t st);
+// conv3x3.hip: 3x3 / stride-1 / pad-1 convolutions with C % 16 == 0 and Cout % 64 == 0 (halo patch staged once per channel chunk, taps walked in LDS)
+bool halo_plan(const ConvIn& in, ConvPlan& p);
+void halo_note_2gib(const ConvIn& in);
+void halo_conv3x3(const ConvPlan& p, const ConvGeom& g, const float* wg, int Cout, float* out, const float* bias, int act, float beta, const float* mask,
                   hipStream_t st, float* pool_out = nullptr, unsigned char* pool_idx = nullptr);
+// gemm_nt.hip: the pipeline's implicit-GEMM form (forward / data gradient; ncls = 4: the output parity classes of a stride-2 data gradient), whole tiles only
+bool conv_nt2_plan(const ConvIn& in, ConvPlan& p);
+void conv_nt2(const ConvPlan& p, const ConvGeom& g, int M, const float* wg, int Cout, float* out, long ldc, const float* bias, int act, float beta, int ncls,
+              const int* cls_oy0, const int* cls_ox0, long cls_wstride, int remap, int OHF, int OWF, int osy, int osx, const int* ooy, const int* oox,
+              hipStream_t st);
+// What the fused Winograd entry points take, stated once: the entry points answer RE2E_EUNSUPPORTED from these, the layer-level plan
+// (igemm.hip plan_conv_layer) chooses with them.  winograd.hip / wino_wgrad.hip / wino44.hip.
+enum WinoFit { kWinoFits, kWinoChannels, kWinoGroups, kWinoBytes, kWinoItems };
+WinoFit wino3x3_fit(int NI, int H, int W, int C, int Cout);
+int wino3x3_images(int N, int H, int W, int C, int Cout);      // images per launch: all of them, or as many as keep both tensors under 2 GiB
+WinoFit wino3x3_wgrad_fit(int NI, int H, int W, int C, int Cout);
+WinoFit wino4x4_fit(int NI, int H, int W, int C, int Cout, int pad);
+WinoFit wino4x4_wgrad_fit(int NI, int H, int W, int C, int Cout, int pad);

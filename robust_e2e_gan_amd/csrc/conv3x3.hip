@@ -371,81 +371,79 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs p) {
   }
 }
 
+// dynamic LDS of one workgroup: the staged patch with its halo + the 9 x 64 x 16 weight slice
+constexpr size_t halo_lds_bytes(int TH, int TW) { return (size_t)(((TW + 2) * (TH + 2) * 4 + 255) / 256 * 64 * LDC + 9 * 64 * LDC) * sizeof(float); }
+
+// One work item per workgroup: since an item's set-up is a handful of scalar instructions (lane-constant addresses), a fresh workgroup per
+// item costs nothing measurable alone on the chip (conv1_2 0.851 of peak against 0.838 / 0.852 / 0.850 with 2 / 3 items / persistent
+// workgroups, conv2_2 0.811 against 0.770 / 0.768 / 0.820: no half-empty last round) and its 70 us lifetime interleaves best with the other
+// streams of the training step (72.41 -> 72.07 ms against the former 2-3 items; 3 + 3 runs, one GPU session).  The kernel keeps its item loop.
 template <int TH, int TW, int DIR, bool RELU>
 void launch_halo(const HaloArgs& a, hipStream_t st) {
-  constexpr int HP = (TW + 2) * (TH + 2);
-  constexpr int AIT = (HP * 4 + 255) / 256;
-  constexpr size_t lds = (size_t)(AIT * 64 * LDC + 9 * 64 * LDC) * sizeof(float);
+  constexpr size_t lds = halo_lds_bytes(TH, TW);
   static LdsLimit lim;
   lim.ensure(reinterpret_cast<const void*>(&conv3x3_halo_kernel<TH, TW, DIR, RELU>), lds);
-  static const int slots = [] {          // two workgroups per CU (LDS and registers both allow exactly two)
-    if (exp_env("RE2E_HALO_SLOTS")) return atoi(exp_env("RE2E_HALO_SLOTS"));   // occupancy experiments
-    return 2 * re2e_cu_count();
-  }();
-  // items per workgroup: RE2E_HALO_IPW = 0 persistent, n > 0 fixed.  Default 1: since an item's set-up is a handful of scalar
-  // instructions (lane-constant addresses), a fresh workgroup per item costs nothing measurable alone on the chip (conv1_2 0.851
-  // of peak against 0.838 / 0.852 / 0.850 with 2 / 3 / persistent, conv2_2 0.811 against 0.770 / 0.768 / 0.820: no half-empty
-  // last round) and its 70 us lifetime interleaves best with the other streams of the training step (72.41 -> 72.07 ms against
-  // the former 2-3 items; 3 + 3 runs, one GPU session).
-  static const int ipw_env = exp_env("RE2E_HALO_IPW") ? atoi(exp_env("RE2E_HALO_IPW")) : -1;
-  HaloArgs b = a;
-  b.ipw = ipw_env >= 0 ? ipw_env : 1;
-  const int nwg = b.ipw == 0 ? (a.nitems < slots ? a.nitems : slots) : (a.nitems + b.ipw - 1) / b.ipw;
   static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;   // tools/igemm_table.py joins this with a kernel trace
   if (log_calls)
     fprintf(stderr, "[igemm] A=Halo%s B=DenseK tile=%dx%dx%d vec=1 M=%d N=%d K=%d splits=1\n", DIR > 0 ? "F" : "D", TH * TW, NT, CK,
             a.NI * a.H * a.W, a.Cout, 9 * a.C);
-  hipLaunchKernelGGL((conv3x3_halo_kernel<TH, TW, DIR, RELU>), dim3((unsigned)nwg), dim3(256), lds, st, b);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<TH, TW, DIR, RELU>), dim3((unsigned)a.nitems), dim3(256), lds, st, a);
 }
 
 }  // namespace
 
-// Returns true when the geometry is a 3x3 / stride-1 / pad-1 convolution (forward or data-gradient form) this kernel
-// covers and the launch was enqueued; false -> the caller uses the general engine.
-bool halo_conv3x3(const ConvGeom& g, const float* wg, int Cout, float* out, const float* bias, int act, float beta, const float* mask,
-                  hipStream_t st, float* pool_out, unsigned char* pool_idx) {
-  static const bool off = exp_env("RE2E_NO_HALO") != nullptr;     // A/B measurements against the general engine
-  if (off) return false;
-  if (g.KH != 3 || g.KW != 3 || g.SY != 1 || g.SX != 1 || g.PH != g.H || g.PW != g.W) return false;
+// The halo-patch kernel's part of plan_conv: true when the geometry is a 3x3 / stride-1 / pad-1 convolution (forward or data-gradient form)
+// this kernel covers, with the patch shape, instantiation and grid; false -> the pipeline or the general engine.
+bool halo_plan(const ConvIn& in, ConvPlan& p) {
+  if (in.KH != 3 || in.KW != 3 || in.SY != 1 || in.SX != 1 || in.PH != in.H || in.PW != in.W) return false;
   int dir;
-  if (g.DY == 1 && g.DX == 1 && g.OY0 == -1 && g.OX0 == -1) dir = 1;
-  else if (g.DY == -1 && g.DX == -1 && g.OY0 == 1 && g.OX0 == 1) dir = -1;
+  if (in.DY == 1 && in.DX == 1 && in.OY0 == -1 && in.OX0 == -1) dir = 1;
+  else if (in.DY == -1 && in.DX == -1 && in.OY0 == 1 && in.OX0 == 1) dir = -1;
   else return false;
-  if (g.C % CK || Cout % NT) return false;
-  if (act != RE2E_ACT_NONE && act != RE2E_ACT_RELU) return false;
-  if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(mask) | reinterpret_cast<uintptr_t>(pool_out)) & 15) return false;
-  if (pool_out && (act != RE2E_ACT_RELU || beta != 0.f || mask || dir != 1 || (reinterpret_cast<uintptr_t>(pool_idx) & 3))) return false;
-  const long in_bytes = (long)g.NI * g.H * g.W * g.C * 4, wg_bytes = (long)Cout * 9 * g.C * 4;
-  const long out_bytes = (long)g.NI * g.H * g.W * Cout * 4;
-  if (in_bytes >= 0x7FFFFF00L || wg_bytes >= 0x7FFFFF00L || out_bytes >= 0x7FFFFF00L) {
-    // the buffer descriptors address 2 GiB: a geometry this kernel would otherwise cover goes to the general engine (~15 % slower
-    // at the VGG shapes) -- say so once instead of losing the time silently (e.g. B = 64 per GPU at T = 800: 2.1 GB activations)
-    static std::once_flag warned;
-    std::call_once(warned, [&] {
-      fprintf(stderr, "[re2e] note: 3x3 convolution %dx%dx%d, %d->%d channels has a tensor of >= 2 GiB: the halo-patch kernel declines it, "
-                      "the general implicit-GEMM engine runs it (slower; split the batch to stay below 2 GiB per tensor)\n",
-              g.NI, g.H, g.W, g.C, Cout);
-    });
-    return false;
-  }
-  if ((reinterpret_cast<uintptr_t>(g.in) | reinterpret_cast<uintptr_t>(wg)) & 15) return false;
+  if (in.C % CK || in.Cout % NT) return false;
+  if (in.act != RE2E_ACT_NONE && in.act != RE2E_ACT_RELU) return false;
+  if (!in.out16 || !in.mask16 || !in.pool16) return false;
+  if (in.pool && (in.act != RE2E_ACT_RELU || in.beta != 0.f || in.mask || dir != 1 || !in.idx4)) return false;
+  const long in_bytes = (long)in.NI * in.H * in.W * in.C * 4, wg_bytes = (long)in.Cout * 9 * in.C * 4;
+  const long out_bytes = (long)in.NI * in.H * in.W * in.Cout * 4;
+  // the buffer descriptors address 2 GiB: a geometry this kernel would otherwise cover goes to the general engine (~15 % slower at the VGG shapes)
+  if (in_bytes >= 0x7FFFFF00L || wg_bytes >= 0x7FFFFF00L || out_bytes >= 0x7FFFFF00L) { p.note_2gib = true; return false; }
+  if (!in.in16 || !in.wg16) return false;
+  // patch shape: 16 x 16 (smaller halo) unless 32 x 8 wastes fewer padded pixels (W = 40: 416 x 40 against 400 x 48)
+  const long pad16 = (long)cdiv(in.H, 16) * 16 * cdiv(in.W, 16) * 16, pad8 = (long)cdiv(in.H, 32) * 32 * cdiv(in.W, 8) * 8;
+  const bool wide = pad16 <= pad8;
+  p.th = wide ? 16 : 32; p.tw = wide ? 16 : 8;
+  const long nitems = (long)in.NI * cdiv(in.W, p.tw) * cdiv(in.H, p.th) * (in.Cout / NT);
+  if (nitems >= 0x7FFFFFF0L) return false;
+  p.route = kHalo; p.dir = dir; p.relu = in.act == RE2E_ACT_RELU;
+  p.nitems = p.grid = (int)nitems;
+  p.lds = wide ? halo_lds_bytes(16, 16) : halo_lds_bytes(32, 8);
+  return true;
+}
+
+// ... say so once instead of losing the time silently (e.g. B = 64 per GPU at T = 800: 2.1 GB activations)
+void halo_note_2gib(const ConvIn& in) {
+  static std::once_flag warned;
+  std::call_once(warned, [&] {
+    fprintf(stderr, "[re2e] note: 3x3 convolution %dx%dx%d, %d->%d channels has a tensor of >= 2 GiB: the halo-patch kernel declines it, "
+                    "the general implicit-GEMM engine runs it (slower; split the batch to stay below 2 GiB per tensor)\n",
+            in.NI, in.H, in.W, in.C, in.Cout);
+  });
+}
+
+// Enqueue the halo-patch plan.
+void halo_conv3x3(const ConvPlan& p, const ConvGeom& g, const float* wg, int Cout, float* out, const float* bias, int act, float beta, const float* mask,
+                  hipStream_t st, float* pool_out, unsigned char* pool_idx) {
   HaloArgs a;
   a.in = g.in; a.wg = wg; a.out = pool_out ? nullptr : out; a.bias = bias; a.mask = mask; a.pool_out = pool_out; a.pool_idx = pool_idx;
   a.NI = g.NI; a.H = g.H; a.W = g.W; a.C = g.C; a.Cout = Cout; a.act = act; a.beta = beta;
-  a.ngn = Cout / NT; a.in_bytes = (unsigned)in_bytes; a.wg_bytes = (unsigned)wg_bytes; a.out_bytes = (unsigned)out_bytes;
-  // patch shape: 16 x 16 (smaller halo) unless 32 x 8 wastes fewer padded pixels (W = 40: 416 x 40 against 400 x 48)
-  const long pad16 = (long)cdiv(g.H, 16) * 16 * cdiv(g.W, 16) * 16, pad8 = (long)cdiv(g.H, 32) * 32 * cdiv(g.W, 8) * 8;
-  const bool wide = pad16 <= pad8;
-  const int TH = wide ? 16 : 32, TW = wide ? 16 : 8;
-  a.tiles_x = cdiv(g.W, TW); a.tiles_y = cdiv(g.H, TH);
-  const long nitems = (long)a.NI * a.tiles_x * a.tiles_y * a.ngn;
-  if (nitems >= 0x7FFFFFF0L) return false;
-  a.nitems = (int)nitems;
-  const bool relu = act == RE2E_ACT_RELU;
+  a.ngn = Cout / NT; a.in_bytes = (unsigned)((long)g.NI * g.H * g.W * g.C * 4); a.wg_bytes = (unsigned)((long)Cout * 9 * g.C * 4);
+  a.out_bytes = (unsigned)((long)g.NI * g.H * g.W * Cout * 4);
+  a.tiles_x = cdiv(g.W, p.tw); a.tiles_y = cdiv(g.H, p.th);
+  a.nitems = p.nitems; a.ipw = 1;
 #define HALO_GO(TH_, TW_) do { \
-    if (dir > 0) { if (relu) launch_halo<TH_, TW_, 1, true>(a, st); else launch_halo<TH_, TW_, 1, false>(a, st); } \
-    else { if (relu) launch_halo<TH_, TW_, -1, true>(a, st); else launch_halo<TH_, TW_, -1, false>(a, st); } } while (0)
-  if (wide) HALO_GO(16, 16); else HALO_GO(32, 8);
+    if (p.dir > 0) { if (p.relu) launch_halo<TH_, TW_, 1, true>(a, st); else launch_halo<TH_, TW_, 1, false>(a, st); } \
+    else { if (p.relu) launch_halo<TH_, TW_, -1, true>(a, st); else launch_halo<TH_, TW_, -1, false>(a, st); } } while (0)
+  if (p.th == 16) HALO_GO(16, 16); else HALO_GO(32, 8);
 #undef HALO_GO
-  return true;
 }

@@ -519,17 +519,15 @@ const NtVariant VARIANTS[] = {RE2E_NT_VARIANTS(RE2E_NT_ROW)};
 
 // Experiment switches of this file (experiments build; the shipped library answers "unset"), all read here, at every call so that one process can
 // compare forms:  RE2E_NT2 = "old" (igemm.hip's engine) | "<variant>[,<sk>]" (a row of the table, 0 = choose; sk = 0 whole tiles only, 1 stream-K tail
-// where the model says it pays (default), 2 wherever there is a partial round);  RE2E_CONV_NT2 = 0: convolutions stay on the gather engine;
-// RE2E_NT2_TAILWG: unit ranges per CU of an all-tail 4-wave product;  RE2E_NT2_LOG: one line per plan.
-struct NtSwitches { bool old, conv_off, log; int variant, sk, tailwg; };
+// where the model says it pays (default), 2 wherever there is a partial round);  RE2E_NT2_TAILWG: unit ranges per CU of an all-tail 4-wave product;  RE2E_NT2_LOG: one line per plan.
+struct NtSwitches { bool old, log; int variant, sk, tailwg; };
 NtSwitches nt_switches() {
-  NtSwitches s = {false, false, exp_env("RE2E_NT2_LOG") != nullptr, 0, 1, 1};
+  NtSwitches s = {false, exp_env("RE2E_NT2_LOG") != nullptr, 0, 1, 1};
   if (const char* e = exp_env("RE2E_NT2")) {
     s.old = e[0] == 'o';
     s.variant = atoi(e);
     if (const char* c = strchr(e, ',')) s.sk = atoi(c + 1);
   }
-  if (const char* e = exp_env("RE2E_CONV_NT2")) s.conv_off = atoi(e) == 0;
   if (const char* e = exp_env("RE2E_NT2_TAILWG")) s.tailwg = atoi(e);
   return s;
 }
@@ -645,35 +643,43 @@ int* nt2_ticket_slice() {
   return pool[dev] + (size_t)(next[dev]++ % POOL_SLICES) * POOL_SLICE_INTS;
 }
 
-// Implicit-GEMM convolution forward / data gradient on the same pipeline (MODE 2).  g: geometry of ONE class (g.in = the image); ncls = 1, or 4 with
-// per-class offsets / weight sets / output positions (stride-2 data gradient).  Returns 1 when launched here, 0 when left to igemm.hip's gather engine.
-int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, long ldc, const float* bias, int act, float beta, int ncls,
-             const int* cls_oy0, const int* cls_ox0, long cls_wstride, int remap, int OHF, int OWF, int osy, int osx, const int* ooy, const int* oox,
-             hipStream_t st) {
-  const NtSwitches sw = nt_switches();
-  if (sw.conv_off) return 0;
-  const int K = g.KH * g.KW * g.C;
-  if (g.C % 16 || Cout % 4 || g.KH * g.KW > 32 || g.KH * g.KW < 2 || ncls < 1 || ncls > 4) return 0;
-  if ((reinterpret_cast<uintptr_t>(g.in) & 15) || (reinterpret_cast<uintptr_t>(wg) & 15) || (reinterpret_cast<uintptr_t>(out) & 15) || ldc % 4) return 0;
-  if (bias && (reinterpret_cast<uintptr_t>(bias) & 15)) return 0;
-  if (act == RE2E_ACT_SIGMOID_MASK_MUL || (long)M * ncls > 0x7FFFFFFFL || M < 256) return 0;
+// Implicit-GEMM convolution forward / data gradient on the same pipeline (MODE 2): the pipeline's part of plan_conv.  false: the geometry is left
+// to igemm.hip's gather engine.  Whole tiles only (the convolution entry points carry no workspace for partial slabs; the step's shapes fill their
+// rounds: 500 / 250 / 4000 tiles), n_dp counted over the classes.
+bool conv_nt2_plan(const ConvIn& in, ConvPlan& p) {
+  const int ncls = in.kind == kConvDgradS2 ? 4 : 1, M = in.NI * in.PH * in.PW, Cout = in.Cout;
+  const int K = in.KH * in.KW * in.C;
+  if (in.C % 16 || Cout % 4 || in.KH * in.KW > 32 || in.KH * in.KW < 2) return false;
+  if (!in.in16 || !in.wg16 || !in.out16 || !in.bias16) return false;
+  if (in.act == RE2E_ACT_SIGMOID_MASK_MUL || (long)M * ncls > 0x7FFFFFFFL || M < 256) return false;
   // the most negative tap position over all classes fixes how far in front of the tensor the descriptor starts
-  const int ylo = g.DY < 0 ? (g.KH - 1) * g.DY : 0, xlo = g.DX < 0 ? (g.KW - 1) * g.DX : 0;
+  const int ylo = in.DY < 0 ? (in.KH - 1) * in.DY : 0, xlo = in.DX < 0 ? (in.KW - 1) * in.DX : 0;
   int pady = 0, padx = 0;
   for (int c = 0; c < ncls; ++c) {
-    const int oy = (cls_oy0 ? cls_oy0[c] : g.OY0) + ylo, ox = (cls_ox0 ? cls_ox0[c] : g.OX0) + xlo;
+    const int oy = (ncls > 1 ? in.cls_o0[c >> 1] : in.OY0) + ylo, ox = (ncls > 1 ? in.cls_o0[c & 1] : in.OX0) + xlo;
     if (-oy > pady) pady = -oy;
     if (-ox > padx) padx = -ox;
   }
-  const long shift = ((long)pady * g.W + padx) * g.C * 4;
-  const long in_bytes = (long)g.NI * g.H * g.W * g.C * 4;
+  const long shift = ((long)pady * in.W + padx) * in.C * 4;
+  const long in_bytes = (long)in.NI * in.H * in.W * in.C * 4;
   // rows past the last pixel (phantom rows of the last tile) carry an empty tap mask; their offsets may be anything, but stay 31-bit
-  if (in_bytes + shift + (long)(g.KH * g.W + g.KW) * g.C * 4 * 4 >= 0x7FFFFFF0L) return 0;
-  if ((long)ncls * Cout * K * 4 >= 0x7FFFFFF0L) return 0;
-  // whole tiles only (the convolution entry points carry no workspace for partial slabs; the step's shapes fill their rounds: 500 / 250 / 4000 tiles)
-  NtPlan q = nt2_plan(M, Cout, K, re2e_stream_is_filler(st), re2e_cu_count(), false);
-  if (!q.variant || g.C % q.bk) return 0;
+  if (in_bytes + shift + (long)(in.KH * in.W + in.KW) * in.C * 4 * 4 >= 0x7FFFFFF0L) return false;
+  if ((long)ncls * Cout * K * 4 >= 0x7FFFFFF0L) return false;
+  NtPlan q = nt2_plan(M, Cout, K, in.filler, in.cus, false);
+  if (!q.variant || in.C % q.bk) return false;
   q.n_dp = ncls * q.ntm * q.ntn;
+  p.nt = q; p.shift = shift;
+  return true;
+}
+
+// Enqueue the pipeline plan.  g: geometry of ONE class (g.in = the image); ncls = 1, or 4 with per-class offsets / weight sets / output positions
+// (stride-2 data gradient).
+void conv_nt2(const ConvPlan& p, const ConvGeom& g, int M, const float* wg, int Cout, float* out, long ldc, const float* bias, int act, float beta, int ncls,
+              const int* cls_oy0, const int* cls_ox0, long cls_wstride, int remap, int OHF, int OWF, int osy, int osx, const int* ooy, const int* oox,
+              hipStream_t st) {
+  const NtPlan& q = p.nt;
+  const int K = g.KH * g.KW * g.C;
+  const long shift = p.shift, in_bytes = (long)g.NI * g.H * g.W * g.C * 4;
   NtArgs a;
   memset(&a, 0, sizeof(a));
   a.A = reinterpret_cast<const float*>(reinterpret_cast<const char*>(g.in) - shift); a.B = wg; a.C = out;
@@ -688,9 +694,8 @@ int conv_nt2(const ConvGeom& g, int M, const float* wg, int Cout, float* out, lo
     a.ooy[c] = ooy ? ooy[c < ncls ? c : 0] : 0; a.oox[c] = oox ? oox[c < ncls ? c : 0] : 0;
   }
   a.a_shift = (unsigned)shift;
-  if (sw.log) fprintf(stderr, "[conv2] %dx%dx%d cls %d variant %d tiles %ld dp %d sk %d\n", M, Cout, K, ncls, q.variant, (long)ncls * q.ntm * q.ntn, q.n_dp, q.g_sk);
+  if (nt_switches().log) fprintf(stderr, "[conv2] %dx%dx%d cls %d variant %d tiles %ld dp %d sk %d\n", M, Cout, K, ncls, q.variant, (long)ncls * q.ntm * q.ntn, q.n_dp, q.g_sk);
   nt2_run<2>(a, q, (long)M * ncls, K, 1, st);
-  return 1;
 }
 
 // Enqueue a pipeline plan of plan_gemm (igemm.hip), which has checked the operands (nt2_operands_ok) and, for a stream-K tail, the workspace and

@@ -831,13 +831,12 @@ constexpr TileRow kTiles[] = {RE2E_ENGINE_TILES(RE2E_TILE_ROW)};
 constexpr unsigned bit(EngineTile t) { return 1u << t; }
 
 // Experiment switches of this file (experiments build; the shipped library answers "unset"), all read here.  They choose between SHIPPED forms for
-// same-session A/B runs: RE2E_NO_SKINNY_GEMM (M <= 32 products on the 32x128 engine tile), RE2E_NO_ROW_TAIL, RE2E_NO_THIN (Cin == 1 / Cout == 1
-// convolutions through the implicit GEMM), RE2E_TN_XCD_KSLICE = 0 (tiles keep their XCD for all K slices, rounds 1-4), RE2E_IGEMM_NOMEM.
-struct EngineSwitches { bool no_skinny_wg, no_row_tail, no_thin, no_xcd_kslice, nomem; };
+// same-session A/B runs: RE2E_NO_SKINNY_GEMM (M <= 32 products on the 32x128 engine tile), RE2E_NO_ROW_TAIL, RE2E_TN_XCD_KSLICE = 0 (tiles keep
+// their XCD for all K slices, rounds 1-4), RE2E_IGEMM_NOMEM.  (The convolutions' switches: conv_switches below.)
+struct EngineSwitches { bool no_skinny_wg, no_row_tail, no_xcd_kslice, nomem; };
 EngineSwitches engine_switches() {      // (read at every call: tools/bench_tn_xcd.py flips one between calls)
   const char* zx = exp_env("RE2E_TN_XCD_KSLICE");
-  return {exp_env("RE2E_NO_SKINNY_GEMM") != nullptr, exp_env("RE2E_NO_ROW_TAIL") != nullptr, exp_env("RE2E_NO_THIN") != nullptr, zx && atoi(zx) == 0,
-          exp_env("RE2E_IGEMM_NOMEM") != nullptr};
+  return {exp_env("RE2E_NO_SKINNY_GEMM") != nullptr, exp_env("RE2E_NO_ROW_TAIL") != nullptr, zx && atoi(zx) == 0, exp_env("RE2E_IGEMM_NOMEM") != nullptr};
 }
 
 template <class LA, class LB, class CF, bool VEC>
@@ -1215,39 +1214,119 @@ __global__ void weight_gather_kernel(const float* W, float* dst, int Cout, int C
   dst[i] = W[(((long)co * Cin + ci) * KH + kh) * KW + kw];
 }
 
-// The engine's tile of a convolution forward / data gradient: the column count picks the narrow tiles, else the big tile of its form
-static EngineTile conv_tile(int Cout, int M, bool vec, bool filler) {
-  return Cout <= 32 ? kT256x32 : Cout <= 64 ? kT256x64 : big_tile(true, vec, M, filler);
-}
-
-template <bool V>
-static void conv_engine(const ConvGeom& g, int M, int K, const float* wg, int Cout, const Epi& ep, hipStream_t st) {
-  ConvK la{g, g.in, (unsigned)((long)g.NI * g.H * g.W * g.C * 4), M, K};
-  DenseK lb{wg, kbytes(Cout, K, K), (long)K, Cout, K};
-  launch_tile<ConvK, DenseK, V, big_built<V>(true) | bit(kT256x64) | bit(kT256x32)>(conv_tile(Cout, M, V, re2e_stream_is_filler(st)), la, lb, ep, K, st);
-}
-
-// The shared tail of the forward / data-gradient entry points, behind the thin and the halo-patch kernels: gemm_nt.hip's pipeline where it takes
-// the geometry (ncls classes with their input offsets oy0 / ox0 and output positions ooy / oox; not with a ReLU mask), else the gather engine.
-static void conv_pipeline_or_engine(const ConvGeom& g, const float* wg, int Cout, Epi& ep, int ncls, const int* oy0, const int* ox0, const int* ooy,
-                                    const int* oox, bool mask, hipStream_t st) {
-  const int K = g.KH * g.KW * g.C;
-  if (!mask && conv_nt2(g, ep.M, wg, Cout, ep.C, Cout, ep.bias, ep.act, ep.beta, ncls, oy0, ox0, ep.cls_wstride, ep.remap, ep.OHF, ep.OWF, ep.osy, ep.osx, ooy,
-                        oox, st))
-    return;
-  if (g.C % 4 == 0 && aligned16(g.in) && aligned16(wg)) conv_engine<true>(g, ep.M, K, wg, Cout, ep, st);
-  else conv_engine<false>(g, ep.M, K, wg, Cout, ep, st);
-}
-
-// Forward / data-gradient implicit GEMM:
-//   out[pix(n,py,px)][co] = act( sum_{kh,kw,ci} in[n][py*SY+kh*DY+OY0][px*SX+kw*DX+OX0][ci] * w[co][kh][kw][ci] + bias[co] )
-// written at out[((n*OHF + py*osy+ooy)*OWF + px*osx+oox)*Cout + co].
 // out = mask > 0 ? out : 0 (four channels per thread when the channel count allows): the separate pass of re2e_conv_igemm_masked
 // for geometries the halo-patch kernel does not cover
 __global__ void relu_mask_kernel(float* __restrict__ out, const float* __restrict__ mask, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) out[i] = mask[i] > 0.f ? out[i] : 0.f;
 }
 
+// ---- which kernel serves a convolution: ONE plan per call, made before anything is enqueued ----------------------------------------------------
+// plan_conv is a pure host function of ConvIn (common.h).  re2e_conv_igemm, re2e_conv_igemm_masked, re2e_conv3x3_relu_pool, re2e_conv_dgrad_s2,
+// re2e_conv_wgrad and re2e_conv_wgrad_workspace_bytes enqueue exactly what it names; re2e_conv_plan prints it (tests/test_abi.py holds the table of
+// expected plans).  Forward / data gradient, in order:
+//   thin      Cin == 1 or Cout == 1: thinconv.hip's direct kernels (thin_fwd_plan)
+//   halo      3x3 / stride 1 / pad 1 with C % 16 == 0 and Cout % 64 == 0, tensors under 2 GiB: conv3x3.hip (halo_plan); the ReLU mask and the
+//             fused pool are its epilogues
+//   pipeline  C % 16 == 0, from 256 rows, no ReLU mask: gemm_nt.hip's LDS-DMA kernel, whole tiles (conv_nt2_plan)
+//   engine    everything else: a row of the tile table, and the separate relu_mask_kernel pass where a mask is asked for
+// Weight gradient: thin (Cin == 1 / Cout == 1, its slab count) or the engine (tile, K slices = slabs, the reduce, which always runs: it applies
+// the weight-layout permute).  The slice count is a function of the shape alone -- the ladder for 16-byte loadable operands -- so that
+// re2e_conv_wgrad_workspace_bytes, which sees no pointers, sizes what the launch uses; `vec` then only picks between tiles that are built.
+
+// Experiment switches of the convolutions (experiments build; the shipped library answers "unset"), all read here, at the top of the plan.  They
+// choose between SHIPPED forms for same-session A/B runs: RE2E_NO_THIN (Cin == 1 / Cout == 1 convolutions through the implicit GEMM),
+// RE2E_NO_COUT1_ROWS (the Cout == 1 row-tile kernel), RE2E_NO_HALO (3x3 layers on the pipeline / engine), RE2E_CONV_NT2 = 0 (convolutions stay on
+// the gather engine).
+struct ConvSwitches { bool no_thin, no_cout1_rows, no_halo, no_nt2; };
+static ConvSwitches conv_switches() {
+  const char* nt2 = exp_env("RE2E_CONV_NT2");
+  return {exp_env("RE2E_NO_THIN") != nullptr, exp_env("RE2E_NO_COUT1_ROWS") != nullptr, exp_env("RE2E_NO_HALO") != nullptr, nt2 && atoi(nt2) == 0};
+}
+
+// The engine's tile of a convolution forward / data gradient: the column count picks the narrow tiles, else the big tile of its form
+static EngineTile conv_tile(int Cout, int M, bool vec, bool filler) {
+  return Cout <= 32 ? kT256x32 : Cout <= 64 ? kT256x64 : big_tile(true, vec, M, filler);
+}
+static EngineTile wgrad_tile(int Mrows, int Cout, bool vec) {
+  if (Cout <= 32) return kT256x32;
+  if (Cout <= 64) return vec && Mrows % 192 == 0 && Mrows % 256 != 0 ? kT192x64 : kT256x64;
+  return vec && Mrows % 192 == 0 && Mrows % 128 != 0 ? kT192x64 : kT128;      // conv2_1: 576 x 128; else the 4-wave big tile (see big_tile)
+}
+
+static void plan_wgrad(const ConvIn& in, const ConvSwitches& sw, ConvPlan& p) {
+  const int Mrows = in.KH * in.KW * in.C, Cout = in.Cout;
+  const long P = (long)in.NI * in.PH * in.PW, rows = (long)in.NI * in.PH;
+  const bool aligned = in.in16 && in.wg16;
+  p.vec = aligned && in.C % 4 == 0 && Cout % 4 == 0;
+  p.tile = wgrad_tile(Mrows, Cout, p.vec);
+  const int thin = (in.C == 1 || Cout == 1) && !sw.no_thin ? thin_wgrad_slabs(in.C, Cout, in.KH, in.KW, P, rows) : 0;
+  const int engine = pick_splits(Mrows, Cout, (int)P, wgrad_tile(Mrows, Cout, true), in.cus);
+  p.route = thin && aligned ? (in.C == 1 ? kWgradCin1 : kWgradCout1) : kWgradEngine;
+  p.splits = p.route == kWgradEngine ? engine : thin;
+  p.wide_reduce = p.splits >= 64 && (long)Mrows * Cout <= 65536;
+  p.need_bytes = (size_t)p.splits * Mrows * Cout * sizeof(float);
+  p.ws_bytes = (size_t)(thin ? thin : engine) * Mrows * Cout * sizeof(float);      // aligned operands: what the caller sized before it had pointers
+}
+
+ConvPlan plan_conv(const ConvIn& in) {
+  ConvPlan p;
+  memset(&p, 0, sizeof(p));
+  const ConvSwitches sw = conv_switches();
+  if (in.kind == kConvWgrad) { plan_wgrad(in, sw, p); return p; }
+  const bool one = in.kind == kConvIgemm;      // the four classes of re2e_conv_dgrad_s2 go to the pipeline or the engine
+  if (one && !in.pool && (in.Cout == 1 || in.C == 1) && !sw.no_thin && !in.mask && thin_fwd_plan(in, sw.no_cout1_rows, p)) return p;
+  if (one && !in.remap && !sw.no_halo && halo_plan(in, p)) return p;
+  if (in.pool) { p.route = kConvNone; return p; }
+  if (!in.mask && !sw.no_nt2 && conv_nt2_plan(in, p)) { p.route = kConvPipeline; return p; }
+  p.route = kConvEngine;
+  p.vec = in.C % 4 == 0 && in.in16 && in.wg16;
+  p.tile = conv_tile(in.Cout, in.NI * in.PH * in.PW, p.vec, in.filler);
+  p.mask_pass = in.mask;
+  return p;
+}
+
+static inline bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }      // absent operands count as aligned
+
+static ConvIn conv_in(ConvKind kind, const ConvGeom& g, const float* wg, int Cout, const float* out, const float* bias, int act, float beta, bool remap,
+                      const float* mask, const float* pool_out, const unsigned char* pool_idx, hipStream_t st) {
+  ConvIn in;
+  memset(&in, 0, sizeof(in));
+  in.kind = kind;
+  in.NI = g.NI; in.H = g.H; in.W = g.W; in.C = g.C; in.PH = g.PH; in.PW = g.PW; in.KH = g.KH; in.KW = g.KW;
+  in.SY = g.SY; in.SX = g.SX; in.DY = g.DY; in.DX = g.DX; in.OY0 = g.OY0; in.OX0 = g.OX0;
+  in.Cout = Cout; in.act = act; in.beta = beta; in.remap = remap; in.mask = mask != nullptr; in.pool = pool_out != nullptr;
+  in.in16 = al16(g.in); in.wg16 = al16(wg); in.out16 = al16(out); in.bias16 = al16(bias); in.mask16 = al16(mask); in.pool16 = al16(pool_out);
+  in.idx4 = (reinterpret_cast<uintptr_t>(pool_idx) & 3) == 0;
+  in.filler = re2e_stream_is_filler(st); in.cus = re2e_cu_count();
+  return in;
+}
+
+template <bool V>
+static void conv_engine(int tile, const ConvGeom& g, int M, int K, const float* wg, int Cout, const Epi& ep, hipStream_t st) {
+  ConvK la{g, g.in, (unsigned)((long)g.NI * g.H * g.W * g.C * 4), M, K};
+  DenseK lb{wg, kbytes(Cout, K, K), (long)K, Cout, K};
+  launch_tile<ConvK, DenseK, V, big_built<V>(true) | bit(kT256x64) | bit(kT256x32)>(tile, la, lb, ep, K, st);
+}
+
+// The shared tail of the forward / data-gradient entry points: enqueue the pipeline or the engine plan (ncls classes with their input offsets
+// oy0 / ox0 and output positions ooy / oox), and the mask pass behind the engine.
+static void conv_pipeline_or_engine(const ConvPlan& p, const ConvGeom& g, const float* wg, int Cout, Epi& ep, int ncls, const int* oy0, const int* ox0,
+                                    const int* ooy, const int* oox, const float* mask, hipStream_t st) {
+  const int K = g.KH * g.KW * g.C;
+  if (p.route == kConvPipeline)
+    conv_nt2(p, g, ep.M, wg, Cout, ep.C, Cout, ep.bias, ep.act, ep.beta, ncls, oy0, ox0, ep.cls_wstride, ep.remap, ep.OHF, ep.OWF, ep.osy, ep.osx, ooy, oox, st);
+  else if (p.vec) conv_engine<true>(p.tile, g, ep.M, K, wg, Cout, ep, st);
+  else conv_engine<false>(p.tile, g, ep.M, K, wg, Cout, ep, st);
+  if (p.mask_pass) {
+    const long n = (long)g.NI * ep.OHF * ep.OWF * Cout;
+    const long nb = (n + 255) / 256;
+    hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)(nb < 65535 * 8 ? nb : 65535 * 8)), dim3(256), 0, st, ep.C, mask, n);
+  }
+}
+
+// Forward / data-gradient implicit GEMM:
+//   out[pix(n,py,px)][co] = act( sum_{kh,kw,ci} in[n][py*SY+kh*DY+OY0][px*SX+kw*DX+OX0][ci] * w[co][kh][kw][ci] + bias[co] )
+// written at out[((n*OHF + py*osy+ooy)*OWF + px*osx+oox)*Cout + co].
 static int conv_igemm_impl(const float* in, int NI, int H, int W, int C, const float* wg, int Cout, int KH, int KW,
                            int PH, int PW, int SY, int SX, int DY, int DX, int OY0, int OX0, float* out, int OHF,
                            int OWF, int osy, int osx, int ooy, int oox, const float* bias, int act, float beta, const float* mask,
@@ -1263,22 +1342,16 @@ static int conv_igemm_impl(const float* in, int NI, int H, int W, int C, const f
   ep.C = out; ep.ldc = Cout; ep.M = NI * PH * PW; ep.N = Cout; ep.bias = bias; ep.act = act; ep.beta = beta; ep.nsplit = 1;
   ep.remap = 1; ep.PH = PH; ep.PW = PW; ep.OHF = OHF; ep.OWF = OWF; ep.osy = osy; ep.osx = osx; ep.ooy = ooy; ep.oox = oox;
   if (osy == 1 && osx == 1 && ooy == 0 && oox == 0 && OHF == PH && OWF == PW) ep.remap = 0;
-  if ((Cout == 1 || C == 1) && !engine_switches().no_thin && !mask) {
+  const ConvIn ci = conv_in(kConvIgemm, g, wg, Cout, out, bias, act, beta, ep.remap != 0, mask, nullptr, nullptr, stream);
+  const ConvPlan p = plan_conv(ci);
+  if (p.note_2gib) halo_note_2gib(ci);
+  if (p.route == kCin1Fwd || p.route == kCout1Rows || p.route == kCout1) {
     OutMap om{out, (long)Cout, ep.remap, PH, PW, OHF, OWF, osy, osx, ooy, oox};
-    if (thin_conv_forward(g, wg, Cout, om, bias, act, beta, stream)) {
-      RE2E_LAUNCH_CHECK();
-      return RE2E_OK;
-    }
-  }
-  if (!ep.remap && halo_conv3x3(g, wg, Cout, out, bias, act, beta, mask, stream)) {
-    RE2E_LAUNCH_CHECK();
-    return RE2E_OK;
-  }
-  conv_pipeline_or_engine(g, wg, Cout, ep, 1, &OY0, &OX0, &ooy, &oox, mask != nullptr, stream);
-  if (mask) {
-    const long n = (long)NI * OHF * OWF * Cout;
-    const long nb = (n + 255) / 256;
-    hipLaunchKernelGGL(relu_mask_kernel, dim3((unsigned)(nb < 65535 * 8 ? nb : 65535 * 8)), dim3(256), 0, stream, out, mask, n);
+    thin_conv_forward(p, g, wg, Cout, om, bias, act, beta, stream);
+  } else if (p.route == kHalo) {
+    halo_conv3x3(p, g, wg, Cout, out, bias, act, beta, mask, stream);
+  } else {
+    conv_pipeline_or_engine(p, g, wg, Cout, ep, 1, &OY0, &OX0, &ooy, &oox, mask, stream);
   }
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
@@ -1297,10 +1370,14 @@ extern "C" int re2e_conv3x3_relu_pool(const float* in, int NI, int H, int W, int
   RE2E_CHECK_ARG(in && wg && pooled && idx_u8, "null operand");
   RE2E_CHECK_ARG(NI > 0 && H > 0 && W > 0 && C > 0 && Cout > 0, "bad geometry");
   ConvGeom g{in, NI, H, W, C, H, W, 3, 3, 1, 1, 1, 1, -1, -1};
-  if (!halo_conv3x3(g, wg, Cout, nullptr, bias, RE2E_ACT_RELU, 0.f, nullptr, stream, pooled, idx_u8)) {
+  const ConvIn ci = conv_in(kConvIgemm, g, wg, Cout, nullptr, bias, RE2E_ACT_RELU, 0.f, false, nullptr, pooled, idx_u8, stream);
+  const ConvPlan p = plan_conv(ci);
+  if (p.note_2gib) halo_note_2gib(ci);
+  if (p.route != kHalo) {
     re2e_set_error("re2e_conv3x3_relu_pool: needs C %% 16 == 0, Cout %% 64 == 0, 16-byte aligned tensors < 2 GiB");
     return RE2E_EUNSUPPORTED;
   }
+  halo_conv3x3(p, g, wg, Cout, nullptr, bias, RE2E_ACT_RELU, 0.f, nullptr, stream, pooled, idx_u8);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }
@@ -1312,6 +1389,13 @@ extern "C" int re2e_conv_igemm_masked(const float* in, int NI, int H, int W, int
   RE2E_CHECK_ARG(osy == 1 && osx == 1 && ooy == 0 && oox == 0 && OHF == PH && OWF == PW, "the mask variant covers dense outputs only");
   return conv_igemm_impl(in, NI, H, W, C, wg, Cout, KH, KW, PH, PW, SY, SX, DY, DX, OY0, OX0, out, OHF, OWF, osy, osx, ooy, oox, nullptr,
                          RE2E_ACT_NONE, 0.f, relu_out, stream);
+}
+
+// The geometry of ONE output parity class of a stride-2 data gradient and the input offsets of parity 0 / 1:
+// oh = (2i + p + pad - kh)/2 = i + (p + pad - kh0)/2 - a with kh0 = (p + pad) & 1
+static ConvGeom dgrad_s2_geom(const float* dz, int N, int OH, int OW, int Cout, int KH, int KW, int H, int Wd, int pad, int o0[2]) {
+  for (int p = 0; p < 2; ++p) o0[p] = (p + pad - ((p + pad) & 1)) / 2;
+  return ConvGeom{dz, N, OH, OW, Cout, (H + 1) / 2, (Wd + 1) / 2, KH / 2, KW / 2, 1, 1, -1, -1, 0, 0};
 }
 
 // Stride-2 data gradient (transposed convolution) in ONE launch: blockIdx.z walks the four output parity
@@ -1328,48 +1412,36 @@ extern "C" int re2e_conv_dgrad_s2(const float* dz, int N, int OH, int OW, int Co
   const long wtot = (long)Cin * TA * TB * Cout;
   hipLaunchKernelGGL(weight_gather_kernel, dim3(cdiv(wtot, 256), 4), dim3(256), 0, stream, W, wt_ws, Cout, Cin, KH, KW, 1, TA, TB,
                      0, 0, 2, pad);
-  ConvGeom g{dz, N, OH, OW, Cout, PH, PW, TA, TB, 1, 1, -1, -1, 0, 0};
   Epi ep;
   memset(&ep, 0, sizeof(ep));
+  const ConvGeom g = dgrad_s2_geom(dz, N, OH, OW, Cout, KH, KW, H, Wd, pad, ep.cls_oy0);
+  ep.cls_ox0[0] = ep.cls_oy0[0]; ep.cls_ox0[1] = ep.cls_oy0[1];
   ep.C = dx; ep.ldc = Cin; ep.M = N * PH * PW; ep.N = Cin; ep.act = RE2E_ACT_NONE; ep.nsplit = 1;
   ep.remap = 1; ep.PH = PH; ep.PW = PW; ep.OHF = H; ep.OWF = Wd; ep.osy = 2; ep.osx = 2;
   ep.ncls = 4; ep.cls_wstride = wtot;
-  for (int p = 0; p < 2; ++p) {   // oh = (2i + p + pad - kh)/2 = i + (p + pad - kh0)/2 - a
-    const int k0 = (p + pad) & 1;
-    ep.cls_oy0[p] = (p + pad - k0) / 2; ep.cls_ox0[p] = ep.cls_oy0[p];
-  }
   // class (ph, pw) = cls >> 1, cls & 1: input offsets cls_oy0[ph] / cls_ox0[pw], output positions (2i + ph, 2j + pw)
   int oy0[4], ox0[4], oo_y[4], oo_x[4];
   for (int c = 0; c < 4; ++c) { oy0[c] = ep.cls_oy0[c >> 1]; ox0[c] = ep.cls_ox0[c & 1]; oo_y[c] = c >> 1; oo_x[c] = c & 1; }
-  conv_pipeline_or_engine(g, wt_ws, Cin, ep, 4, oy0, ox0, oo_y, oo_x, false, stream);
+  ConvIn ci = conv_in(kConvDgradS2, g, wt_ws, Cin, dx, nullptr, RE2E_ACT_NONE, 0.f, true, nullptr, nullptr, nullptr, stream);
+  ci.cls_o0[0] = ep.cls_oy0[0]; ci.cls_o0[1] = ep.cls_oy0[1];
+  conv_pipeline_or_engine(plan_conv(ci), g, wt_ws, Cin, ep, 4, oy0, ox0, oo_y, oo_x, nullptr, stream);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }
 
-// The plan of a convolution weight gradient: the kernel, its K slices (= slabs: the reduce always runs, it applies the weight-layout permute)
-// and the reduce.  The slice count is a function of the shape alone -- the ladder for 16-byte loadable operands -- so that
-// re2e_conv_wgrad_workspace_bytes, which sees no pointers, sizes what the launch uses; `vec` then only picks between tiles that are built.
-struct WgradPlan { bool thin; EngineTile tile; int splits; bool wide_reduce; };
-static EngineTile wgrad_tile(int Mrows, int Cout, bool vec) {
-  if (Cout <= 32) return kT256x32;
-  if (Cout <= 64) return vec && Mrows % 192 == 0 && Mrows % 256 != 0 ? kT192x64 : kT256x64;
-  return vec && Mrows % 192 == 0 && Mrows % 128 != 0 ? kT192x64 : kT128;      // conv2_1: 576 x 128; else the 4-wave big tile (see big_tile)
-}
-static WgradPlan plan_wgrad(int Mrows, int Cout, long P, long rows, int C, int KH, int KW, bool aligned, bool vec, int cus) {
-  WgradPlan w = {false, wgrad_tile(Mrows, Cout, vec), 0, false};
-  if ((C == 1 || Cout == 1) && !engine_switches().no_thin && aligned) {
-    w.splits = thin_wgrad_slabs(C, Cout, KH, KW, P, rows);
-    w.thin = w.splits > 0;
-  }
-  if (!w.thin) w.splits = pick_splits(Mrows, Cout, (int)P, wgrad_tile(Mrows, Cout, true), cus);
-  w.wide_reduce = w.splits >= 64 && (long)Mrows * Cout <= 65536;
-  return w;
+static ConvIn wgrad_in(const float* in, int NI, int H, int W, int C, const float* dout, int Cout, int KH, int KW, int PH, int PW, int SY, int SX, int OY0,
+                       int OX0, bool filler, int cus) {
+  ConvIn ci;
+  memset(&ci, 0, sizeof(ci));
+  ci.kind = kConvWgrad;
+  ci.NI = NI; ci.H = H; ci.W = W; ci.C = C; ci.PH = PH; ci.PW = PW; ci.KH = KH; ci.KW = KW; ci.SY = SY; ci.SX = SX; ci.DY = ci.DX = 1; ci.OY0 = OY0; ci.OX0 = OX0;
+  ci.Cout = Cout; ci.in16 = al16(in); ci.wg16 = al16(dout); ci.out16 = ci.bias16 = ci.mask16 = ci.pool16 = ci.idx4 = true;
+  ci.filler = filler; ci.cus = cus;
+  return ci;
 }
 
 extern "C" size_t re2e_conv_wgrad_workspace_bytes(int NI, int PH, int PW, int C, int Cout, int KH, int KW) {
-  const int Mrows = KH * KW * C;
-  const long P = (long)NI * PH * PW;
-  return (size_t)plan_wgrad(Mrows, Cout, P, (long)NI * PH, C, KH, KW, true, true, re2e_cu_count()).splits * Mrows * Cout * sizeof(float);
+  return plan_conv(wgrad_in(nullptr, NI, 0, 0, C, nullptr, Cout, KH, KW, PH, PW, 1, 1, 0, 0, false, re2e_cu_count())).ws_bytes;
 }
 
 // Weight gradient: dW[co][ci][kh][kw] (+)= sum_pix dout[pix][co] * in[n][py*SY+kh+OY0][px*SX+kw+OX0][ci]
@@ -1382,10 +1454,9 @@ extern "C" int re2e_conv_wgrad(const float* in, int NI, int H, int W, int C, con
   const long P = (long)NI * PH * PW;
   RE2E_CHECK_ARG(P < 2147483647L, "too many pixels");
   RE2E_CHECK_ARG((long)NI * H * W * C * 4 < 0xFFFFFFF0L && P * Cout * 4 < 0xFFFFFFF0L, "tensor larger than 4 GiB");
-  const bool aligned = aligned16(in) && aligned16(dout), vec = aligned && C % 4 == 0 && Cout % 4 == 0;
-  const WgradPlan w = plan_wgrad(Mrows, Cout, P, (long)NI * PH, C, KH, KW, aligned, vec, re2e_cu_count());
-  RE2E_CHECK_ARG(workspace_bytes >= (size_t)w.splits * Mrows * Cout * sizeof(float), "workspace too small");
-  if (w.thin) thin_wgrad(g, dout, Cout, (float*)workspace, w.splits, stream);
+  const ConvPlan w = plan_conv(wgrad_in(in, NI, H, W, C, dout, Cout, KH, KW, PH, PW, SY, SX, OY0, OX0, re2e_stream_is_filler(stream), re2e_cu_count()));
+  RE2E_CHECK_ARG(workspace_bytes >= w.need_bytes, "workspace too small");
+  if (w.route != kWgradEngine) thin_wgrad(g, dout, Cout, (float*)workspace, w.splits, stream);
   else {
     Epi ep;
     memset(&ep, 0, sizeof(ep));
@@ -1394,7 +1465,7 @@ extern "C" int re2e_conv_wgrad(const float* in, int NI, int H, int W, int C, con
     ConvM la{g, g.in, (unsigned)((long)g.NI * g.H * g.W * g.C * 4), Mrows, (int)P};
     DenseM lb{dout, kbytes(P, Cout, Cout), (long)Cout, Cout, (int)P};
     constexpr unsigned BUILT = bit(kT128) | bit(kT256x64) | bit(kT256x32);
-    if (vec) launch_tile<ConvM, DenseM, true, BUILT | bit(kT192x64)>(w.tile, la, lb, ep, (int)P, stream);
+    if (w.vec) launch_tile<ConvM, DenseM, true, BUILT | bit(kT192x64)>(w.tile, la, lb, ep, (int)P, stream);
     else launch_tile<ConvM, DenseM, false, BUILT>(w.tile, la, lb, ep, (int)P, stream);
   }
   const long tot = (long)Mrows * Cout;
@@ -1408,6 +1479,142 @@ extern "C" int re2e_conv_wgrad(const float* in, int NI, int H, int W, int C, con
   return RE2E_OK;
 }
 
+// ---- the layer-level choice, in the same plan: Winograd F(2x2,3x3), Winograd F(2x2,4x4) or the direct kernels above ---------------------------------
+// What ops.py asks per convolution (memoised on the arguments): the family; for Winograd 3x3 the images per launch (tensors of 2 GiB or more run as
+// slices of the image axis); for the pooled forward whether the one-launch fused pool applies; the workspace; and for the direct family the plan of
+// the entry point the layer then calls, from the ConvGeom ops.py derives.  dir: 0 forward, 1 data gradient, 2 weight gradient.
+//   Winograd 3x3   3x3 / stride 1 / pad 1 layers re2e_conv3x3_wino takes (wino3x3_fit) with one image under 2 GiB.  Weight gradient: additionally
+//                  Cin % 64 == 0 -- stricter than re2e_conv3x3_wino_wgrad itself (Cout % 32), see DESIGN.md section 4
+//   Winograd 4x4   4x4 / stride 1 / pad 1 with >= 64 channels both ways and >= 4096 pixels (the discriminator's conv4), no bias / activation / pool / mask
+namespace {
+struct ConvLayerIn {
+  int dir, N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, act;
+  bool bias, pool, mask, w_contig, x_contig, dz_contig, no_wino, no_wino_wgrad, aligned, filler; int cus;
+};
+enum ConvFamily { kFamWino3x3, kFamWino4x4, kFamDirect, kFamNone };
+struct ConvLayerPlan { ConvFamily family; int images; bool fused_pool, wino_note; size_t ws_bytes; ConvPlan direct; };
+
+// wino_note: a layer that looks like a Winograd layer is left to the direct kernels because ONE image has 2 GiB or more (ops.py says so once)
+bool wino3_layer(const ConvLayerIn& l, int C, int Cout, ConvLayerPlan& lp) {
+  if (l.no_wino || l.KH != 3 || l.KW != 3 || l.stride != 1 || l.pad != 1) return false;
+  const WinoFit f = wino3x3_fit(1, l.H, l.W, C, Cout);
+  if (f == kWinoChannels || f == kWinoGroups) return false;
+  if (f != kWinoFits) { lp.wino_note = true; return false; }
+  lp.images = wino3x3_images(l.N, l.H, l.W, C, Cout);
+  return true;
+}
+bool wino4_layer(const ConvLayerIn& l, int H, int W, int C, int Cout) {
+  return !l.no_wino && l.KH == 4 && l.KW == 4 && l.stride == 1 && l.pad == 1 && C % 16 == 0 && Cout % 16 == 0 && (C < Cout ? C : Cout) >= 64 &&
+         (long)l.N * H * W >= 4096 && H >= 3 && W >= 3;
+}
+
+ConvIn layer_conv_in(const ConvLayerIn& l, ConvKind kind, const ConvGeom& g, int Cout, int act, bool remap, bool mask, bool pool) {
+  ConvIn in;
+  memset(&in, 0, sizeof(in));
+  in.kind = kind;
+  in.NI = g.NI; in.H = g.H; in.W = g.W; in.C = g.C; in.PH = g.PH; in.PW = g.PW; in.KH = g.KH; in.KW = g.KW;
+  in.SY = g.SY; in.SX = g.SX; in.DY = g.DY; in.DX = g.DX; in.OY0 = g.OY0; in.OX0 = g.OX0;
+  in.Cout = Cout; in.act = act; in.remap = remap; in.mask = mask; in.pool = pool;
+  in.in16 = in.wg16 = in.out16 = in.bias16 = in.mask16 = in.pool16 = in.idx4 = l.aligned;
+  in.filler = l.filler; in.cus = l.cus;
+  return in;
+}
+
+ConvLayerPlan plan_conv_layer(const ConvLayerIn& l) {
+  ConvLayerPlan lp;
+  memset(&lp, 0, sizeof(lp));
+  lp.family = kFamDirect;
+  const int N = l.N, H = l.H, W = l.W, Cin = l.Cin, Cout = l.Cout, KH = l.KH, KW = l.KW, s = l.stride, pad = l.pad;
+  const int OH = l.OH ? l.OH : (H + 2 * pad - KH) / s + 1, OW = l.OW ? l.OW : (W + 2 * pad - KW) / s + 1;
+  if (l.dir == 0) {
+    if ((l.act == RE2E_ACT_NONE || l.act == RE2E_ACT_RELU) && wino3_layer(l, Cin, Cout, lp) && l.w_contig) {
+      lp.family = kFamWino3x3; lp.ws_bytes = re2e_conv3x3_wino_workspace_bytes(Cin, Cout);
+    } else if (l.act == RE2E_ACT_NONE && !l.bias && !l.pool && wino4_layer(l, H, W, Cin, Cout) && l.w_contig && wino4x4_fit(N, H, W, Cin, Cout, pad) == kWinoFits) {
+      lp.family = kFamWino4x4; lp.ws_bytes = re2e_conv4x4_wino_workspace_bytes(N, H, W, Cin, Cout, pad);
+    } else {
+      if (l.pool && KH == 3 && KW == 3 && s == 1 && pad == 1) {      // re2e_conv3x3_relu_pool: only the pooled activation and its index bytes are written
+        lp.direct = plan_conv(layer_conv_in(l, kConvIgemm, ConvGeom{nullptr, N, H, W, Cin, H, W, 3, 3, 1, 1, 1, 1, -1, -1}, Cout, RE2E_ACT_RELU, false, false, true));
+        lp.fused_pool = lp.direct.route == kHalo;
+      }
+      if (!lp.fused_pool)
+        lp.direct = plan_conv(layer_conv_in(l, kConvIgemm, ConvGeom{nullptr, N, H, W, Cin, OH, OW, KH, KW, s, s, 1, 1, -pad, -pad}, Cout, l.act, false, false, false));
+    }
+  } else if (l.dir == 1) {      // in = dz (N, OH, OW, Cout), out = dx (N, H, W, Cin)
+    if (s == 1 && wino3_layer(l, Cout, Cin, lp) && OH == H && OW == W && l.w_contig) {
+      lp.family = kFamWino3x3; lp.ws_bytes = re2e_conv3x3_wino_workspace_bytes(Cout, Cin);
+    } else if (!l.mask && wino4_layer(l, OH, OW, Cout, Cin) && OH == H - 1 && OW == W - 1 && l.w_contig && wino4x4_fit(N, OH, OW, Cout, Cin, 3 - pad) == kWinoFits) {
+      lp.family = kFamWino4x4; lp.ws_bytes = re2e_conv4x4_wino_workspace_bytes(N, OH, OW, Cout, Cin, 3 - pad);
+    } else if (s == 1) {
+      lp.direct = plan_conv(layer_conv_in(l, kConvIgemm, ConvGeom{nullptr, N, OH, OW, Cout, H, W, KH, KW, 1, 1, -1, -1, pad, pad}, Cin, RE2E_ACT_NONE, false, l.mask, false));
+    } else if (s == 2 && KH % 2 == 0 && KW % 2 == 0 && !l.mask) {
+      int o0[2];
+      const ConvGeom g = dgrad_s2_geom(nullptr, N, OH, OW, Cout, KH, KW, H, W, pad, o0);
+      if (Cin != 1) {      // re2e_conv_dgrad_s2: all four output parity classes in one launch
+        ConvIn in = layer_conv_in(l, kConvDgradS2, g, Cin, RE2E_ACT_NONE, true, false, false);
+        in.cls_o0[0] = o0[0]; in.cls_o0[1] = o0[1];
+        lp.direct = plan_conv(in);
+      } else {             // one re2e_conv_igemm per class: the plan of class (0, 0)
+        ConvGeom g0 = g;
+        g0.OY0 = g0.OX0 = o0[0];
+        lp.direct = plan_conv(layer_conv_in(l, kConvIgemm, g0, Cin, RE2E_ACT_NONE, true, false, false));
+      }
+    } else {
+      lp.family = kFamNone;      // ops.conv_dgrad: stride 1, or stride 2 with even kernels
+    }
+  } else {
+    if (!l.no_wino_wgrad && wino3_layer(l, Cin, Cout, lp) && Cin % 64 == 0 && l.x_contig && l.dz_contig &&
+        wino3x3_wgrad_fit(lp.images, H, W, Cin, Cout) == kWinoFits) {
+      lp.family = kFamWino3x3; lp.ws_bytes = re2e_conv3x3_wino_wgrad_workspace_bytes(lp.images, H, W, Cin, Cout);
+    } else if (wino4_layer(l, H, W, Cin, Cout) && l.x_contig && l.dz_contig && wino4x4_wgrad_fit(N, H, W, Cin, Cout, pad) == kWinoFits) {
+      lp.family = kFamWino4x4; lp.ws_bytes = re2e_conv4x4_wino_wgrad_workspace_bytes(N, H, W, Cin, Cout, pad);
+    } else {
+      ConvIn in = layer_conv_in(l, kConvWgrad, ConvGeom{nullptr, N, H, W, Cin, OH, OW, KH, KW, s, s, 1, 1, -pad, -pad}, Cout, RE2E_ACT_NONE, false, false, false);
+      lp.direct = plan_conv(in);
+      lp.ws_bytes = lp.direct.ws_bytes;
+    }
+  }
+  return lp;
+}
+
+int print_conv_plan(char* out, size_t nb, const ConvPlan& p) {
+  const NtPlan& q = p.nt;
+  const TileRow& t = kTiles[p.tile];
+  switch (p.route) {
+    case kCin1Fwd: return snprintf(out, nb, "route=cin1_fwd taps=%dx%d grid=%d mask_pass=0 note=%d", p.kh, p.kw, p.grid, (int)p.note_2gib);
+    case kCout1Rows: return snprintf(out, nb, "route=cout1_rows grid=%d lds=%zu mask_pass=0 note=%d", p.grid, p.lds, (int)p.note_2gib);
+    case kCout1: return snprintf(out, nb, "route=cout1 L=%d kh=%d kw=%d ch=%d grid=%d lds=%zu mask_pass=0 note=%d", p.L, p.kh, p.kw, p.ch, p.grid, p.lds, (int)p.note_2gib);
+    case kHalo: return snprintf(out, nb, "route=halo patch=%dx%d dir=%d relu=%d items=%d grid=%d lds=%zu mask_pass=0 note=0", p.th, p.tw, p.dir, (int)p.relu, p.nitems, p.grid, p.lds);
+    case kConvPipeline: return snprintf(out, nb, "route=pipeline variant=%d tile=%dx%dx%d n_dp=%d mask_pass=0 note=%d", q.variant, q.bm, q.bn, q.bk, q.n_dp, (int)p.note_2gib);
+    case kConvEngine: return snprintf(out, nb, "route=engine tile=%dx%dx%d vec=%d mask_pass=%d note=%d", t.bm, t.bn, t.bk, (int)p.vec, (int)p.mask_pass, (int)p.note_2gib);
+    case kWgradCin1: return snprintf(out, nb, "route=wgrad_cin1 slabs=%d wide_reduce=%d need=%zu", p.splits, (int)p.wide_reduce, p.need_bytes);
+    case kWgradCout1: return snprintf(out, nb, "route=wgrad_cout1 slabs=%d wide_reduce=%d need=%zu", p.splits, (int)p.wide_reduce, p.need_bytes);
+    case kWgradEngine: return snprintf(out, nb, "route=wgrad_engine tile=%dx%dx%d vec=%d splits=%d wide_reduce=%d need=%zu", t.bm, t.bn, t.bk, (int)p.vec, p.splits, (int)p.wide_reduce, p.need_bytes);
+    default: return snprintf(out, nb, "route=none note=%d", (int)p.note_2gib);
+  }
+}
+}  // namespace
+
+extern "C" int re2e_conv_plan(int dir, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int OH, int OW, int act, int flags,
+                              int cus, char* out, size_t out_bytes) {
+  RE2E_CHECK_ARG(dir >= 0 && dir <= 2 && N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0 && OH >= 0 && OW >= 0, "bad geometry");
+  RE2E_CHECK_ARG(act >= 0 && act <= RE2E_ACT_SIGMOID && cus >= 0 && out && out_bytes > 0, "bad argument");
+  if (cus == 0) cus = re2e_cu_count();
+  const ConvLayerIn l = {dir, N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, act, (flags & RE2E_CONV_BIAS) != 0, (flags & RE2E_CONV_POOL) != 0,
+                         (flags & RE2E_CONV_MASK) != 0, !(flags & RE2E_CONV_W_STRIDED), !(flags & RE2E_CONV_X_STRIDED), !(flags & RE2E_CONV_DZ_STRIDED),
+                         (flags & RE2E_CONV_NO_WINOGRAD) != 0, (flags & RE2E_CONV_NO_WINO_WGRAD) != 0, !(flags & RE2E_CONV_UNALIGNED),
+                         (flags & RE2E_CONV_FILLER) != 0, cus};
+  const ConvLayerPlan lp = plan_conv_layer(l);
+  if (lp.family == kFamNone) { re2e_set_error("re2e_conv_plan: the data gradient supports stride 1, or stride 2 with even kernels and no ReLU mask"); return RE2E_EUNSUPPORTED; }
+  int n;
+  if (lp.family == kFamWino3x3) n = snprintf(out, out_bytes, "family=wino3x3 images=%d ws=%zu", lp.images, lp.ws_bytes);
+  else if (lp.family == kFamWino4x4) n = snprintf(out, out_bytes, "family=wino4x4 ws=%zu", lp.ws_bytes);
+  else {
+    n = snprintf(out, out_bytes, "family=direct wino_note=%d fused_pool=%d ws=%zu ", (int)lp.wino_note, (int)lp.fused_pool, lp.ws_bytes);
+    if (n > 0 && (size_t)n < out_bytes) n += print_conv_plan(out + n, out_bytes - n, lp.direct);
+  }
+  RE2E_CHECK_ARG(n > 0 && (size_t)n < out_bytes, "out_bytes too small");
+  return RE2E_OK;
+}
 extern "C" int re2e_conv_weight_gather(const float* W, float* dst, int Cout, int Cin, int KH, int KW, int transpose,
                                        int TA, int TB, int kh0, int kw0, int kstep, hipStream_t stream) {
   RE2E_CHECK_ARG(W && dst, "null operand");

@@ -319,6 +319,7 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 constexpr int COUT1_CHUNK = 128;   // pixels per (chunk, tap) workgroup of the Cout == 1 weight gradient
+constexpr int ROWS_TH = 16;        // output rows per workgroup of the row-tile Cout == 1 kernel
 
 inline int cin1_span(const ConvGeom& g) { return (g.PW - 1) * g.SX + (g.KW - 1) * g.DX + 1; }
 
@@ -377,44 +378,62 @@ __global__ __launch_bounds__(256) void conv_cin1_fwd_kernel(ConvGeom g, const fl
 
 }  // namespace
 
-bool thin_conv_forward(const ConvGeom& g, const float* wg, int Cout, const OutMap& o, const float* bias, int act, float beta,
-                       hipStream_t st) {
-  const int M = g.NI * g.PH * g.PW;
-  const int K = g.KH * g.KW * g.C;
-  if (g.C == 1 && Cout % 4 == 0 && Cout <= 256 && pow2(Cout / 4) && !o.remap && o.ldc == Cout && beta == 0.f && aligned16(o.out) &&
-      ((g.KH == 3 && g.KW == 3) || (g.KH == 4 && g.KW == 4))) {
+// The thin kernels' part of plan_conv: which of the three forward families takes the call, with its instantiation and grid.  false: none does.
+bool thin_fwd_plan(const ConvIn& in, bool no_rows, ConvPlan& p) {
+  const int M = in.NI * in.PH * in.PW, K = in.KH * in.KW * in.C, Cout = in.Cout;
+  if (in.C == 1 && Cout % 4 == 0 && Cout <= 256 && pow2(Cout / 4) && !in.remap && in.beta == 0.f && in.out16 &&
+      ((in.KH == 3 && in.KW == 3) || (in.KH == 4 && in.KW == 4))) {
     const int npl = 256 / (Cout / 4);
-    const int grid = (int)min((long)cdiv(M, npl * 8), 8192L);     // >= 8 pixels per thread
-    if (g.KH == 3) hipLaunchKernelGGL((conv_cin1_fwd_kernel<3, 3>), dim3(grid), dim3(256), 0, st, g, wg, Cout, (long)M, o.out, bias, act);
-    else hipLaunchKernelGGL((conv_cin1_fwd_kernel<4, 4>), dim3(grid), dim3(256), 0, st, g, wg, Cout, (long)M, o.out, bias, act);
+    p.route = kCin1Fwd; p.kh = in.KH; p.kw = in.KW;
+    p.grid = (int)min((long)cdiv(M, npl * 8), 8192L);     // >= 8 pixels per thread
     return true;
   }
-  if (!(Cout == 1 && g.C % 4 == 0 && K <= 16384 && aligned16(g.in) && aligned16(wg))) return false;
+  if (!(Cout == 1 && in.C % 4 == 0 && K <= 16384 && in.in16 && in.wg16)) return false;
   // 64 channels, 3x3, stride 1, taps within one pixel of the output position, dense single-channel output: row-tile kernel
-  static const bool no_rows = exp_env("RE2E_NO_COUT1_ROWS") != nullptr;
-  if (!no_rows && g.C == 64 && g.KH == 3 && g.KW == 3 && g.SY == 1 && g.SX == 1 && g.PH == g.H && g.PW == g.W && !o.remap && o.ldc == 1 &&
-      (g.DY == 1 || g.DY == -1) && (g.DX == 1 || g.DX == -1) && g.OY0 == -g.DY && g.OX0 == -g.DX && g.W >= 16 && g.W <= 256 &&
-      (long)g.H * g.W * 256 < 0x7fffffffL) {
-    constexpr int TH = 16;
-    const size_t lds = (size_t)(TH + 2) * (g.W + 2) * 9 * sizeof(float);
-    auto kern = conv_cout1_rows3x3_kernel<TH>;
-    static LdsLimit lim;
-    lim.ensure(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(g.NI * cdiv(g.H, TH))), dim3(256), lds, st, g, wg, o, bias, act, beta);
+  if (!no_rows && in.C == 64 && in.KH == 3 && in.KW == 3 && in.SY == 1 && in.SX == 1 && in.PH == in.H && in.PW == in.W && !in.remap &&
+      (in.DY == 1 || in.DY == -1) && (in.DX == 1 || in.DX == -1) && in.OY0 == -in.DY && in.OX0 == -in.DX && in.W >= 16 && in.W <= 256 &&
+      (long)in.H * in.W * 256 < 0x7fffffffL) {
+    p.route = kCout1Rows;
+    p.lds = (size_t)(ROWS_TH + 2) * (in.W + 2) * 9 * sizeof(float);
+    p.grid = in.NI * cdiv(in.H, ROWS_TH);
     return true;
   }
-  const int c4n = g.C / 4;
+  const int c4n = in.C / 4;
   int L = 1;
   while (L < 64 && c4n % (L * 2) == 0) L *= 2;
   const int npass = cdiv(M, 256 / L);
-  const int grid = (int)min((long)cdiv(npass, 8), 4096L);      // >= 8 consecutive passes per workgroup
-  const int taps = g.KH * 16 + g.KW;
-#define RE2E_ARGS g, wg, K, M, o, bias, act, beta, grid, st
+  const int taps = in.KH * 16 + in.KW;
+  p.route = kCout1; p.L = L; p.kh = p.kw = p.ch = 0; p.lds = (size_t)K * 4;
+  p.grid = (int)min((long)cdiv(npass, 8), 4096L);      // >= 8 consecutive passes per workgroup
   // the shapes of the training step get compile-time tap / chunk counts; anything else the run-time loops
-  if (L == 16 && c4n == 16 && taps == 3 * 16 + 3) launch_cout1<16, 3, 3, 1>(RE2E_ARGS);        // VGG conv1_1 data gradient
-  else if (L == 16 && c4n == 16 && taps == 2 * 16 + 2) launch_cout1<16, 2, 2, 1>(RE2E_ARGS);   // D conv1 data gradient (parity class)
-  else if (L == 64 && c4n == 128 && taps == 4 * 16 + 4) launch_cout1<64, 4, 4, 2>(RE2E_ARGS);  // D conv5 forward
-  else switch (L) {
+  if (L == 16 && c4n == 16 && taps == 3 * 16 + 3) { p.kh = p.kw = 3; p.ch = 1; }             // VGG conv1_1 data gradient
+  else if (L == 16 && c4n == 16 && taps == 2 * 16 + 2) { p.kh = p.kw = 2; p.ch = 1; }        // D conv1 data gradient (parity class)
+  else if (L == 64 && c4n == 128 && taps == 4 * 16 + 4) { p.kh = p.kw = 4; p.ch = 2; }       // D conv5 forward
+  return true;
+}
+
+// Enqueue the thin forward kernel the plan names.
+void thin_conv_forward(const ConvPlan& p, const ConvGeom& g, const float* wg, int Cout, const OutMap& o, const float* bias, int act, float beta,
+                       hipStream_t st) {
+  const int M = g.NI * g.PH * g.PW;
+  const int K = g.KH * g.KW * g.C;
+  if (p.route == kCin1Fwd) {
+    if (p.kh == 3) hipLaunchKernelGGL((conv_cin1_fwd_kernel<3, 3>), dim3(p.grid), dim3(256), 0, st, g, wg, Cout, (long)M, o.out, bias, act);
+    else hipLaunchKernelGGL((conv_cin1_fwd_kernel<4, 4>), dim3(p.grid), dim3(256), 0, st, g, wg, Cout, (long)M, o.out, bias, act);
+    return;
+  }
+  if (p.route == kCout1Rows) {
+    auto kern = conv_cout1_rows3x3_kernel<ROWS_TH>;
+    static LdsLimit lim;
+    lim.ensure(reinterpret_cast<const void*>(kern), p.lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256), p.lds, st, g, wg, o, bias, act, beta);
+    return;
+  }
+#define RE2E_ARGS g, wg, K, M, o, bias, act, beta, p.grid, st
+  if (p.kh == 3) launch_cout1<16, 3, 3, 1>(RE2E_ARGS);
+  else if (p.kh == 2) launch_cout1<16, 2, 2, 1>(RE2E_ARGS);
+  else if (p.kh == 4) launch_cout1<64, 4, 4, 2>(RE2E_ARGS);
+  else switch (p.L) {
     case 1: launch_cout1<1, 0, 0, 0>(RE2E_ARGS); break;
     case 2: launch_cout1<2, 0, 0, 0>(RE2E_ARGS); break;
     case 4: launch_cout1<4, 0, 0, 0>(RE2E_ARGS); break;
@@ -424,7 +443,6 @@ bool thin_conv_forward(const ConvGeom& g, const float* wg, int Cout, const OutMa
     default: launch_cout1<64, 0, 0, 0>(RE2E_ARGS); break;
   }
 #undef RE2E_ARGS
-  return true;
 }
 
 // rows = NI*PH output rows (Cin == 1 path), P = pixels

@@ -231,6 +231,13 @@ W44Plan w44_plan(int NI, int H, int W, int C, int Cout, int pad) {
 }
 }  // namespace
 
+// What re2e_conv4x4_wino takes: C % 16 == 0, Cout % 4 == 0, transformed operands under 4 GiB
+WinoFit wino4x4_fit(int NI, int H, int W, int C, int Cout, int pad) {
+  if (C % 16 || Cout % 4) return kWinoChannels;
+  const W44Plan p = w44_plan(NI, H, W, C, Cout, pad);
+  return p.P * 25 * C * 4 >= 0xFFFFFFF0L || (long)Cout * 25 * C * 4 >= 0xFFFFFFF0L || p.P >= 0x7fffffffL ? kWinoBytes : kWinoFits;
+}
+
 extern "C" size_t re2e_conv4x4_wino_workspace_bytes(int NI, int H, int W, int C, int Cout, int pad) {
   if (NI <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || pad < 0 || H + 2 * pad < 4 || W + 2 * pad < 4) return 0;
   return w44_plan(NI, H, W, C, Cout, pad).total;
@@ -240,12 +247,13 @@ extern "C" int re2e_conv4x4_wino(const float* in, int NI, int H, int W, int C, c
                                  void* workspace, size_t workspace_bytes, hipStream_t stream) {
   RE2E_CHECK_ARG(in && w && out && workspace, "null operand");
   RE2E_CHECK_ARG(NI > 0 && H > 0 && W > 0 && C > 0 && Cout > 0 && pad >= 0 && H + 2 * pad >= 4 && W + 2 * pad >= 4, "bad geometry");
-  if (C % 16 || Cout % 4) { re2e_set_error("re2e_conv4x4_wino: C must be a multiple of 16 and Cout of 4 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
+  const WinoFit fit = wino4x4_fit(NI, H, W, C, Cout, pad);
+  if (fit == kWinoChannels) { re2e_set_error("re2e_conv4x4_wino: C must be a multiple of 16 and Cout of 4 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
   const W44Plan p = w44_plan(NI, H, W, C, Cout, pad);
   RE2E_CHECK_ARG(workspace_bytes >= p.total, "workspace too small (re2e_conv4x4_wino_workspace_bytes)");
   RE2E_CHECK_ARG((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "in / out / workspace must be 16-byte aligned");
-  if (p.P * 25 * C * 4 >= 0xFFFFFFF0L || (long)Cout * 25 * C * 4 >= 0xFFFFFFF0L || p.P >= 0x7fffffffL) {
+  if (fit != kWinoFits) {
     re2e_set_error("re2e_conv4x4_wino: transformed operand larger than 4 GiB");
     return RE2E_EUNSUPPORTED;
   }
@@ -290,6 +298,12 @@ W44WgradPlan w44_wgrad_plan(int NI, int H, int W, int C, int Cout, int pad) {
 }
 }  // namespace
 
+// What re2e_conv4x4_wino_wgrad takes: C % 4 == 0, Cout % 4 == 0, transformed operands under 4 GiB
+WinoFit wino4x4_wgrad_fit(int NI, int H, int W, int C, int Cout, int pad) {
+  if (C % 4 || Cout % 4) return kWinoChannels;
+  return 25 * w44_wgrad_plan(NI, H, W, C, Cout, pad).Ppad * (long)(C > Cout ? C : Cout) * 4 >= 0xFFFFFFF0L ? kWinoBytes : kWinoFits;
+}
+
 extern "C" size_t re2e_conv4x4_wino_wgrad_workspace_bytes(int NI, int H, int W, int C, int Cout, int pad) {
   if (NI <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || pad < 0 || H + 2 * pad < 4 || W + 2 * pad < 4) return 0;
   return w44_wgrad_plan(NI, H, W, C, Cout, pad).total;
@@ -300,12 +314,13 @@ extern "C" int re2e_conv4x4_wino_wgrad(const float* in, int NI, int H, int W, in
   RE2E_CHECK_ARG(in && dout && gw && workspace, "null operand");
   RE2E_CHECK_ARG(NI > 0 && H > 0 && W > 0 && C > 0 && Cout > 0 && pad >= 0 && H + 2 * pad >= 4 && W + 2 * pad >= 4, "bad geometry");
   RE2E_CHECK_ARG(beta == 0.f || beta == 1.f, "beta must be 0 or 1");
-  if (C % 4 || Cout % 4) { re2e_set_error("re2e_conv4x4_wino_wgrad: C and Cout must be multiples of 4 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
+  const WinoFit fit = wino4x4_wgrad_fit(NI, H, W, C, Cout, pad);
+  if (fit == kWinoChannels) { re2e_set_error("re2e_conv4x4_wino_wgrad: C and Cout must be multiples of 4 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
   const W44WgradPlan p = w44_wgrad_plan(NI, H, W, C, Cout, pad);
   RE2E_CHECK_ARG(workspace_bytes >= p.total, "workspace too small (re2e_conv4x4_wino_wgrad_workspace_bytes)");
   RE2E_CHECK_ARG((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "in / dout / workspace must be 16-byte aligned");
-  if (25 * p.Ppad * (long)(C > Cout ? C : Cout) * 4 >= 0xFFFFFFF0L) { re2e_set_error("re2e_conv4x4_wino_wgrad: transformed operand larger than 4 GiB"); return RE2E_EUNSUPPORTED; }
+  if (fit != kWinoFits) { re2e_set_error("re2e_conv4x4_wino_wgrad: transformed operand larger than 4 GiB"); return RE2E_EUNSUPPORTED; }
   float* V = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.v_off);
   float* dM = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.m_off);
   float* S = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.s_off);

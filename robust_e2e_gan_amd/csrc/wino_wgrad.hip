@@ -169,10 +169,6 @@ __global__ __launch_bounds__(256, 2) void wino_wgrad_kernel(WwArgs p) {
       }
 }
 
-#ifdef RE2E_EXPERIMENTS
-#include "experiments/wino_wgrad_dma.hip"    // the rejected LDS-DMA / packed-transform form (RE2E_WW_DMA=1): experiments build only
-#endif
-
 // red[e] = sum over the patch ranges of slabs[split][e], e < 16 * C * Cout: 16 slab lanes per element, combined through LDS in a fixed
 // order (deterministic).  A thread per (c, o) walking 768 slabs on its own made the finishing pass as long as the products for the
 // 64-channel layers (4096 threads, one dependent round trip per slab).
@@ -243,16 +239,6 @@ WwPlan ww_plan(int NI, int H, int W, int C, int Cout) {
 template <int TXW>
 void launch_ww(const WwArgs& a, hipStream_t st) {
   constexpr int PW = 2 * TXW, PH = 64 / TXW;
-#ifdef RE2E_EXPERIMENTS
-  static const bool dma = exp_env("RE2E_WW_DMA") && atoi(exp_env("RE2E_WW_DMA")) == 1;
-  if (dma) {
-    constexpr size_t lds2 = (size_t)2 * (192 * WW_CB + PW * PH * WW_OB) * sizeof(float);
-    static LdsLimit lim2;
-    lim2.ensure(reinterpret_cast<const void*>(&wino_wgrad_dma_kernel<TXW>), lds2);
-    hipLaunchKernelGGL((wino_wgrad_dma_kernel<TXW>), dim3((unsigned)(cdiv(a.nsplit, 8) * 8 * a.nblk)), dim3(256), lds2, st, a);
-    return;
-  }
-#endif
   constexpr size_t lds = (size_t)((PW + 2) * (PH + 2) * WW_CB + PW * PH * WW_OB) * sizeof(float);
   static LdsLimit lim;
   lim.ensure(reinterpret_cast<const void*>(&wino_wgrad_kernel<TXW>), lds);
@@ -265,14 +251,22 @@ extern "C" size_t re2e_conv3x3_wino_wgrad_workspace_bytes(int NI, int H, int W, 
   return ww_plan(NI, H, W, C, Cout).bytes;
 }
 
+// What re2e_conv3x3_wino_wgrad takes: C % 64 == 0, Cout % 32 == 0, tensors under 2 GiB
+WinoFit wino3x3_wgrad_fit(int NI, int H, int W, int C, int Cout) {
+  if (C % WW_CB || Cout % WW_OB) return kWinoChannels;
+  const long x_bytes = (long)NI * H * W * C * 4, dy_bytes = (long)NI * H * W * Cout * 4;
+  return x_bytes >= 0x7FFFFF00L || dy_bytes >= 0x7FFFFF00L ? kWinoBytes : kWinoFits;
+}
+
 static int ww_impl(const float* in, int NI, int H, int W, int C, const float* dout, int Cout, float* gw, float beta, const int* row_lim, void* workspace,
                    size_t workspace_bytes, hipStream_t stream) {
   RE2E_CHECK_ARG(in && dout && gw && workspace, "null operand");
   RE2E_CHECK_ARG(NI > 0 && H > 0 && W > 0 && C > 0 && Cout > 0, "bad geometry");
   RE2E_CHECK_ARG(beta == 0.f || beta == 1.f, "beta must be 0 or 1");
-  if (C % WW_CB || Cout % WW_OB) { re2e_set_error("re2e_conv3x3_wino_wgrad: C must be a multiple of 64 and Cout of 32 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
+  const WinoFit fit = wino3x3_wgrad_fit(NI, H, W, C, Cout);
+  if (fit == kWinoChannels) { re2e_set_error("re2e_conv3x3_wino_wgrad: C must be a multiple of 64 and Cout of 32 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
+  if (fit != kWinoFits) { re2e_set_error("re2e_conv3x3_wino_wgrad: tensors must be < 2 GiB"); return RE2E_EUNSUPPORTED; }
   const long x_bytes = (long)NI * H * W * C * 4, dy_bytes = (long)NI * H * W * Cout * 4;
-  if (x_bytes >= 0x7FFFFF00L || dy_bytes >= 0x7FFFFF00L) { re2e_set_error("re2e_conv3x3_wino_wgrad: tensors must be < 2 GiB"); return RE2E_EUNSUPPORTED; }
   RE2E_CHECK_ARG((reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(dout) & 15) == 0, "in / dout must be 16-byte aligned");
   const WwPlan q = ww_plan(NI, H, W, C, Cout);
   RE2E_CHECK_ARG(workspace_bytes >= q.bytes, "workspace too small (re2e_conv3x3_wino_wgrad_workspace_bytes)");

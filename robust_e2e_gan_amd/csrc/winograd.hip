@@ -539,10 +539,6 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
 }
 
 
-#ifdef RE2E_EXPERIMENTS
-#include "experiments/wino_pipe.hip"      // the rejected pipelined form (RE2E_WINO_PIPE=1): experiments build only
-#endif
-
 template <int TXW, bool LDSIN, bool C64 = false>
 void launch_wino(const WinoArgs& a, hipStream_t st) {
   size_t lds = (size_t)8 * 32 * LDR * sizeof(float);      // the exchange buffer (LDSIN: aliases the two staged halves, 2 x 24 KB)
@@ -559,23 +555,47 @@ extern "C" size_t re2e_conv3x3_wino_workspace_bytes(int C, int Cout) {
   return C > 0 && Cout > 0 ? (size_t)16 * C * Cout * sizeof(float) : 0;
 }
 
+// patch shape: 16 x 8 pixels (8 x 4 tiles) unless 8 x 16 wastes fewer padded pixels (W = 40: 8-wide patches fit exactly); returns the patches of an image
+static long wino_patches(int H, int W, bool* wide_out) {
+  const long pad_w = (long)cdiv(H, 8) * 8 * cdiv(W, 16) * 16, pad_n = (long)cdiv(H, 16) * 16 * cdiv(W, 8) * 8;
+  const bool wide = pad_w <= pad_n;
+  if (wide_out) *wide_out = wide;
+  return (long)cdiv(W, wide ? 16 : 8) * cdiv(H, wide ? 8 : 16);
+}
+
+// What re2e_conv3x3_wino takes of a launch over NI images: C % 8 == 0, Cout / 64 a power of two (192 or 320 output channels stay with the direct
+// kernels), tensors under 2 GiB (31-bit offsets) and a grid the launch can express.
+WinoFit wino3x3_fit(int NI, int H, int W, int C, int Cout) {
+  if (C % WCK || Cout % WNT) return kWinoChannels;
+  if ((Cout / WNT) & (Cout / WNT - 1)) return kWinoGroups;
+  const long in_bytes = (long)NI * H * W * C * 4, out_bytes = (long)NI * H * W * Cout * 4, u_bytes = (long)16 * C * Cout * 4;
+  if (in_bytes >= 0x7FFFFF00L || out_bytes >= 0x7FFFFF00L || u_bytes >= 0x7FFFFF00L) return kWinoBytes;
+  if ((long)wino_patches(H, W, nullptr) * (Cout / WNT) >= 0x7FFFFFF0L || NI > 65535) return kWinoItems;
+  return kWinoFits;
+}
+int wino3x3_images(int N, int H, int W, int C, int Cout) {
+  const long per = (long)H * W * (C > Cout ? C : Cout) * 4, n = 0x7FFFFF00L / per;
+  return (int)(n < 1 ? 1 : n < N ? n : N);
+}
+
 static int wino_impl(const float* in, int NI, int H, int W, int C, const float* w, int Cout, int dgrad, const float* bias, int relu,
                      const float* mask, float* out, float* pool_out, unsigned char* pool_idx, const int* row_lim, void* workspace,
                      size_t workspace_bytes, hipStream_t stream) {
   RE2E_CHECK_ARG(in && w && workspace && (out || pool_out), "null operand");
   RE2E_CHECK_ARG(NI > 0 && H > 0 && W > 0 && C > 0 && Cout > 0, "bad geometry");
   RE2E_CHECK_ARG(!pool_out || (pool_idx && relu && !mask && !dgrad), "pool_out needs pool_idx, relu = 1, no mask, forward direction");
-  if (C % WCK || Cout % WNT) { re2e_set_error("re2e_conv3x3_wino: C must be a multiple of 8 and Cout of 64 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED; }
-  const long in_bytes = (long)NI * H * W * C * 4, out_bytes = (long)NI * H * W * Cout * 4, u_bytes = (long)16 * C * Cout * 4;
-  if (in_bytes >= 0x7FFFFF00L || out_bytes >= 0x7FFFFF00L || u_bytes >= 0x7FFFFF00L) {
-    re2e_set_error("re2e_conv3x3_wino: tensors must be < 2 GiB");
-    return RE2E_EUNSUPPORTED;
+  switch (wino3x3_fit(NI, H, W, C, Cout)) {
+    case kWinoChannels: re2e_set_error("re2e_conv3x3_wino: C must be a multiple of 8 and Cout of 64 (got %d, %d)", C, Cout); return RE2E_EUNSUPPORTED;
+    case kWinoGroups: re2e_set_error("re2e_conv3x3_wino: Cout / 64 must be a power of two (got Cout = %d)", Cout); return RE2E_EUNSUPPORTED;
+    case kWinoBytes: re2e_set_error("re2e_conv3x3_wino: tensors must be < 2 GiB"); return RE2E_EUNSUPPORTED;
+    case kWinoItems: re2e_set_error("re2e_conv3x3_wino: too many work items"); return RE2E_EUNSUPPORTED;
+    case kWinoFits: break;
   }
+  const long in_bytes = (long)NI * H * W * C * 4, out_bytes = (long)NI * H * W * Cout * 4, u_bytes = (long)16 * C * Cout * 4;
   const uintptr_t al = reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(mask) |
                        reinterpret_cast<uintptr_t>(pool_out) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(workspace);
   if ((al & 15) || (reinterpret_cast<uintptr_t>(pool_idx) & 3)) { re2e_set_error("re2e_conv3x3_wino: operands must be 16-byte aligned"); return RE2E_EUNSUPPORTED; }
   RE2E_CHECK_ARG(workspace_bytes >= (size_t)u_bytes, "workspace too small");
-  if ((Cout / WNT) & (Cout / WNT - 1)) { re2e_set_error("re2e_conv3x3_wino: Cout / 64 must be a power of two (got Cout = %d)", Cout); return RE2E_EUNSUPPORTED; }
   float* uf = (float*)workspace;
   const long total = (long)16 * C * Cout;
   hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)(cdiv(total, 256) > 2048 ? 2048 : cdiv(total, 256))), dim3(256), 0, stream, w, Cout, C, dgrad, uf);
@@ -584,18 +604,15 @@ static int wino_impl(const float* in, int NI, int H, int W, int C, const float* 
   a.NI = NI; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.relu = relu;
   a.row_lim = row_lim;
   const int ngn = Cout / WNT;
-  if (ngn & (ngn - 1)) { re2e_set_error("re2e_conv3x3_wino: Cout / 64 must be a power of two (got Cout = %d)", Cout); return RE2E_EUNSUPPORTED; }
   a.ngn_shift = 0;
   while ((1 << a.ngn_shift) < ngn) ++a.ngn_shift;
   a.in_bytes = (unsigned)in_bytes; a.u_bytes = (unsigned)u_bytes; a.out_bytes = (unsigned)out_bytes;
   a.pool_bytes = (unsigned)((long)NI * ((H + 1) / 2) * ((W + 1) / 2) * Cout * 4);
-  // patch shape: 16 x 8 pixels (8 x 4 tiles) unless 8 x 16 wastes fewer padded pixels (W = 40: 8-wide patches fit exactly)
-  const long pad_w = (long)cdiv(H, 8) * 8 * cdiv(W, 16) * 16, pad_n = (long)cdiv(H, 16) * 16 * cdiv(W, 8) * 8;
-  const bool wide = pad_w <= pad_n;
+  bool wide;
+  (void)wino_patches(H, W, &wide);
   const int PWp = wide ? 16 : 8, PHp = wide ? 8 : 16;
   a.tiles_x = cdiv(W, PWp); a.tiles_y = cdiv(H, PHp);
   const long per_image = (long)a.tiles_x * a.tiles_y * ngn;
-  if (per_image >= 0x7FFFFFF0L || NI > 65535) { re2e_set_error("re2e_conv3x3_wino: too many work items"); return RE2E_EUNSUPPORTED; }
   a.per_image = (int)per_image;
   static const int dbg_env = exp_env("RE2E_WINO_DBG") ? atoi(exp_env("RE2E_WINO_DBG")) : 0;
   a.dbg = dbg_env;
@@ -604,9 +621,6 @@ static int wino_impl(const float* in, int NI, int H, int W, int C, const float* 
   static const bool log_calls = getenv("RE2E_IGEMM_LOG") != nullptr;   // tools/igemm_table.py joins this with a kernel trace
   if (log_calls)
     fprintf(stderr, "[igemm] A=Wino%s B=DenseK tile=128x64x8 vec=1 M=%ld N=%d K=%d splits=1\n", dgrad ? "D" : "F", (long)NI * H * W, Cout, 9 * C);
-#ifdef RE2E_EXPERIMENTS
-  if (wino_pipe_try(a, per_image, NI, C, wide, stream)) { RE2E_LAUNCH_CHECK(); return RE2E_OK; }
-#endif
   // the input patch through LDS (round 6) wherever the channel count allows it (whole pairs of 32-channel halves); RE2E_WINO_LDSIN=0 (experiments
   // build): the per-lane loads of rounds 3-5
   static const bool ldsin_env = !(exp_env("RE2E_WINO_LDSIN") && atoi(exp_env("RE2E_WINO_LDSIN")) == 0);

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 322      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 323      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -36,6 +36,7 @@ SIGNATURES = {
     're2e_gemm_nt_rows': (I, [I, I, I, P, L, P, L, P, L, P, P, I, F, P, I, I, P, Z, P]),
     're2e_gemm_tn_rows': (I, [I, I, I, P, L, P, L, P, L, F, P, I, I, P, Z, P]),
     're2e_fill_rows': (I, [P, L, I, P, I, F, P, I, P]),
+    're2e_conv_plan': (I, [I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P, Z]),
     're2e_conv_igemm': (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, P, I, I, I, I, I, I, P, I, F, P]),
     're2e_conv3x3_relu_pool': (I, [P, I, I, I, I, P, I, P, P, P, P]),
     're2e_conv_igemm_masked': (I, [P, I, I, I, I, P, I, I, I, I, I, I, I, I, I, I, I, P, I, I, I, I, I, I, P, P]),
@@ -354,3 +355,21 @@ def cu_masked_stream(enabled_cus, total_cus=256, device=None, first=0):
         return torch.cuda.ExternalStream(st.value, device=device)
     except Exception:
         return None
+
+
+# re2e_conv_plan's flags (include/re2e.h RE2E_CONV_*)
+CONV_BIAS, CONV_POOL, CONV_MASK, CONV_W_STRIDED, CONV_X_STRIDED, CONV_DZ_STRIDED, CONV_NO_WINOGRAD, CONV_NO_WINO_WGRAD, CONV_UNALIGNED, CONV_FILLER = \
+    (1 << i for i in range(10))
+CONV_FWD, CONV_DGRAD, CONV_WGRAD = range(3)
+
+
+def conv_plan(direction, N, H, W, Cin, Cout, KH, KW, stride, pad, OH=0, OW=0, act=ACT_NONE, flags=0, cus=0):
+    """re2e_conv_plan as a dict of strings: the family (wino3x3 / wino4x4 / direct) a layer's forward, data gradient or weight gradient runs
+    with, its images per launch, fused pool and workspace bytes, and for the direct family the route, instantiation and grid of the entry point
+    it calls.  flags: CONV_* (cus > 0: on a chip of that many CUs, no device needed; 0: the current device)."""
+    buf = ctypes.create_string_buffer(320)
+    lib = load()
+    rc = lib.re2e_conv_plan(direction, N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, act, flags, cus, buf, len(buf))
+    if rc != 0:
+        raise Re2eError('re2e_conv_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    return dict(kv.split('=') for kv in buf.value.decode().split())

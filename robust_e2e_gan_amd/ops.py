@@ -669,11 +669,11 @@ def _conv_out(h, k, s, p):
     return (h + 2 * p - k) // s + 1
 
 
-WINOGRAD = lib.exp_env('RE2E_NO_WINOGRAD') is None
-WINO_WGRAD = lib.exp_env('RE2E_NO_WINO_WGRAD') is None      # A/B switch (RE2E_EXPERIMENTS=1): the direct halo-patch / engine kernels instead
-
-
+# A/B switches (RE2E_EXPERIMENTS=1), passed into every plan query: the direct halo-patch / pipeline / engine kernels instead of the Winograd ones
+_PLAN_SWITCHES = (lib.CONV_NO_WINOGRAD if lib.exp_env('RE2E_NO_WINOGRAD') is not None else 0) | \
+    (lib.CONV_NO_WINO_WGRAD if lib.exp_env('RE2E_NO_WINO_WGRAD') is not None else 0)
 _WINO_DECLINED = set()
+_CONV_PLANS = {}
 
 
 def _wino_note(kind, N, H, Wd, C, Cout):
@@ -687,22 +687,27 @@ def _wino_note(kind, N, H, Wd, C, Cout):
               file=sys.stderr, flush=True)
 
 
-def _wino_ok(N, H, Wd, C, Cout, k, stride, pad):
-    """3x3 / stride-1 / pad-1 layers the fused Winograd F(2x2,3x3) kernel covers (re2e_conv3x3_wino: C % 8 == 0, Cout / 64 a power of
-    two -- 192 or 320 output channels stay with the direct engine).  The kernels address with 31-bit offsets; a tensor of 2 GiB or more
-    (a per-GPU batch of 64: 128 images x 800 x 80 x 64 channels) is cut along the image axis by the callers (``_wino_images``)."""
-    g = Cout // 64
-    if not (WINOGRAD and k == (3, 3) and stride == 1 and pad == 1 and C % 8 == 0 and Cout % 64 == 0 and g & (g - 1) == 0):
-        return False
-    if H * Wd * max(C, Cout) * 4 >= 2 ** 31 - 256:            # one image alone is too large
-        _wino_note('3x3', N, H, Wd, C, Cout)
-        return False
-    return True
+def conv_plan(direction, N, H, Wd, Cin, Cout, KH, KW, stride, pad, OH=0, OW=0, act=lib.ACT_NONE, flags=0, switches=_PLAN_SWITCHES):
+    """What the library's convolution plan (re2e_conv_plan: csrc/igemm.hip plan_conv_layer) names for one pass of a layer: ``(family, images
+    per Winograd 3x3 launch, fused pool)`` with family 'wino3x3' / 'wino4x4' / 'direct'.  The plan is a pure function of these integers, so
+    it is asked once per distinct call; a step's ~60 convolution passes cost a dict hit each."""
+    flags |= switches
+    key = (direction, N, H, Wd, Cin, Cout, KH, KW, stride, pad, OH, OW, act, flags)
+    got = _CONV_PLANS.get(key)
+    if got is None:
+        d = lib.conv_plan(direction, N, H, Wd, Cin, Cout, KH, KW, stride, pad, OH, OW, act, flags)
+        if d.get('wino_note') == '1':
+            C, K = (Cout, Cin) if direction == lib.CONV_DGRAD else (Cin, Cout)
+            _wino_note('3x3', N, H, Wd, C, K)
+        got = _CONV_PLANS[key] = (d['family'], int(d.get('images', 0)), d.get('fused_pool') == '1')
+    return got
 
 
 def _wino_images(N, H, Wd, C, Cout):
-    """Images per launch of the fused Winograd kernels: all of them, or as many as keep both tensors under 2 GiB."""
-    return max(1, min(N, (2 ** 31 - 256) // (H * Wd * max(C, Cout) * 4)))
+    """Images per launch of the fused Winograd 3x3 kernels, as the plan names them: all of them, or as many as keep both tensors under 2 GiB
+    (a shape the plan does not give to them: one launch, which re2e_conv3x3_wino answers with its reason)."""
+    family, images, _ = conv_plan(lib.CONV_FWD, N, H, Wd, C, Cout, 3, 3, 1, 1, switches=0)
+    return images if family == 'wino3x3' else N
 
 
 class RowLims(object):
@@ -776,13 +781,6 @@ def conv3x3_wino(x, W, Cout, dgrad=False, bias=None, relu=False, mask=None, pool
     return y
 
 
-def _wino44_ok(N, H, Wd, C, Cout, k, stride, pad):
-    """4x4 / stride-1 / pad-1 layers with enough channels and pixels for Winograd F(2x2,4x4) to pay (re2e_conv4x4_wino: the
-    discriminator's conv4 and its data gradient -- both directions need C % 16 == 0 and Cout % 16 == 0)."""
-    return (WINOGRAD and k == (4, 4) and stride == 1 and pad == 1 and C % 16 == 0 and Cout % 16 == 0 and min(C, Cout) >= 64
-            and N * H * Wd >= 4096 and H >= 3 and Wd >= 3)
-
-
 def conv4x4_wino(x, W, Cout, pad, dgrad=False):
     """re2e_conv4x4_wino on NHWC ``x`` with the layer's weight ``W`` in PyTorch layout: forward (pad = the layer's padding) or data
     gradient (``x`` is dy, ``Cout`` the layer's input channels, pad = 3 - the layer's padding)."""
@@ -809,7 +807,9 @@ class Conv2dFn(torch.autograd.Function):
         ctx.pool = bool(pool)                          # the result is maxpool2(relu(conv)), 2x2 / stride 2 / ceil mode
         ctx.W, ctx.b, ctx.cfg = W, b, (stride, pad, act)
         ctx.lims = None
-        if act in (lib.ACT_NONE, lib.ACT_RELU) and _wino_ok(N, H, Wd, Cin, Cout, (KH, KW), stride, pad) and W.is_contiguous():
+        family, _, fused = conv_plan(lib.CONV_FWD, N, H, Wd, Cin, Cout, KH, KW, stride, pad, 0, 0, act, (lib.CONV_BIAS if b is not None else 0) |
+                                     (lib.CONV_POOL if pool else 0) | (0 if W.is_contiguous() else lib.CONV_W_STRIDED))
+        if family == 'wino3x3':
             # 3x3 / stride-1 VGG layers: fused Winograd F(2x2,3x3), 2.25x fewer matrix instructions than the direct kernels below
             # ``lims`` (RowLims, ragged image batches): rows beyond an utterance's reach are not computed; zeros where a later kernel reads all rows
             ctx.lims = lims
@@ -825,7 +825,7 @@ class Conv2dFn(torch.autograd.Function):
                 fill_image_rows(y, lims.out, 1, lims.out_tail)
             ctx.save_for_backward(x, y if (act != lib.ACT_NONE and not ctx.act_bwd_done) else None)
             return y
-        if act == lib.ACT_NONE and b is None and not pool and _wino44_ok(N, H, Wd, Cin, Cout, (KH, KW), stride, pad) and W.is_contiguous():
+        if family == 'wino4x4':
             y = conv4x4_wino(x.contiguous(), W, Cout, pad)            # the discriminator's conv4: F(2x2,4x4), 2.56x fewer matrix FLOPs
             ctx.save_for_backward(x, None)
             return y
@@ -836,8 +836,6 @@ class Conv2dFn(torch.autograd.Function):
             # kernel does not cover run the convolution and the pool (with the ReLU mask in its index byte) one after the other
             yp = empty((N, (OH + 1) // 2, (OW + 1) // 2, Cout), x)
             idx = torch.empty(yp.shape, dtype=torch.uint8, device=x.device)
-            fused = KH == 3 and KW == 3 and stride == 1 and pad == 1 and Cin % 16 == 0 and Cout % 64 == 0 and x.numel() * 4 < 2 ** 31 - 256 \
-                and N * OH * OW * Cout * 4 < 2 ** 31 - 256
             if fused:
                 call('re2e_conv3x3_relu_pool', x.data_ptr(), N, H, Wd, Cin, wg.data_ptr(), Cout, ptr(b), yp.data_ptr(), idx.data_ptr())
             else:
@@ -878,10 +876,11 @@ class Conv2dFn(torch.autograd.Function):
             if lims is not None and lims.inp is not None:
                 fill_image_rows(dx, lims.inp, 1, lims.inp_tail)         # the gradient is zero there: written, not computed
         with param_grads(dz, x, lims):
-            if need_w and WINO_WGRAD and _wino_ok(N, H, Wd, Cin, Cout, (KH, KW), stride, pad) and Cin % 64 == 0 and x.is_contiguous() \
-                    and dz.is_contiguous():
-                # 3x3 / stride-1 VGG layers: the sum over pixels in the Winograd domain (re2e_conv3x3_wino_wgrad), 2.25x fewer matrix FLOPs
-                nb = _wino_images(N, H, Wd, Cin, Cout)                # tensors of 2 GiB or more: slices of the image axis, accumulated
+            family, nb, _ = conv_plan(lib.CONV_WGRAD, N, H, Wd, Cin, Cout, KH, KW, stride, pad, 0, 0, lib.ACT_NONE, (
+                0 if x.is_contiguous() else lib.CONV_X_STRIDED) | (0 if dz.is_contiguous() else lib.CONV_DZ_STRIDED)) if need_w else (None, 0, False)
+            if family == 'wino3x3':
+                # 3x3 / stride-1 VGG layers: the sum over pixels in the Winograd domain (re2e_conv3x3_wino_wgrad), 2.25x fewer matrix FLOPs;
+                # nb images per launch (tensors of 2 GiB or more: slices of the image axis, accumulated)
                 wsb = query('re2e_conv3x3_wino_wgrad_workspace_bytes', nb, H, Wd, Cin, Cout)
                 ws = workspace(wsb, x.device, 'winow')
                 _note_row_limits(lims.out if lims is not None else None, H, Wd)
@@ -894,7 +893,7 @@ class Conv2dFn(torch.autograd.Function):
                         else:
                             call('re2e_conv3x3_wino_wgrad', x[i:i + n].data_ptr(), n, H, Wd, Cin, dz[i:i + n].data_ptr(), Cout, gw.data_ptr(),
                                  beta if i == 0 else 1.0, ws.data_ptr(), wsb)
-            elif need_w and _wino44_ok(N, H, Wd, Cin, Cout, (KH, KW), stride, pad) and x.is_contiguous() and dz.is_contiguous():
+            elif family == 'wino4x4':
                 wsb = query('re2e_conv4x4_wino_wgrad_workspace_bytes', N, H, Wd, Cin, Cout, pad)
                 ws = workspace(wsb, x.device, 'wino44w')
                 with accumulate(W) as (gw, beta):
@@ -917,9 +916,15 @@ def conv_dgrad(dz, W, xshape, stride, pad, relu_out=None, row_lim=None):
     N, H, Wd, Cin = xshape
     Cout, _, KH, KW = W.shape
     OH, OW = dz.shape[1], dz.shape[2]
-    if stride == 1 and _wino_ok(N, H, Wd, Cout, Cin, (KH, KW), stride, pad) and (OH, OW) == (H, Wd) and W.is_contiguous():
+    if relu_out is not None and stride != 1:
+        raise lib.Re2eError('conv_dgrad: relu_out needs stride 1')
+    if stride != 1 and (stride != 2 or KH % 2 or KW % 2):
+        raise lib.Re2eError('conv data gradient supports stride 1, or stride 2 with even kernels')
+    family = conv_plan(lib.CONV_DGRAD, N, H, Wd, Cin, Cout, KH, KW, stride, pad, OH, OW, lib.ACT_NONE, (lib.CONV_MASK if relu_out is not None else 0) |
+                       (0 if W.is_contiguous() else lib.CONV_W_STRIDED))[0]
+    if family == 'wino3x3':
         return conv3x3_wino(_f32(dz), W, Cin, dgrad=True, mask=relu_out, row_lim=row_lim)
-    if relu_out is None and _wino44_ok(N, OH, OW, Cout, Cin, (KH, KW), stride, pad) and (OH, OW) == (H - 1, Wd - 1) and W.is_contiguous():
+    if family == 'wino4x4':
         return conv4x4_wino(_f32(dz).contiguous(), W, Cin, 3 - pad, dgrad=True)
     if stride == 1:
         wt = empty((Cin, KH, KW, Cout), dz)
@@ -932,10 +937,6 @@ def conv_dgrad(dz, W, xshape, stride, pad, relu_out=None, row_lim=None):
             call('re2e_conv_igemm', dz.data_ptr(), N, OH, OW, Cout, wt.data_ptr(), Cin, KH, KW, H, Wd, 1, 1, -1, -1, pad, pad,
                  dx.data_ptr(), H, Wd, 1, 1, 0, 0, None, lib.ACT_NONE, 0.0)
         return dx
-    if relu_out is not None:
-        raise lib.Re2eError('conv_dgrad: relu_out needs stride 1')
-    if stride != 2 or KH % 2 or KW % 2:
-        raise lib.Re2eError('conv data gradient supports stride 1, or stride 2 with even kernels')
     if Cin != 1:    # all four output parity classes in one launch
         dx = empty((N, H, Wd, Cin), dz)
         wt = empty((4, Cin, KH // 2, KW // 2, Cout), dz)

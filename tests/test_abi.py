@@ -235,6 +235,86 @@ def test_gemm_plan_table():
                                 assert int(got['ws']) == so.re2e_gemm_workspace_bytes(form[0], form[1], M, N, K), where
 
 
+# what the convolution entry points instantiate.  A copy of the BUILT masks of csrc/igemm.hip's conv_engine / re2e_conv_wgrad, of thinconv.hip's
+# launch_cout1 / conv_cin1_fwd_kernel instantiations and of conv3x3.hip's HALO_GO: it has to follow them when an instantiation is added or dropped.
+_CONV_ENGINE_BUILT = {
+    ('engine', 1): {'128x128x16', '256x128x16', '256x64x16', '256x32x32'}, ('engine', 0): {'128x128x16', '256x64x16', '256x32x32'},
+    ('wgrad_engine', 1): {'128x128x16', '256x64x16', '256x32x32', '192x64x16'}, ('wgrad_engine', 0): {'128x128x16', '256x64x16', '256x32x32'},
+}
+_COUT1_BUILT = {(16, 3, 3, 1), (16, 2, 2, 1), (64, 4, 4, 2)} | {(L, 0, 0, 0) for L in (1, 2, 4, 8, 16, 32, 64)}
+
+
+def _check_conv_plan_is_built(got, where):
+    route = got.get('route')
+    if got['family'] != 'direct':
+        assert got['family'] in ('wino3x3', 'wino4x4') and int(got['ws']) > 0, where
+    elif route in ('engine', 'wgrad_engine'):
+        assert got['tile'] in _CONV_ENGINE_BUILT[route, int(got['vec'])], where
+    elif route == 'pipeline':
+        assert _PIPELINE_BUILT.get(int(got['variant'])) == got['tile'] and int(got['n_dp']) >= 1, where
+    elif route == 'cout1':
+        assert tuple(int(got[k]) for k in ('L', 'kh', 'kw', 'ch')) in _COUT1_BUILT and int(got['grid']) >= 1, where
+    elif route == 'cin1_fwd':
+        assert got['taps'] in ('3x3', '4x4') and int(got['grid']) >= 1, where
+    elif route == 'halo':
+        assert got['patch'] in ('16x16', '32x8') and got['dir'] in ('1', '-1') and got['relu'] in ('0', '1') and got['grid'] == got['items'], where
+    else:
+        assert route in ('cout1_rows', 'wgrad_cin1', 'wgrad_cout1'), where
+
+
+def test_conv_plan_table():
+    """re2e_conv_plan (csrc/igemm.hip plan_conv_layer / plan_conv, which ops.py and the convolution entry points choose their kernels with) on a
+    256-CU chip against tests/golden/conv_plan_table.json: rows of [direction, N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW, activation,
+    RE2E_CONV_* flags] -> the plan.  The table was dumped from the commit BEFORE plan_conv existed, by a reader over its choosers -- ops.py's
+    predicates as Conv2dFn / conv_dgrad combined them, and its entry points with every launch site recording instead of enqueueing: a row
+    that changes is a change of behaviour.  It holds every convolution pass of one bench.py step, every CONVS row of test_kernels_gpu.py and
+    the boundaries between the routes, each also with unaligned operands, behind RE2E_NO_WINOGRAD and on a filler stream where that changes
+    the plan.  Then over a sweep of sizes, directions, stream roles and two chip sizes every plan names something that is built, the weight
+    gradient's workspace covers its need and does not depend on the stream role, and no Winograd launch gets a tensor of 2 GiB or more.  No
+    device is touched where cus > 0."""
+    import json
+    from robust_e2e_gan_amd import lib
+    if not os.path.exists(lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    rows = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'conv_plan_table.json')))
+    assert len(rows) == 466
+    for args, want in rows:
+        got = lib.conv_plan(*args[:13], flags=args[13], cus=256)
+        assert got == want, (args, got, want)
+        _check_conv_plan_is_built(got, args)
+    so = lib.load()
+    points = 0
+    for cus in (64, 256, 0):          # 0: the chip re2e_conv_wgrad_workspace_bytes itself plans for (256 CUs without a device)
+        for k, stride in ((3, 1), (4, 1), (4, 2)):
+            for N, H, W in ((1, 5, 3), (2, 33, 8), (3, 21, 24), (32, 100, 40), (128, 800, 80)):
+                if stride == 2 and (H % 2 or W % 2):
+                    H, W = H + H % 2, W + W % 2
+                for Cin, Cout in ((1, 64), (64, 1), (512, 1), (6, 10), (12, 20), (16, 64), (16, 192), (64, 64), (64, 128), (256, 512)):
+                    for direction in (lib.CONV_FWD, lib.CONV_DGRAD, lib.CONV_WGRAD):
+                        for extra in (0, lib.CONV_NO_WINOGRAD | lib.CONV_NO_WINO_WGRAD, lib.CONV_UNALIGNED, lib.CONV_MASK if direction == lib.CONV_DGRAD and
+                                      stride == 1 else lib.CONV_POOL if direction == lib.CONV_FWD and k == 3 else 0):
+                            act = _RELU if extra == lib.CONV_POOL else _NONE
+                            plans = [lib.conv_plan(direction, N, H, W, Cin, Cout, k, k, stride, 1, act=act, flags=extra | f, cus=cus)
+                                     for f in (0, lib.CONV_FILLER)]
+                            for got, other in (plans, plans[::-1]):
+                                where = (cus, direction, N, H, W, Cin, Cout, k, stride, extra, got)
+                                points += 1
+                                _check_conv_plan_is_built(got, where)
+                                assert got['family'] == other['family'] and got['ws'] == other['ws'], where
+                                if got['family'] == 'wino3x3':
+                                    assert 1 <= int(got['images']) <= N and int(got['images']) * H * W * max(Cin, Cout) * 4 < 2 ** 31, where
+                                if got.get('route', '').startswith('wgrad') and not extra & lib.CONV_UNALIGNED:
+                                    # (the workspace is sized before there are pointers, for 16-byte aligned operands: an unaligned Cin == 1 /
+                                    # Cout == 1 call goes to the engine, whose slice count may exceed the thin kernels' -- re2e_conv_wgrad then
+                                    # answers "workspace too small", as before the plan existed; DESIGN.md section 4)
+                                    assert int(got['ws']) >= int(got['need']), where
+                                    if cus == 0:
+                                        OH, OW = (H + 2 - k) // stride + 1, (W + 2 - k) // stride + 1
+                                        assert int(got['ws']) == so.re2e_conv_wgrad_workspace_bytes(N, OH, OW, Cin, Cout, k, k), where
+    assert points == 3 * 3 * 5 * 10 * 3 * 4 * 2
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from robust_e2e_gan_amd import lib
     monkeypatch.setattr(lib, '_lib', None)

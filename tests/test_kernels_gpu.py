@@ -382,44 +382,66 @@ def test_mean_loss(kind):
         close('lsgan', l1.view(1), ((a - 1.0) ** 2).mean().view(1), tol=1e-5)
 
 
-CONVS = [  # N, H, W, Cin, Cout, k, stride, pad, act, bias
-    (3, 37, 20, 1, 8, 3, 1, 1, 'relu', True),
-    (2, 16, 12, 64, 64, 3, 1, 1, 'relu', True),
-    (2, 9, 10, 64, 128, 3, 1, 1, None, True),
-    (3, 37, 80, 1, 8, 4, 2, 1, 'lrelu', True),
-    (3, 18, 40, 8, 16, 4, 2, 1, None, False),
-    (2, 18, 40, 64, 128, 4, 2, 1, None, False),
-    (3, 9, 9, 16, 32, 4, 1, 1, None, False),
-    (3, 8, 8, 32, 1, 4, 1, 1, None, True),
-    (2, 7, 5, 6, 10, 3, 1, 1, 'relu', True),
+def _conv_route(plan):
+    """The route of a lib.conv_plan answer in one word: the Winograd family, or the direct kernel with what tells its instantiations apart."""
+    if plan['family'] != 'direct':
+        return plan['family']
+    r = plan['route']
+    if r == 'halo':
+        r += ':' + plan['patch']
+    elif r in ('engine', 'wgrad_engine'):
+        r += ':' + plan['tile']
+    elif r == 'cout1':
+        r += ':L' + plan['L'] + ('k' + plan['kh'] if plan['kh'] != '0' else '')
+    return r
+
+
+W3, W4 = ('wino3x3',) * 3, ('wino4x4',) * 3
+CONVS = [  # N, H, W, Cin, Cout, k, stride, pad, act, bias, (route of the forward, the data gradient, the weight gradient: lib.conv_plan)
+    (3, 37, 20, 1, 8, 3, 1, 1, 'relu', True, ('cin1_fwd', 'cout1:L2', 'wgrad_cin1')),
+    (2, 16, 12, 64, 64, 3, 1, 1, 'relu', True, W3),
+    (2, 9, 10, 64, 128, 3, 1, 1, None, True, W3),
+    (3, 37, 80, 1, 8, 4, 2, 1, 'lrelu', True, ('cin1_fwd', 'cout1:L2', 'wgrad_cin1')),
+    (3, 18, 40, 8, 16, 4, 2, 1, None, False, ('engine:256x32x32', 'pipeline', 'wgrad_engine:256x32x32')),
+    (2, 18, 40, 64, 128, 4, 2, 1, None, False, ('pipeline', 'pipeline', 'wgrad_engine:128x128x16')),
+    (3, 9, 9, 16, 32, 4, 1, 1, None, False, ('engine:256x32x32', 'engine:256x32x32', 'wgrad_engine:256x32x32')),
+    (3, 8, 8, 32, 1, 4, 1, 1, None, True, ('cout1:L8', 'cin1_fwd', 'wgrad_cout1')),
+    (2, 7, 5, 6, 10, 3, 1, 1, 'relu', True, ('engine:256x32x32', 'engine:256x32x32', 'wgrad_engine:256x32x32')),
     # thin-channel direct kernels (thinconv.hip): Cin == 1 / Cout == 1 at the VGG / discriminator widths,
     # plus widths the thin weight-gradient kernels do not cover (fall back to the implicit GEMM)
-    (2, 21, 16, 1, 64, 3, 1, 1, 'relu', True),
-    (2, 37, 20, 1, 64, 4, 2, 1, 'lrelu', True),
-    (2, 12, 9, 512, 1, 4, 1, 1, None, True),
-    (2, 11, 7, 64, 1, 3, 1, 1, None, False),
-    (2, 9, 8, 1, 12, 3, 1, 1, None, True),
-    (2, 9, 8, 12, 1, 3, 1, 1, 'lrelu', True),
+    (2, 21, 16, 1, 64, 3, 1, 1, 'relu', True, ('cin1_fwd', 'cout1_rows', 'wgrad_cin1')),
+    (2, 37, 20, 1, 64, 4, 2, 1, 'lrelu', True, ('cin1_fwd', 'cout1:L16k2', 'wgrad_cin1')),
+    (2, 12, 9, 512, 1, 4, 1, 1, None, True, ('cout1:L64k4', 'engine:128x128x16', 'wgrad_cout1')),
+    (2, 11, 7, 64, 1, 3, 1, 1, None, False, ('cout1:L16k3', 'cin1_fwd', 'wgrad_cout1')),
+    (2, 9, 8, 1, 12, 3, 1, 1, None, True, ('engine:256x32x32', 'cout1:L1', 'wgrad_engine:256x32x32')),
+    (2, 9, 8, 12, 1, 3, 1, 1, 'lrelu', True, ('cout1:L1', 'engine:256x32x32', 'wgrad_engine:256x32x32')),
     # the row-tile Cout == 1 kernel (16 lanes per pixel): full-width rows, a width that is not a multiple of 16, ragged last row tile
-    (2, 19, 80, 1, 64, 3, 1, 1, 'relu', True),
-    (1, 13, 23, 64, 1, 3, 1, 1, None, True),
-    # halo-patch 3x3 kernels (conv3x3.hip): C % 16 == 0 and Cout % 64 == 0; 16x16 patches (ragged in both directions) and
-    # the 32x8 patches chosen for narrow images; one / two 64-channel groups; 1, 4 and 8 channel chunks
-    (1, 35, 80, 64, 64, 3, 1, 1, 'relu', True),
-    (1, 100, 40, 128, 64, 3, 1, 1, None, False),
-    (2, 33, 8, 16, 64, 3, 1, 1, 'relu', True),
-    (1, 67, 40, 64, 128, 3, 1, 1, 'relu', True),
-    (3, 5, 3, 32, 128, 3, 1, 1, None, True),
+    (2, 19, 80, 1, 64, 3, 1, 1, 'relu', True, ('cin1_fwd', 'cout1_rows', 'wgrad_cin1')),
+    (1, 13, 23, 64, 1, 3, 1, 1, None, True, ('cout1_rows', 'cin1_fwd', 'wgrad_cout1')),
+    # 3x3 / stride-1 / pad-1 layers with C % 8 == 0 and Cout / 64 a power of two: since Winograd became the default these run on the fused
+    # F(2x2,3x3) kernels (winograd.hip, wino_wgrad.hip: 16x8 and 8x16 patches, ragged edges, one / two 64-channel groups, 2 - 16 channel
+    # chunks) in every direction whose channel counts allow it; the data gradient into 16 / 32 channels and the weight gradient from 16 / 32
+    # channels go to the pipeline / the engine.  The halo-patch kernels (conv3x3.hip) these rows were written for are reached through the
+    # entry points: test_conv_direct_routes_*, test_conv3x3_halo_equals_general_engine_and_accumulates, test_conv_relu_pool_one_launch.
+    (1, 35, 80, 64, 64, 3, 1, 1, 'relu', True, W3),
+    (1, 100, 40, 128, 64, 3, 1, 1, None, False, W3),
+    (2, 33, 8, 16, 64, 3, 1, 1, 'relu', True, ('wino3x3', 'pipeline', 'wgrad_engine:256x64x16')),
+    (1, 67, 40, 64, 128, 3, 1, 1, 'relu', True, W3),
+    (3, 5, 3, 32, 128, 3, 1, 1, None, True, ('wino3x3', 'engine:256x32x32', 'wgrad_engine:128x128x16')),
     # Winograd F(2x2,4x4) (wino44.hip): 4x4 / stride 1 / pad 1, >= 64 channels both ways; odd output sizes (ragged tiles)
-    (2, 50, 48, 64, 128, 4, 1, 1, None, False),
-    (1, 67, 65, 128, 64, 4, 1, 1, None, False),
+    (2, 50, 48, 64, 128, 4, 1, 1, None, False, W4),
+    (1, 67, 65, 128, 64, 4, 1, 1, None, False, W4),
 ]
 
 
 @pytest.mark.parametrize('cfg', CONVS)
 def test_conv2d(cfg):
     ops, lib = _ops()
-    N, H, W, Cin, Cout, k, s, p, act, has_b = cfg
+    N, H, W, Cin, Cout, k, s, p, act, has_b, routes = cfg
+    # which kernels this row runs, as the plan ops.conv2d asks reports it: a routing change must not silently empty the row of its purpose
+    got = tuple(_conv_route(lib.conv_plan(d, N, H, W, Cin, Cout, k, k, s, p, act=ops.ACT[act] if d == lib.CONV_FWD else lib.ACT_NONE,
+                                          flags=lib.CONV_BIAS if has_b and d == lib.CONV_FWD else 0)) for d in (lib.CONV_FWD, lib.CONV_DGRAD, lib.CONV_WGRAD))
+    assert got == routes
     x, Wt = rnd(N, Cin, H, W), rnd(Cout, Cin, k, k, seed=1, scale=1.0 / math.sqrt(Cin * k * k))
     b = rnd(Cout, seed=2) if has_b else None
     xr, Wr = x.clone().requires_grad_(True), Wt.clone().requires_grad_(True)
@@ -440,12 +462,66 @@ def test_conv2d(cfg):
         close('db', bg.grad, br.grad, tol=2e-4)
 
 
+@pytest.mark.parametrize('N,H,W,C,K,route,items', [(2, 33, 8, 16, 128, 'halo:32x8', '8'), (1, 35, 19, 32, 64, 'halo:16x16', '6')])
+def test_conv_direct_routes_forward_halo(N, H, W, C, K, route, items):
+    """re2e_conv_igemm with bias and ReLU on the halo-patch kernel: 32x8 patches on a narrow image (ragged: 33 rows) with two 64-channel groups, and
+    16x16 patches ragged in both directions -- routes no CONVS row reaches since the layers they serve go to Winograd; against F.conv2d."""
+    ops, lib = _ops()
+    plan = lib.conv_plan(lib.CONV_FWD, N, H, W, C, K, 3, 3, 1, 1, act=lib.ACT_RELU, flags=lib.CONV_BIAS | lib.CONV_NO_WINOGRAD)
+    assert (_conv_route(plan), plan['dir'], plan['relu'], plan['items'], plan['mask_pass']) == (route, '1', '1', items, '0')
+    x, Wt, b = rnd(N, H, W, C), rnd(K, C, 3, 3, seed=1, scale=0.1), rnd(K, seed=2)
+    ref = F.relu(F.conv2d(x.permute(0, 3, 1, 2), Wt, b, padding=1)).permute(0, 2, 3, 1)
+    xg, Wg, bg = x.to(DEV), Wt.to(DEV), b.to(DEV)
+    wg = torch.empty(K, 3, 3, C, device=DEV)
+    lib.call('re2e_conv_weight_gather', Wg.data_ptr(), wg.data_ptr(), K, C, 3, 3, 0, 3, 3, 0, 0, 1)
+    y = torch.full((N, H, W, K), float('nan'), device=DEV)
+    lib.call('re2e_conv_igemm', xg.data_ptr(), N, H, W, C, wg.data_ptr(), K, 3, 3, H, W, 1, 1, 1, 1, -1, -1, y.data_ptr(), H, W, 1, 1, 0, 0,
+             bg.data_ptr(), lib.ACT_RELU, 0.0)
+    close('y', y, ref, tol=2e-4)
+
+
+@pytest.mark.parametrize('N,H,W,Cin,Cout,route,mask_pass', [(1, 21, 24, 64, 64, 'halo:32x8', '0'), (1, 35, 19, 64, 64, 'halo:16x16', '0'),
+                                                                  (1, 9, 7, 12, 20, 'engine:256x32x32', '1')])
+def test_conv_direct_routes_masked_data_gradient(N, H, W, Cin, Cout, route, mask_pass):
+    """re2e_conv_igemm_masked (data gradient taken through the ReLU in front of the layer) on the two routes it has: the halo-patch kernel
+    in its data-gradient form with the mask in its epilogue (32x8 patches, which the 21 x 24 image gets, and 16x16 patches ragged in both
+    directions), and the engine followed by the
+    separate mask pass -- routes no CONVS row reaches (those layers' data gradients go to Winograd or carry no mask); against autograd."""
+    ops, lib = _ops()
+    plan = lib.conv_plan(lib.CONV_DGRAD, N, H, W, Cin, Cout, 3, 3, 1, 1, flags=lib.CONV_MASK | lib.CONV_NO_WINOGRAD)
+    assert (_conv_route(plan), plan['mask_pass']) == (route, mask_pass) and plan.get('dir', '-1') == '-1'
+    pre, Wt, dz = rnd(N, Cin, H, W), rnd(Cout, Cin, 3, 3, seed=1, scale=0.1), rnd(N, Cout, H, W, seed=2)
+    pr = pre.clone().requires_grad_(True)
+    (F.conv2d(F.relu(pr), Wt, padding=1) * dz).sum().backward()
+    relu_out = F.relu(pre).permute(0, 2, 3, 1).contiguous().to(DEV)
+    dzg, Wg = dz.permute(0, 2, 3, 1).contiguous().to(DEV), Wt.to(DEV)
+    wt = torch.empty(Cin, 3, 3, Cout, device=DEV)
+    lib.call('re2e_conv_weight_gather', Wg.data_ptr(), wt.data_ptr(), Cout, Cin, 3, 3, 1, 3, 3, 0, 0, 1)
+    dx = torch.full((N, H, W, Cin), float('nan'), device=DEV)
+    lib.call('re2e_conv_igemm_masked', dzg.data_ptr(), N, H, W, Cout, wt.data_ptr(), Cin, 3, 3, H, W, 1, 1, -1, -1, 1, 1, dx.data_ptr(), H, W, 1, 1, 0, 0,
+             relu_out.data_ptr())
+    close('dx', dx.permute(0, 3, 1, 2), pr.grad, tol=2e-4)
+
+
+def test_conv3x3_relu_pool_declines_what_the_plan_does_not_fuse():
+    """re2e_conv3x3_relu_pool on a shape whose plan reports no fused pool (6 -> 10 channels): RE2E_EUNSUPPORTED, nothing enqueued."""
+    ops, lib = _ops()
+    N, H, W, C, K = 2, 9, 7, 6, 10
+    assert lib.conv_plan(lib.CONV_FWD, N, H, W, C, K, 3, 3, 1, 1, act=lib.ACT_RELU, flags=lib.CONV_BIAS | lib.CONV_POOL)['fused_pool'] == '0'
+    x, wg, b = torch.zeros(N, H, W, C, device=DEV), torch.zeros(K, 3, 3, C, device=DEV), torch.zeros(K, device=DEV)
+    yp = torch.zeros(N, (H + 1) // 2, (W + 1) // 2, K, device=DEV)
+    idx = torch.zeros(yp.shape, dtype=torch.uint8, device=DEV)
+    with pytest.raises(lib.Re2eError):
+        lib.call('re2e_conv3x3_relu_pool', x.data_ptr(), N, H, W, C, wg.data_ptr(), K, b.data_ptr(), yp.data_ptr(), idx.data_ptr())
+
+
 def test_conv3x3_halo_equals_general_engine_and_accumulates():
-    """The halo-patch kernel against the general implicit-GEMM engine on the same call (RE2E_NO_HALO is read once per
-    process, so the general engine is reached through a geometry the halo kernel declines: the same convolution with the
-    input channels padded to C+4 ... is not the same call; instead compare with F.conv2d) and the beta = 1 epilogue."""
+    """re2e_conv_igemm on a 3x3 / stride-1 / pad-1 geometry the halo-patch kernel takes (32x8 patches -- 24 columns pad less that way --, a ragged
+    last patch row, two channel chunks, one 64-channel group; the plan is asserted), against F.conv2d: the beta = 1 epilogue (bias, no activation, added to what
+    the output held) and the ReLU epilogue."""
     ops, lib = _ops()
     N, H, W, C, K = 2, 21, 24, 32, 64
+    assert _conv_route(lib.conv_plan(lib.CONV_FWD, N, H, W, C, K, 3, 3, 1, 1, flags=lib.CONV_BIAS | lib.CONV_NO_WINOGRAD)) == 'halo:32x8'
     x, Wt, b = rnd(N, H, W, C), rnd(K, C, 3, 3, seed=1, scale=0.1), rnd(K, seed=2)
     ref = F.conv2d(x.permute(0, 3, 1, 2), Wt, b, padding=1).permute(0, 2, 3, 1)
     xg, Wg, bg = x.to(DEV), Wt.to(DEV), b.to(DEV)
@@ -1465,7 +1541,7 @@ def test_conv3x3_wino_above_2gib_runs_in_image_slices():
     (each under the limit: one launch) -- bitwise for the per-image results, 1e-5 for the weight gradient (a different split over patches)."""
     ops, lib = _ops()
     N, H, W, C, K = 132, 800, 80, 64, 64
-    assert N * H * W * C * 4 >= 2 ** 31 and ops._wino_ok(N, H, W, C, K, (3, 3), 1, 1) and ops._wino_images(N, H, W, C, K) < N
+    assert N * H * W * C * 4 >= 2 ** 31 and ops.conv_plan(lib.CONV_FWD, N, H, W, C, K, 3, 3, 1, 1)[0] == 'wino3x3' and ops._wino_images(N, H, W, C, K) < N
     g = torch.Generator(device=DEV).manual_seed(3)
     x = torch.randn(N, H, W, C, device=DEV, generator=g)
     Wt = torch.randn(K, C, 3, 3, device=DEV, generator=g) / math.sqrt(9 * C)

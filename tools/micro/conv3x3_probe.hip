@@ -23,9 +23,9 @@ int main(int argc, char** argv) {
   HaloArgs a;
   a.in = in; a.wg = wg; a.out = out; a.bias = bias; a.mask = nullptr; a.pool_out = nullptr; a.pool_idx = nullptr; a.NI = N; a.H = H; a.W = W; a.C = C; a.Cout = K; a.act = RE2E_ACT_RELU; a.beta = 0.f;
   a.ngn = K / NT; a.in_bytes = (unsigned)(nin * 4); a.wg_bytes = (unsigned)(nw * 4); a.out_bytes = (unsigned)(nout * 4); a.tiles_x = cdiv(W, 16); a.tiles_y = cdiv(H, 16);
-  a.nitems = N * a.tiles_x * a.tiles_y * a.ngn; a.ipw = 0;
-  const int slots = getenv("RE2E_HALO_SLOTS") ? atoi(getenv("RE2E_HALO_SLOTS")) : 512;
-  const long nwg = a.nitems < slots ? a.nitems : slots;
+  a.nitems = N * a.tiles_x * a.tiles_y * a.ngn; a.ipw = 1;      // one item per workgroup, as the library launches it
+  const int slots = 512;                                         // two workgroups resident per CU
+  const long nwg = a.nitems;
   hipMalloc(&a.stamps, nwg * 18 * 8);
   hipMemset(a.stamps, 0, nwg * 18 * 8);
   hipEvent_t e0, e1;
@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
   hipEventRecord(e1);
   hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, e0, e1); ms /= 10;
-  printf("N=%d: %.3f ms per launch, %.1f TFLOP/s (%ld persistent workgroups, %d items)\n", N, ms, 2.0 * 9 * C * K * N * H * W / ms / 1e9, nwg, a.nitems);
+  printf("N=%d: %.3f ms per launch, %.1f TFLOP/s (%ld workgroups, %d items)\n", N, ms, 2.0 * 9 * C * K * N * H * W / ms / 1e9, nwg, a.nitems);
   std::vector<unsigned long long> st(nwg * 18);
   hipMemcpy(st.data(), a.stamps, nwg * 18 * 8, hipMemcpyDeviceToHost);
   const char* names[] = {"stage chunk 0 (fetched under the previous item)", "matrix block", "barrier", "stage next chunk", "epilogue"};

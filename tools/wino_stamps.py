@@ -11,7 +11,6 @@ import torch
 dev = 'cuda:0'
 st = torch.zeros(4096 * 4 * 8, dtype=torch.int64, device=dev)
 os.environ['RE2E_WINO_STAMPS'] = '%x' % st.data_ptr()
-os.environ.setdefault('RE2E_WINO_IPW', '1')
 from robust_e2e_gan_amd import ops   # noqa: E402
 
 N, H, W, C, K = 64, 800, 80, 64, 64
@@ -27,7 +26,7 @@ print('workgroups stamped:', s.shape[0])
 d = s[:, :, 1:7] - s[:, :, 0:6]
 names = ['prologue', 'main loop', 'R calc + LDS write', 'barrier 1', 'stage 2 + stores', 'barrier 2']
 tot = (s[:, :, 6] - s[:, :, 0])
-print('memtime ticks per phase (mean over the stamped workgroups x 4 waves; items per workgroup = %s)' % os.environ['RE2E_WINO_IPW'])
+print('memtime ticks per phase (mean over the stamped workgroups x 4 waves)')
 for i, nme in enumerate(names):
     print('  %-20s %9.1f  (%4.1f %%)' % (nme, d[:, :, i].mean(), 100 * d[:, :, i].mean() / tot.mean()))
 print('  %-20s %9.1f' % ('total', tot.mean()))
