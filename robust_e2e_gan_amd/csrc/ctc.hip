@@ -7,6 +7,8 @@
 //   ctc_alpha_beta : one workgroup per utterance, alpha/beta recursions with the previous column
 //                    staged in LDS; log domain
 //   ctc_grad       : one wavefront per row, dlogits = scale * (softmax - occupancy)
+// An utterance whose frames cannot carry its labels (hlen < L + repeats) has nll = +inf, the loss is +inf and its gradient rows
+// are NaN (what F.ctc_loss gives); the other utterances of the batch are unaffected.
 // HBM traffic: logits are read twice (lse, grad) and dlogits written once.
 #include "common.h"
 
@@ -127,7 +129,12 @@ __global__ void ctc_alpha_beta(int T, int B, const int* __restrict__ hlens, cons
     float* cur = p0;
     if (s < Sb) cur[s] = a;
     __syncthreads();
-    if (s == 0) nll[b] = -(Sb > 1 ? lse2(cur[Sb - 1], cur[Sb - 2]) : cur[Sb - 1]);
+    if (s == 0) {
+      // no alignment (fewer frames than labels + repeats): the log-likelihood is still at the NEG floor -> nll = +inf, as F.ctc_loss
+      // answers; ctc_grad turns it into NaN gradient rows, which the step gate's finite check refuses
+      const float ll = Sb > 1 ? lse2(cur[Sb - 1], cur[Sb - 2]) : cur[Sb - 1];
+      nll[b] = ll <= 0.5f * NEG ? INFINITY : -ll;
+    }
   } else if (s == 0) nll[b] = 0.f;
   __syncthreads();
   // ---- beta (includes lp at its own frame) ----
@@ -176,8 +183,9 @@ __global__ __launch_bounds__(256) void ctc_grad(const float* __restrict__ logits
   int Sb = active ? 2 * llen[b] + 1 : 0;
   const int* lab = labels + (live ? loff[b] : 0);
   float blank = 0.f;
-  if (active) {
-    float nl = nll[b];
+  const float nl = active ? nll[b] : 0.f;
+  const bool feasible = nl < INFINITY;     // an utterance without any alignment (nll = +inf): its active rows are written as NaN
+  if (active && feasible) {
     for (int s = lane; s < Sb; s += 64) {
       long i = (long)row * S + s;
       float a = alpha[i], be = beta[i];
@@ -198,12 +206,12 @@ __global__ __launch_bounds__(256) void ctc_grad(const float* __restrict__ logits
       for (int v = lane; v < V; v += 64) {
         float y = expf(x[v] - l);
         if (v == 0) y -= blank;
-        dst[v] = scale * y;
+        dst[v] = feasible ? scale * y : __uint_as_float(0x7fc00000u);
       }
     }
   }
   __syncthreads();     // block-wide visibility of the row just written (and of occ[])
-  if (active) {
+  if (active && feasible) {
     for (int s = 1 + 2 * lane; s < Sb; s += 128) {     // odd states: one label each
       int l = lab[s >> 1];
       bool first = true;

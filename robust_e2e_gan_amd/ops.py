@@ -1777,10 +1777,15 @@ class DecoderLoopFn(torch.autograd.Function):
     ``sample_steps`` (optional tuple of L1 bools): step i feeds back the arg-max of step i-1's output layer instead
     of the reference label (scheduled sampling e2e_decoder.py:123-127, and the greedy pass of
     calculate_all_attentions :408-412); needs ``out_w`` / ``out_b`` in ``P``.  The fed-back token is an integer, so
-    no gradient flows through the arg-max -- only into the embedding row that was used."""
+    no gradient flows through the arg-max -- only into the embedding row that was used.
+
+    ``w_grad``: the attention weights (L1,B,T), the second output, are only displayed by the model and leave the loop as a
+    non-differentiable tensor.  With ``w_grad=True`` they are a differentiable output: an upstream gradient on them enters each
+    step's softmax backward beside the recurrence's own (re2e_attloc_bwd's ``dw_in``), on the launch-per-step backward -- the
+    persistent reverse loop has no input for it."""
 
     @staticmethod
-    def forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps=None):
+    def forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps=None, w_grad=False):
         _need_gpu(hmask)
         hmask, pre = _f32(hmask), _f32(pre)
         dev = hmask.device
@@ -1845,16 +1850,21 @@ class DecoderLoopFn(torch.autograd.Function):
         ctx.persist = bool(lwsb)
         ctx.dims = (B, T, E, A, Dd, D, C, Fh, L1)
         ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, conv, dpj)
-        ctx.mark_non_differentiable(w)
+        ctx.w_grad = bool(w_grad)
+        if w_grad:
+            ctx.set_materialize_grads(False)        # the gradient of an output nothing downstream used arrives as None, not as zeros
+        else:
+            ctx.mark_non_differentiable(w)
         return z[1:], w
 
     @staticmethod
-    def backward(ctx, dZ, _dw_unused):
+    def backward(ctx, dZ, dW):
         hmask, pre, emb, cx, z, c, w, gates, conv, dpj = ctx.saved_tensors
         Pm = ctx.Pm
         B, T, E, A, Dd, D, C, Fh, L1 = ctx.dims
         dev = hmask.device
-        dZ = _f32(dZ)
+        dZ = _f32(dZ) if dZ is not None else zeros((L1, B, D), hmask)
+        dW = _f32(dW) if (getattr(ctx, 'w_grad', False) and dW is not None) else None      # upstream gradient on the attention weights
         w_ih = Pm['w_ih']
         ldw = Dd + E
         w_ctx = w_ih.data_ptr() + 4 * Dd
@@ -1873,7 +1883,7 @@ class DecoderLoopFn(torch.autograd.Function):
         have_dw = False
         fused = DECODER_FUSED and B <= 32
         # the whole reverse loop as ONE persistent launch (csrc/decloop.hip) when the forward took that form too (no sampled tokens)
-        bwsb = query('re2e_dec_loop_bwd_workspace_bytes', L1, B, T, E, D, A, C, Fh) if (ctx.persist and DECODER_PERSIST and fused) else 0
+        bwsb = query('re2e_dec_loop_bwd_workspace_bytes', L1, B, T, E, D, A, C, Fh) if (ctx.persist and DECODER_PERSIST and fused and dW is None) else 0
         if bwsb:
             bws = workspace(bwsb, dev, 'decloop_bwd')
             # the grow-only workspace is read once more by re2e_dec_loop_dwconv on the weight-gradient stream (below): a second backward on this
@@ -1902,9 +1912,15 @@ class DecoderLoopFn(torch.autograd.Function):
                 dc_a, dc_b = dc_b, dc_a
                 gemm(gates[i], w_ctx, d_cx, B, E, 4 * D, ldb=ldw, dev=dev)                     # d ctx = dgates W_ih[:, Dd:]
                 gemm(gates[i], Pm['w_hh'], dz_carry, B, D, 4 * D)                                # d z_{i-1} (recurrent path)
+            dw_in = dw_a.data_ptr() if have_dw else None               # d w_i from step i + 1's location conv
+            if dW is not None:
+                if have_dw:
+                    call('re2e_axpby', 1.0, dW[i].data_ptr(), 1.0, dw_a.data_ptr(), B * T)
+                else:
+                    dw_in = dW[i].data_ptr()
             call('re2e_attloc_bwd', pre.data_ptr(), hmask.data_ptr(), w[i - 1].data_ptr() if i > 0 else None, w[i].data_ptr(),
                  ctx.hlens.data_ptr(), Pm['mlp_att'].data_ptr(), Pm['loc_conv'].data_ptr(), Pm['gvec_w'].data_ptr(), conv[i].data_ptr(),
-                 dpj[i].data_ptr(), cx[i].data_ptr(), d_cx.data_ptr(), E, dw_a.data_ptr() if have_dw else None, B, T, E, A, C, Fh,
+                 dpj[i].data_ptr(), cx[i].data_ptr(), d_cx.data_ptr(), E, dw_in, B, T, E, A, C, Fh,
                  de_all[i].data_ptr(), dw_b.data_ptr() if i > 0 else None, ddp[i].data_ptr(), partials.data_ptr(), aws.data_ptr(), awsb)
             dw_a, dw_b = dw_b, dw_a
             have_dw = True
@@ -1952,7 +1968,7 @@ class DecoderLoopFn(torch.autograd.Function):
                     with accumulate(Pm[k]) as (gt, beta):
                         call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
                     off += n
-        return d_enc, d_pre, None, None, None, None, None
+        return d_enc, d_pre, None, None, None, None, None, None
 
 
 decoder_loop = DecoderLoopFn.apply
