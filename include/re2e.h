@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 323
+#define RE2E_ABI_VERSION 324
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -481,6 +481,15 @@ int re2e_ctc_bwd(const float* logits, int T, int B, int V, const int* hlens_dev,
 int re2e_ctc_prefix_score(const float* lpz, int T, int V, const float* att_lsm, int nh, const float* r_prev, const int* last_label_dev,
                           const int* out_len_dev, const float* prev_score_dev, int ctc_beam, float att_weight, float ctc_weight, int blank,
                           int eos, int* cand_out, float* local_out, float* ctc_score_out, float* r_new, re2e_stream_t stream);
+/* re2e_ctc_prefix_score for the hypotheses of SEVERAL utterances in one launch (beam search over a batch): lpz (U,Tmax,V), zero-padded;
+ * tlen_dev (U) = frames T_u of each utterance; utt_dev (nh) = the utterance of each hypothesis.  r_prev (nh,Tmax,2) and r_new
+ * (nh,ctc_beam,Tmax,2) are pitched Tmax.  Every loop bound, the clamp of the start frame and the <eos> score (rsum[T_u - 1]) use
+ * T_u = tlen[utt[h]]: over t < T_u a row's outputs are bit for bit those of re2e_ctc_prefix_score on its utterance alone; state entries
+ * at t >= T_u are written as -1e10.  ctc_beam <= 64 and (V + 3 Tmax) floats of LDS (RE2E_EUNSUPPORTED beyond). */
+int re2e_ctc_prefix_score_batch(const float* lpz, int U, int Tmax, int V, const int* tlen_dev, const int* utt_dev, const float* att_lsm, int nh,
+                                const float* r_prev, const int* last_label_dev, const int* out_len_dev, const float* prev_score_dev, int ctc_beam,
+                                float att_weight, float ctc_weight, int blank, int eos, int* cand_out, float* local_out, float* ctc_score_out,
+                                float* r_new, re2e_stream_t stream);
 /* The same scores for a caller-given candidate list cand_dev (nh, ncand) -- ctc_weight == 1.0 scores all V labels in the order of their
  * attention scores (a device-side stable sort): one thread per candidate, outputs (nh, ncand) in the list's order, r_new (nh*ncand, T, 2). */
 int re2e_ctc_prefix_score_cands(const float* lpz, int T, int V, const float* att_lsm, int nh, const float* r_prev, const int* last_label_dev,
@@ -497,6 +506,15 @@ int re2e_attloc_fwd(const float* pre, const float* enc, const float* z, const fl
                     const float* w_decT, const float* w_att, const float* w_conv, const float* gvec, const float* gvec_b,
                     int B, int T, int eprojs, int dunits, int adim, int chans, int filts, float* w_out, float* c_out,
                     long ldc_out, float* conv_out, float* dp_out, float* e_scratch, re2e_stream_t stream);
+/* The same step for `nh` rows (the live hypotheses of a beam search over several utterances) that share U utterances: pre (U,T,adim) and
+ * enc (U,T,eprojs) are read through utt_dev (nh) = the utterance of each row, once per utterance held and not once per row.  hlens_dev (U)
+ * = the frames T_u of each utterance: a row HAS only those -- the softmax and the context run over t < T_u, att_prev reads as 0 beyond, w_out
+ * and conv_out at t >= T_u are written as 0 -- so a row gets bit for bit what re2e_attloc_fwd gives for T = T_u on its utterance alone.
+ * z, att_prev, w_out, c_out, conv_out, dp_out, e_scratch are per row, (nh, .) with frame pitch T.  Same kernels as re2e_attloc_fwd. */
+int re2e_attloc_fwd_rows(const float* pre, const float* enc, int U, const int* hlens_dev, const int* utt_dev, const float* z, const float* att_prev,
+                         const float* w_decT, const float* w_att, const float* w_conv, const float* gvec, const float* gvec_b, int nh, int T,
+                         int eprojs, int dunits, int adim, int chans, int filts, float* w_out, float* c_out, long ldc_out, float* conv_out,
+                         float* dp_out, float* e_scratch, re2e_stream_t stream);
 size_t re2e_attloc_partial_floats(int adim, int chans, int filts);
 size_t re2e_attloc_workspace_bytes(int B, int T, int adim, int chans);
 /* backward of one step: writes de_out (B,T) = d(energy) of this step (kept by the caller for re2e_attloc_dpre),
@@ -539,6 +557,18 @@ int re2e_lm_log_softmax_combine(const float* logits, int n, int V, const float* 
 /* local[k][j] += lm_weight * lm[k][cand_dev[k][j]], k < n, j < ncand (e2e_decoder.py:284-285 on re2e_ctc_prefix_score's outputs);
  * a candidate outside [0, V) gives NaN. */
 int re2e_lm_add_cands(float* local, const float* lm, const int* cand_dev, int n, int ncand, int V, float lm_weight, re2e_stream_t stream);
+
+/* ---- N3 beam pruning on the device (csrc/beamsearch.hip), several utterances per launch.  The nh rows of a position are grouped by
+ * utterance: utterance u owns rows seg_off_dev[u] .. seg_off_dev[u+1]-1 (U+1 offsets; max_seg_rows = the largest group, known to the host).
+ * hyp_score (nh); local (nh,ncand) = the scores of each row's continuations; cand_dev (nh,ncand) = their labels, or NULL when the label is the
+ * column (ncand = V).  Per utterance the min(beam, rows * ncand) best by score = hyp_score[row] + local[row][col] (one fp32 addition), ordered
+ * as recognize_beam's host loop orders them -- score descending, then row ascending, then local descending, then column ascending -- go to
+ * parent_out (row index among the nh), col_out, label_out, score_out, all (U,beam), and count_out (U); entries beyond the count are -1 / -inf.
+ * A NaN ranks as -inf (as in re2e_ctc_prefix_score's selection).  workspace: 2 * nh * min(beam, ncand) 4-byte words.  beam <= 64 and
+ * max_seg_rows <= beam (RE2E_EUNSUPPORTED beyond). */
+int re2e_beam_prune(const int* seg_off_dev, int U, int max_seg_rows, const float* hyp_score, const float* local, const int* cand_dev, int nh,
+                    int ncand, int beam, int* parent_out, int* col_out, int* label_out, float* score_out, int* count_out, void* workspace,
+                    size_t workspace_bytes, re2e_stream_t stream);
 
 /* ---- K11 optimizer (joint_train.py:131-140,188-193; Appendix A.16) ------------------------ */
 /* stats[0]=||g||_2, stats[1]=clip coefficient (<=1), stats[2]=1 if finite else 0; from sumsq[0];

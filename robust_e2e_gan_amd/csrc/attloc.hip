@@ -69,7 +69,8 @@ __global__ __launch_bounds__(NTH) void attloc_energy_kernel(const float* __restr
                                                             const float* __restrict__ att_prev, const int* __restrict__ hlens,
                                                             const float* __restrict__ w_att, const float* __restrict__ w_conv,
                                                             const float* __restrict__ gvec, const float* __restrict__ gvec_b, int B, int T,
-                                                            int A, int C, int F, float* __restrict__ e_out, float* __restrict__ conv_out) {
+                                                            int A, int C, int F, float* __restrict__ e_out, float* __restrict__ conv_out,
+                                                            const int* __restrict__ utt, int U) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int CP = cpad(C), Kf = 2 * F + 1;
   float* ap = sm;                                 // [TCH + 2F]
@@ -77,16 +78,26 @@ __global__ __launch_bounds__(NTH) void attloc_energy_kernel(const float* __restr
   float* wcs = cv + TCH * CP;                     // [C][Kf]  filter taps
   float* cpart = wcs + ((C * Kf + 3) & ~3);       // [NWV][TCH][CP] per-wavefront partial conv tiles
   const int b = blockIdx.y, t0 = blockIdx.x * TCH;
-  const int nt = min(TCH, T - t0);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hl = hlens[b];
+  // utt == nullptr: row b reads pre[b] over all T frames (the training step; hlens[b] only shapes the uniform first att_prev).  With a row ->
+  // utterance map (re2e_attloc_fwd_rows) row b reads pre[utt[b]] and HAS only Tr = hlens[utt[b]] frames: T is the pitch, frames t >= Tr are
+  // absent (att_prev reads as 0 there, conv_out is written as 0), so the row gets what a call with T = Tr on its utterance alone gives
+  const int u = utt ? min(max(utt[b], 0), U - 1) : b;
+  const int hl = hlens[u];
+  const int Tr = utt ? min(max(hl, 1), T) : T;
+  const int nt = min(TCH, Tr - t0);
+  if (nt < TCH && Tr < T) {                             // rows variant: this chunk's frames beyond the row's own
+    const int z0 = max(nt, 0), z1 = min(TCH, T - t0);
+    for (int i = tid + z0 * C; i < z1 * C; i += NTH) conv_out[((long)b * T + t0) * C + i] = 0.f;
+    if (nt <= 0) return;                                // (uniform over the workgroup)
+  }
   // pre rows of this wavefront's 8 frames: issued first, in flight while the location conv runs
   float pv[FPW][AIMAX];
 #pragma unroll
   for (int k = 0; k < FPW; ++k) {
     const int l = wid + NWV * k;
-    const float* pr = pre + ((long)b * T + t0 + (l < nt ? l : 0)) * A;
+    const float* pr = pre + ((long)u * T + t0 + (l < nt ? l : 0)) * A;
 #pragma unroll
     for (int i = 0; i < AIMAX; ++i) { int a = lane + 64 * i; pv[k][i] = a < A ? pr[a] : 0.f; }
   }
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(NTH) void attloc_energy_kernel(const float* __restr
   for (int i = tid; i < TCH + 2 * F; i += NTH) {
     int t = t0 + i - F;
     float v = 0.f;
-    if (t >= 0 && t < T) v = att_prev ? att_prev[(long)b * T + t] : (t < hl ? 1.0f / (float)hl : 0.f);
+    if (t >= 0 && t < Tr) v = att_prev ? att_prev[(long)b * T + t] : (t < hl ? 1.0f / (float)hl : 0.f);
     ap[i] = v;
   }
   __syncthreads();
@@ -167,16 +178,21 @@ __global__ __launch_bounds__(NTH) void attloc_energy_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------
 // forward, part 2: softmax over all T (recomputed per workgroup) + context for a 64-column slice
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NTH) void attloc_context_kernel(const float* __restrict__ e, const float* __restrict__ enc, int B, int T,
-                                                             int E, float* __restrict__ w_out, float* __restrict__ c_out, long ldc_out) {
+__global__ __launch_bounds__(NTH) void attloc_context_kernel(const float* __restrict__ e, const float* __restrict__ enc, int B, int Tp,
+                                                             int E, float* __restrict__ w_out, float* __restrict__ c_out, long ldc_out,
+                                                             const int* __restrict__ utt, const int* __restrict__ hlens, int U) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* w = sm;                         // [T]
-  float* red = w + ((T + 3) & ~3);       // [32]
+  float* w = sm;                         // [Tp]
+  float* red = w + ((Tp + 3) & ~3);      // [32]
   float* scr = red + 32;                 // [16][64]
   const int b = blockIdx.y, d0 = blockIdx.x * 64;
   const int tid = threadIdx.x;
+  // Tp: the pitch of e / w_out / enc; T: the frames of this row -- all of them, or with a row -> utterance map those of its utterance
+  // (attloc_energy_kernel): the softmax and the context run over the row's own frames, w_out beyond them is written as 0
+  const int u = utt ? min(max(utt[b], 0), U - 1) : b;
+  const int T = utt ? min(max(hlens[u], 1), Tp) : Tp;
   float m = -3.0e38f;
-  for (int t = tid; t < T; t += NTH) { float v = 2.f * e[(long)b * T + t]; w[t] = v; m = fmaxf(m, v); }
+  for (int t = tid; t < T; t += NTH) { float v = 2.f * e[(long)b * Tp + t]; w[t] = v; m = fmaxf(m, v); }
   m = block_max(m, red);
   float sum = 0.f;
   for (int t = tid; t < T; t += NTH) { float v = __expf(w[t] - m); w[t] = v; sum += v; }
@@ -186,15 +202,17 @@ __global__ __launch_bounds__(NTH) void attloc_context_kernel(const float* __rest
   for (int t = tid; t < T; t += NTH) {
     float v = w[t] * inv;
     w[t] = v;
-    if (blockIdx.x == 0) w_out[(long)b * T + t] = v;
+    if (blockIdx.x == 0) w_out[(long)b * Tp + t] = v;
   }
+  if (blockIdx.x == 0)
+    for (int t = T + tid; t < Tp; t += NTH) w_out[(long)b * Tp + t] = 0.f;
   __syncthreads();
   // 16 float4 columns x 16 frame groups
   const int c4 = tid & 15, tg = tid >> 4;
   const int ncol = min(64, E - d0);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (c4 * 4 < ncol) {
-    const f32x4* er = reinterpret_cast<const f32x4*>(enc + (long)b * T * E + d0) + c4;
+    const f32x4* er = reinterpret_cast<const f32x4*>(enc + (long)u * Tp * E + d0) + c4;
     const int per = E / 4;
     int t = tg;
     for (; t + 48 < T; t += 64) {
@@ -598,27 +616,48 @@ static int check_dims(const char* fn, int B, int T, int E, int D, int A, int C, 
   return RE2E_OK;
 }
 
+// re2e_attloc_fwd (utt == nullptr: row b is utterance b, U = B) and re2e_attloc_fwd_rows: the same three launches
+static int attloc_fwd_launch(const char* fn, const float* pre, const float* enc, const float* z, const float* att_prev, const int* hlens, const int* utt, int U,
+                             const float* w_decT, const float* w_att, const float* w_conv, const float* gvec, const float* gvec_b, int B, int T, int eprojs,
+                             int dunits, int adim, int chans, int filts, float* w_out, float* c_out, long ldc_out, float* conv_out, float* dp_out,
+                             float* e_scratch, hipStream_t stream) {
+  int rc = check_dims(fn, B, T, eprojs, dunits, adim, chans, filts);
+  if (rc) return rc;
+  const int CP = (chans + 3) & ~3;
+  if (dunits > 1024) { re2e_set_error("%s: dunits > 1024 not supported", fn); return RE2E_EINVAL; }
+  hipLaunchKernelGGL(attloc_decproj_kernel, dim3((adim + 63) / 64, B), dim3(NTH), 0, stream, z, w_decT, dunits, adim, dp_out);
+  size_t lds1 = (size_t)(((TCH + 2 * filts + 3) & ~3) + TCH * CP + ((chans * (2 * filts + 1) + 3) & ~3) + NWV * TCH * CP + 16) * sizeof(float);
+  if (lds1 > 64 * 1024) { re2e_set_error("%s: aconv_filts=%d needs %zu bytes of LDS (>64 KiB)", fn, filts, lds1); return RE2E_EUNSUPPORTED; }
+  hipLaunchKernelGGL(attloc_energy_kernel, dim3(nchunks(T), B), dim3(NTH), lds1, stream, pre, (const float*)dp_out, att_prev, hlens, w_att, w_conv,
+                     gvec, gvec_b, B, T, adim, chans, filts, e_scratch, conv_out, utt, U);
+  size_t lds2 = (size_t)(((T + 3) & ~3) + 32 + 16 * 64 + 16) * sizeof(float);
+  if (lds2 > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attloc_context_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+  hipLaunchKernelGGL(attloc_context_kernel, dim3((eprojs + 63) / 64, B), dim3(NTH), lds2, stream, (const float*)e_scratch, enc, B, T, eprojs, w_out,
+                     c_out, ldc_out, utt, hlens, U);
+  hipError_t e__ = hipGetLastError();
+  if (e__ != hipSuccess) { re2e_set_error("%s: launch failed: %s", fn, hipGetErrorString(e__)); return RE2E_EHIP; }
+  return RE2E_OK;
+}
+
 extern "C" int re2e_attloc_fwd(const float* pre, const float* enc, const float* z, const float* att_prev, const int* hlens,
                                const float* w_decT, const float* w_att, const float* w_conv, const float* gvec, const float* gvec_b,
                                int B, int T, int eprojs, int dunits, int adim, int chans, int filts, float* w_out, float* c_out,
                                long ldc_out, float* conv_out, float* dp_out, float* e_scratch, hipStream_t stream) {
   RE2E_CHECK_ARG(pre && enc && hlens && w_decT && w_att && w_conv && gvec && gvec_b && w_out && c_out && conv_out && dp_out && e_scratch,
                  "null arg");
-  int rc = check_dims("re2e_attloc_fwd", B, T, eprojs, dunits, adim, chans, filts);
-  if (rc) return rc;
-  const int CP = (chans + 3) & ~3;
-  RE2E_CHECK_ARG(dunits <= 1024, "dunits > 1024 not supported");
-  hipLaunchKernelGGL(attloc_decproj_kernel, dim3((adim + 63) / 64, B), dim3(NTH), 0, stream, z, w_decT, dunits, adim, dp_out);
-  size_t lds1 = (size_t)(((TCH + 2 * filts + 3) & ~3) + TCH * CP + ((chans * (2 * filts + 1) + 3) & ~3) + NWV * TCH * CP + 16) * sizeof(float);
-  if (lds1 > 64 * 1024) { re2e_set_error("re2e_attloc_fwd: aconv_filts=%d needs %zu bytes of LDS (>64 KiB)", filts, lds1); return RE2E_EUNSUPPORTED; }
-  hipLaunchKernelGGL(attloc_energy_kernel, dim3(nchunks(T), B), dim3(NTH), lds1, stream, pre, (const float*)dp_out, att_prev, hlens, w_att, w_conv,
-                     gvec, gvec_b, B, T, adim, chans, filts, e_scratch, conv_out);
-  size_t lds2 = (size_t)(((T + 3) & ~3) + 32 + 16 * 64 + 16) * sizeof(float);
-  if (lds2 > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attloc_context_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-  hipLaunchKernelGGL(attloc_context_kernel, dim3((eprojs + 63) / 64, B), dim3(NTH), lds2, stream, (const float*)e_scratch, enc, B, T, eprojs, w_out,
-                     c_out, ldc_out);
-  RE2E_LAUNCH_CHECK();
-  return RE2E_OK;
+  return attloc_fwd_launch("re2e_attloc_fwd", pre, enc, z, att_prev, hlens, nullptr, B, w_decT, w_att, w_conv, gvec, gvec_b, B, T, eprojs, dunits, adim,
+                           chans, filts, w_out, c_out, ldc_out, conv_out, dp_out, e_scratch, stream);
+}
+
+extern "C" int re2e_attloc_fwd_rows(const float* pre, const float* enc, int U, const int* hlens, const int* utt_dev, const float* z, const float* att_prev,
+                                    const float* w_decT, const float* w_att, const float* w_conv, const float* gvec, const float* gvec_b, int nh, int T,
+                                    int eprojs, int dunits, int adim, int chans, int filts, float* w_out, float* c_out, long ldc_out, float* conv_out,
+                                    float* dp_out, float* e_scratch, hipStream_t stream) {
+  RE2E_CHECK_ARG(pre && enc && hlens && utt_dev && w_decT && w_att && w_conv && gvec && gvec_b && w_out && c_out && conv_out && dp_out && e_scratch,
+                 "null arg");
+  RE2E_CHECK_ARG(U > 0, "no utterances");
+  return attloc_fwd_launch("re2e_attloc_fwd_rows", pre, enc, z, att_prev, hlens, utt_dev, U, w_decT, w_att, w_conv, gvec, gvec_b, nh, T, eprojs, dunits,
+                           adim, chans, filts, w_out, c_out, ldc_out, conv_out, dp_out, e_scratch, stream);
 }
 
 extern "C" int re2e_attloc_bwd(const float* pre, const float* enc, const float* att_prev, const float* w_cur, const int* hlens,

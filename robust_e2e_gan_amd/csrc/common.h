@@ -119,6 +119,32 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   return r;
 }
 
+// Top-k of a row held in LDS by a 256-thread workgroup: k rounds of a workgroup arg-max, descending, ties -> lower index (torch.topk
+// order).  The row holds no NaN on entry (the callers store NaN scores as -inf); an entry that has been selected is marked with NaN and
+// skipped afterwards, so the k results are always k DISTINCT valid indices -- also for rows with fewer than k entries above -inf.
+// k <= n (an unselected entry always exists); red_v / red_i: 4 entries of LDS each; the row is published before the call and the
+// results are after it.
+__device__ __forceinline__ void block_topk256(float* row, int n, int k, int* out_i, float* out_v, float* red_v, int* red_i) {
+  constexpr int NONE = 0x7fffffff;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  for (int r = 0; r < k; ++r) {
+    float bv = -INFINITY; int bi = NONE;
+    for (int i = tid; i < n; i += 256) { const float v = row[i]; if (v == v && (bi == NONE || v > bv)) { bv = v; bi = i; } }   // ascending i: first maximum wins
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
+      if (oi != NONE && (bi == NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { red_v[wid] = bv; red_i[wid] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < 4; ++w) if (red_i[w] != NONE && (bi == NONE || red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi))) { bv = red_v[w]; bi = red_i[w]; }
+      out_i[r] = bi; out_v[r] = bv; row[bi] = __uint_as_float(0x7fc00000u);
+    }
+    __syncthreads();
+  }
+}
+
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
     case RE2E_ACT_TANH: return tanhf_(v);

@@ -336,7 +336,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const float* __restrict
   __shared__ int red_i[4];
   __shared__ int cand[64];
   __shared__ float cand_att[64];
-  const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int h = blockIdx.x, tid = threadIdx.x;
   // NaN scores are ranked as -inf (torch.topk would rank them first; a NaN row means the decoder has already diverged) and an
   // entry that has been selected is marked with NaN and skipped afterwards, so the ctc_beam candidates are always ctc_beam
   // DISTINCT, valid labels -- also for rows with fewer than ctc_beam entries above -inf (ties -> lower label, as torch.topk)
@@ -344,27 +344,46 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const float* __restrict
   for (int i = tid; i < 2 * T; i += 256) rp[i] = r_prev[(long)h * 2 * T + i];
   __syncthreads();
   for (int t = tid; t < T; t += 256) rsum[t] = logaddexp_(rp[2 * t], rp[2 * t + 1]);
-  constexpr int NONE = 0x7fffffff;
-  for (int k = 0; k < ctc_beam; ++k) {
-    float bv = -INFINITY; int bi = NONE;
-    for (int i = tid; i < V; i += 256) { const float v = row[i]; if (v == v && (bi == NONE || v > bv)) { bv = v; bi = i; } }   // ascending i: first maximum wins
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64); const int oi = __shfl_xor(bi, o, 64);
-      if (oi != NONE && (bi == NONE || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { red_v[wid] = bv; red_i[wid] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-      for (int w = 1; w < 4; ++w) if (red_i[w] != NONE && (bi == NONE || red_v[w] > bv || (red_v[w] == bv && red_i[w] < bi))) { bv = red_v[w]; bi = red_i[w]; }
-      cand[k] = bi; cand_att[k] = bv; row[bi] = __uint_as_float(0x7fc00000u);     // ctc_beam <= V: an unselected entry always exists
-    }
-    __syncthreads();
-  }
+  block_topk256(row, V, ctc_beam, cand, cand_att, red_v, red_i);     // ctc_beam <= V
   if (tid < ctc_beam)
     prefix_recursion(lpz, T, V, rp, rsum, cand[tid], cand_att[tid], out_len[h], last_label[h], prev_score[h], att_weight, ctc_weight, blank, eos,
                      r_new + ((long)h * ctc_beam + tid) * 2 * T, cand_out + (long)h * ctc_beam + tid, local_out + (long)h * ctc_beam + tid,
                      ctc_out + (long)h * ctc_beam + tid);
+}
+
+// Several utterances per launch (beam search over a batch, model/beam_search.py recognize_beam_batch): hypothesis h belongs to utterance
+// u = utt[h], whose posteriors are lpz[u] (Tmax, V) and whose frame count is T_u = tlen[u].  Everything -- the loop bounds, the clamp of
+// `start`, the <eos> score rsum[T_u - 1] -- runs on T_u, so over t < T_u a row gets bit for bit what ctc_prefix_kernel gives on its utterance
+// alone; the state rows are pitched Tmax and their entries at t >= T_u are written as CTC_LOGZERO (never read).
+__global__ __launch_bounds__(256) void ctc_prefix_batch_kernel(const float* __restrict__ lpz, int U, int Tmax, int V, const int* __restrict__ tlen,
+                                                               const int* __restrict__ utt, const float* __restrict__ att, const float* __restrict__ r_prev,
+                                                               const int* __restrict__ last_label, const int* __restrict__ out_len,
+                                                               const float* __restrict__ prev_score, int ctc_beam, float att_weight, float ctc_weight, int blank,
+                                                               int eos, int* __restrict__ cand_out, float* __restrict__ local_out, float* __restrict__ ctc_out,
+                                                               float* __restrict__ r_new) {
+  extern __shared__ float sm[];
+  float* row = sm;                       // [V]
+  float* rp = sm + V;                    // [Tmax][2]
+  float* rsum = rp + 2 * Tmax;           // [Tmax]
+  __shared__ float red_v[4];
+  __shared__ int red_i[4];
+  __shared__ int cand[64];
+  __shared__ float cand_att[64];
+  const int h = blockIdx.x, tid = threadIdx.x;
+  const int u = min(max(utt[h], 0), U - 1);                 // a bad map or length must not become an address
+  const int T = min(max(tlen[u], 1), Tmax);
+  const float* lp = lpz + (long)u * Tmax * V;
+  for (int i = tid; i < V; i += 256) { const float v = att[(long)h * V + i]; row[i] = v == v ? v : -INFINITY; }     // NaN ranks as -inf, as above
+  for (int i = tid; i < 2 * T; i += 256) rp[i] = r_prev[(long)h * 2 * Tmax + i];
+  __syncthreads();
+  for (int t = tid; t < T; t += 256) rsum[t] = logaddexp_(rp[2 * t], rp[2 * t + 1]);
+  block_topk256(row, V, ctc_beam, cand, cand_att, red_v, red_i);     // ctc_beam <= V
+  if (tid < ctc_beam) {
+    float* rn = r_new + ((long)h * ctc_beam + tid) * 2 * Tmax;
+    prefix_recursion(lp, T, V, rp, rsum, cand[tid], cand_att[tid], out_len[h], last_label[h], prev_score[h], att_weight, ctc_weight, blank, eos, rn,
+                     cand_out + (long)h * ctc_beam + tid, local_out + (long)h * ctc_beam + tid, ctc_out + (long)h * ctc_beam + tid);
+    for (int t = 2 * T; t < 2 * Tmax; ++t) rn[t] = CTC_LOGZERO;
+  }
 }
 
 // The same scores for a GIVEN candidate list (ctc_weight == 1.0 scores all V labels, in the order of their attention scores: the list
@@ -404,6 +423,24 @@ extern "C" int re2e_ctc_prefix_score(const float* lpz, int T, int V, const float
   lim.ensure(reinterpret_cast<const void*>(&ctc_prefix_kernel), lds);
   hipLaunchKernelGGL(ctc_prefix_kernel, dim3(nh), dim3(256), lds, stream, lpz, T, V, att_lsm, r_prev, last_label_dev, out_len_dev, prev_score_dev,
                      ctc_beam, att_weight, ctc_weight, blank, eos, cand_out, local_out, ctc_score_out, r_new);
+  RE2E_LAUNCH_CHECK();
+  return RE2E_OK;
+}
+
+extern "C" int re2e_ctc_prefix_score_batch(const float* lpz, int U, int Tmax, int V, const int* tlen_dev, const int* utt_dev, const float* att_lsm, int nh,
+                                           const float* r_prev, const int* last_label_dev, const int* out_len_dev, const float* prev_score_dev, int ctc_beam,
+                                           float att_weight, float ctc_weight, int blank, int eos, int* cand_out, float* local_out, float* ctc_score_out,
+                                           float* r_new, hipStream_t stream) {
+  RE2E_CHECK_ARG(lpz && tlen_dev && utt_dev && att_lsm && r_prev && last_label_dev && out_len_dev && prev_score_dev && cand_out && local_out &&
+                     ctc_score_out && r_new, "null operand");
+  RE2E_CHECK_ARG(U > 0 && Tmax > 0 && V > 0 && nh > 0 && blank >= 0 && blank < V && eos >= 0 && eos < V, "bad geometry");
+  if (ctc_beam < 1 || ctc_beam > 64 || ctc_beam > V) { re2e_set_error("re2e_ctc_prefix_score_batch: ctc_beam must be in [1, min(64, V)]"); return RE2E_EUNSUPPORTED; }
+  const size_t lds = ((size_t)V + 3 * (size_t)Tmax) * sizeof(float);
+  if (lds > 150 * 1024) { re2e_set_error("re2e_ctc_prefix_score_batch: V + 3 Tmax floats exceed the LDS"); return RE2E_EUNSUPPORTED; }
+  static LdsLimit lim;
+  lim.ensure(reinterpret_cast<const void*>(&ctc_prefix_batch_kernel), lds);
+  hipLaunchKernelGGL(ctc_prefix_batch_kernel, dim3(nh), dim3(256), lds, stream, lpz, U, Tmax, V, tlen_dev, utt_dev, att_lsm, r_prev, last_label_dev,
+                     out_len_dev, prev_score_dev, ctc_beam, att_weight, ctc_weight, blank, eos, cand_out, local_out, ctc_score_out, r_new);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 323      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 324      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -122,8 +122,10 @@ SIGNATURES = {
     're2e_ctc_fwd': (I, [P, I, I, I, P, P, P, P, I, P, P, P, Z, P]),
     're2e_ctc_bwd': (I, [P, I, I, I, P, P, P, P, I, P, P, P, I, P, P]),
     're2e_ctc_prefix_score': (I, [P, I, I, P, I, P, P, P, P, I, F, F, I, I, P, P, P, P, P]),
+    're2e_ctc_prefix_score_batch': (I, [P, I, I, I, P, P, P, I, P, P, P, P, I, F, F, I, I, P, P, P, P, P]),
     're2e_ctc_prefix_score_cands': (I, [P, I, I, P, I, P, P, P, P, P, I, F, F, I, I, P, P, P, P]),
     're2e_attloc_fwd': (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, L, P, P, P, P]),
+    're2e_attloc_fwd_rows': (I, [P, P, I, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P, P, L, P, P, P, P]),
     're2e_attloc_partial_floats': (Z, [I, I, I]),
     're2e_attloc_workspace_bytes': (Z, [I, I, I, I]),
     're2e_attloc_bwd': (I, [P, P, P, P, P, P, P, P, P, P, P, P, L, P, I, I, I, I, I, I, P, P, P, P, P, Z, P]),
@@ -133,6 +135,7 @@ SIGNATURES = {
     're2e_lm_output': (I, [P, P, P, I, I, I, P, P]),
     're2e_lm_log_softmax_combine': (I, [P, I, I, P, F, P, P, P]),
     're2e_lm_add_cands': (I, [P, P, P, I, I, I, F, P]),
+    're2e_beam_prune': (I, [P, I, I, P, P, P, I, I, I, P, P, P, P, P, P, Z, P]),
     're2e_clip_coef': (I, [P, F, P, P]),
     're2e_adadelta_step': (I, [P, P, P, P, L, F, F, F, P, P]),
     're2e_adam_step': (I, [P, P, P, P, L, F, F, F, F, I, P, P]),

@@ -20,7 +20,19 @@ RNNLM shallow fusion (e2e_decoder.py:270-272,284-285; model/lm.py here): the LM 
 in one ``predict`` call per position, its four state tensors (nh, n_units) stay on the device and follow the survivors through the
 same ``parents`` gather as the decoder state.  Attention-only search ranks ``att + lm_weight * lm`` over all V labels; with CTC
 the candidates are chosen on the attention scores alone and ``lm_weight * lm[cand]`` is added to their local scores -- on the
-device-CTC path by re2e_lm_add_cands before the 3 x nh x ctc_beam copy, so the LM's (nh, V) rows never cross to the host there."""
+device-CTC path by re2e_lm_add_cands before the 3 x nh x ctc_beam copy, so the LM's (nh, V) rows never cross to the host there.
+
+Several utterances per search (``recognize_beam_batch``, E2E.recognize_batch): one loop over output positions drives all unfinished
+utterances.  The rows of a position are their live hypotheses, grouped by utterance; an utterance whose own ``end_detect`` fires, whose
+hypotheses run out or that reaches its own ``maxlen`` leaves and its rows are compacted away.  The encoder states and ``mlp_enc`` projections
+are held once per utterance in (U, T'max, .) buffers and read through a row -> utterance map (re2e_attloc_fwd_rows) instead of being
+replicated per hypothesis; the prefix scorer takes the same map and every utterance's own frame count (re2e_ctc_prefix_score_batch); and
+the pruning -- the per-hypothesis top-k plus the repeated ``sorted(kept)[:beam]`` below -- is re2e_beam_prune, which orders the survivors of
+an utterance exactly as that host loop does (score descending, then parent row ascending, then local score descending, then column
+ascending).  The (nh, V) scores never leave the device: one copy of the (U_live, beam) survivor arrays (parent row, column, label, score,
+and on the joint path their prefix scores) crosses per position.  Every score is rounded as on the single-utterance path, so the n-best
+lists are those of ``recognize_beam`` utterance by utterance.  ``ctc_beam`` > 64 (ctc_weight == 1.0) and ``beam_size`` > 64 are beyond the
+kernels' limits: there the batch is a loop over ``recognize_beam``."""
 import numpy as np
 import torch
 
@@ -234,3 +246,178 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
                 r_prev = r_new.index_select(0, rows)
         best = sorted(ended, key=lambda x: x['score'], reverse=True)[:min(len(ended), recog_args.nbest)]
         return [{'yseq': b['yseq'], 'score': float(b['score'])} for b in best]
+
+
+BATCH_MAX_BEAM = 64             # re2e_beam_prune: beam <= 64, at most `beam` rows per utterance
+
+
+def _final_nbest(ended, nbest):
+    best = sorted(ended, key=lambda x: x['score'], reverse=True)[:min(len(ended), nbest)]
+    return [{'yseq': b['yseq'], 'score': float(b['score'])} for b in best]
+
+
+def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
+    """``hs``: list of U (T'_u, eprojs) encoder-state tensors on the GPU; ``lpzs``: list of U (T'_u, V) CTC log posteriors on the same
+    device, or None; the rest as ``recognize_beam``.  Returns U n-best lists, element u being what ``recognize_beam`` returns for
+    utterance u alone."""
+    U = len(hs)
+    if U == 0:
+        return []
+    dev = hs[0].device
+    E = hs[0].shape[1]
+    Ts = [int(h.shape[0]) for h in hs]
+    Tmax = max(Ts)
+    beam, penalty, ctc_weight = recog_args.beam_size, recog_args.penalty, recog_args.ctc_weight
+    out_w = p[prefix + 'dec.output.weight']
+    V = out_w.shape[0]
+    joint = lpzs is not None
+    ctc_beam = (min(V, int(beam * CTC_SCORING_RATIO)) if ctc_weight != 1.0 else V) if joint else 0
+    if beam > BATCH_MAX_BEAM or ctc_beam > DEVICE_CTC_MAX_BEAM or (joint and HOST_CTC_SCORER):
+        # beyond the batched kernels' limits (ctc_weight == 1.0 scores all V labels), or the tests' host scorer: the same result, one utterance
+        # at a time
+        return [recognize_beam(p, hs[u], lpzs[u].detach().cpu().numpy() if joint else None, recog_args, eos, prefix,
+                               lpz_dev=lpzs[u] if joint else None, rnnlm=rnnlm) for u in range(U)]
+    embed, w_ih, w_hh = p[prefix + 'dec.embed.weight'], p[prefix + 'dec.decoder.0.weight_ih'], p[prefix + 'dec.decoder.0.weight_hh']
+    b_ih, b_hh = p[prefix + 'dec.decoder.0.bias_ih'], p[prefix + 'dec.decoder.0.bias_hh']
+    out_b = p[prefix + 'dec.output.bias']
+    mlp_dec, mlp_att = p[prefix + 'att.mlp_dec.weight'], p[prefix + 'att.mlp_att.weight']
+    loc_conv, gvec_w, gvec_b = p[prefix + 'att.loc_conv.weight'], p[prefix + 'att.gvec.weight'], p[prefix + 'att.gvec.bias']
+    Dd, D, A = embed.shape[1], w_hh.shape[1], mlp_dec.shape[0]
+    C, Fh = loc_conv.shape[0], (loc_conv.shape[3] - 1) // 2
+    ldw = Dd + E
+    lm_weight = np.float32(recog_args.lm_weight) if rnnlm is not None else None
+    lm_state = None
+    kk = min(beam, ctc_beam if joint else V)
+    with torch.no_grad():
+        # one copy of every utterance's states and projections, zero rows beyond its length; the projection is the single-utterance
+        # search's own product, utterance by utterance
+        enc, pre = torch.zeros(U, Tmax, E, device=dev), torch.zeros(U, Tmax, A, device=dev)
+        for u, h in enumerate(hs):
+            enc[u, :Ts[u]] = h
+            pre[u, :Ts[u]] = ops.linear(h.unsqueeze(0), p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'])[0]
+        tl = lens_dev(Ts, dev)
+        w_decT = torch.empty(D, A, device=dev)
+        call('re2e_transpose01', mlp_dec.data_ptr(), w_decT.data_ptr(), A, D, 1)
+        w_ctx = w_ih.data_ptr() + 4 * Dd
+        maxlen = [T if recog_args.maxlenratio == 0 else max(1, int(recog_args.maxlenratio * T)) for T in Ts]
+        minlen = [int(recog_args.minlenratio * T) for T in Ts]
+        hyps = [[{'score': np.float32(0.0), 'yseq': [eos]}] for _ in range(U)]
+        ended = [[] for _ in range(U)]
+        if joint:
+            lpz_d = torch.zeros(U, Tmax, V, device=dev)
+            for u in range(U):
+                lpz_d[u, :Ts[u]] = lpzs[u].float()
+            blank_col = lpz_d[:, :, 0].cpu().numpy()                        # CTCPrefixScore.initial_state, per utterance (once per search)
+            r0 = np.full((U, Tmax, 2), LOGZERO, dtype=np.float32)
+            for u in range(U):
+                r0[u, :Ts[u], 1] = np.cumsum(blank_col[u, :Ts[u]], dtype=np.float32)
+                hyps[u][0]['ctc_score'] = np.float32(0.0)
+            r_prev = torch.from_numpy(r0).to(dev)
+        live = list(range(U))
+        z, c, a_prev = torch.zeros(U, D, device=dev), torch.zeros(U, D, device=dev), None
+        i = 0
+        while live:
+            rows = [(u, hp) for u in live for hp in hyps[u]]
+            nh, nl = len(rows), len(live)
+            seg = np.zeros(nl + 1, np.int32)
+            seg[1:] = np.cumsum([len(hyps[u]) for u in live])
+            meta = np.empty((3, nh), np.int32)                              # last label, utterance, output length: one upload
+            meta[0] = [hp['yseq'][i] for _, hp in rows]
+            meta[1] = [u for u, _ in rows]
+            meta[2] = [len(hp['yseq']) - 1 for _, hp in rows]
+            meta_d = host_to_dev(meta, dev)
+            ids, utt, olen = meta_d[0], meta_d[1], meta_d[2]
+            seg_d = host_to_dev(seg, dev)
+            hsc = host_to_dev(np.asarray([hp['score'] for _, hp in rows], np.float32), dev, torch.float32)
+            emb = torch.empty(nh, Dd, device=dev)
+            call('re2e_embedding_fwd', embed.data_ptr(), ids.data_ptr(), nh, Dd, emb.data_ptr(), Dd)
+            w_new, cx = torch.empty(nh, Tmax, device=dev), torch.empty(nh, E, device=dev)
+            conv, dpj, e_scr = torch.empty(nh, Tmax, C, device=dev), torch.empty(nh, A, device=dev), torch.empty(nh, Tmax, device=dev)
+            call('re2e_attloc_fwd_rows', pre.data_ptr(), enc.data_ptr(), U, tl.data_ptr(), utt.data_ptr(), z.data_ptr(),
+                 a_prev.data_ptr() if a_prev is not None else None, w_decT.data_ptr(), mlp_att.data_ptr(), loc_conv.data_ptr(), gvec_w.data_ptr(),
+                 gvec_b.data_ptr(), nh, Tmax, E, D, A, C, Fh, w_new.data_ptr(), cx.data_ptr(), E, conv.data_ptr(), dpj.data_ptr(), e_scr.data_ptr())
+            gates = torch.empty(nh, 4 * D, device=dev)
+            ops.gemm(emb, w_ih, gates, nh, 4 * D, Dd, transb=True, ldb=ldw, bias=b_ih, bias2=b_hh)
+            ops.gemm(cx, w_ctx, gates, nh, 4 * D, E, transb=True, ldb=ldw, beta=1.0, dev=dev)
+            ops.gemm(z, w_hh, gates, nh, 4 * D, D, transb=True, beta=1.0)
+            z_new, c_new = torch.empty(nh, D, device=dev), torch.empty(nh, D, device=dev)
+            call('re2e_lstm_cell_fwd', gates.data_ptr(), c.data_ptr(), c_new.data_ptr(), z_new.data_ptr(), nh, D)
+            logits, lsm = torch.empty(nh, V, device=dev), torch.empty(nh, V, device=dev)
+            ops.gemm(z_new, out_w, logits, nh, V, D, transb=True, bias=out_b)
+            call('re2e_log_softmax_rows', logits.data_ptr(), nh, V, V, lsm.data_ptr())
+            if rnnlm is not None:
+                lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if not joint else None, lm_weight)
+            # the survivors: parent row, column, label, score (and their prefix scores), one int32 buffer -> one copy to the host
+            surv = torch.empty(5 * nl * beam + nl, dtype=torch.int32, device=dev)
+            part = [surv[k * nl * beam:(k + 1) * nl * beam] for k in range(5)]
+            count_d = surv[5 * nl * beam:]
+            ws = torch.empty(2 * nh * kk, dtype=torch.int32, device=dev)
+            if joint:
+                for u in live:
+                    longest = max(len(hp['yseq']) - 1 for hp in hyps[u])
+                    if longest > Ts[u]:
+                        # CTCPrefixScore indexes r[output_length - 1] over the utterance's frames (e2e_ctc.py:128-133): IndexError upstream
+                        raise IndexError('CTC prefix score: utterance %d: hypothesis of %d labels on %d encoder frames (lower maxlenratio)'
+                                         % (u, longest, Ts[u]))
+                prev = host_to_dev(np.asarray([hp['ctc_score'] for _, hp in rows], np.float32), dev, torch.float32)
+                out_d = torch.empty(2, nh, ctc_beam, device=dev)                  # [0] local scores, [1] prefix scores
+                r_new = torch.empty(nh * ctc_beam, 2 * Tmax, device=dev)
+                cand_d = torch.empty(nh, ctc_beam, dtype=torch.int32, device=dev)
+                call('re2e_ctc_prefix_score_batch', lpz_d.data_ptr(), U, Tmax, V, tl.data_ptr(), utt.data_ptr(), lsm.data_ptr(), nh, r_prev.data_ptr(),
+                     ids.data_ptr(), olen.data_ptr(), prev.data_ptr(), ctc_beam, float(np.float32(1.0 - ctc_weight)), float(np.float32(ctc_weight)), 0, eos,
+                     cand_d.data_ptr(), out_d[0].data_ptr(), out_d[1].data_ptr(), r_new.data_ptr())
+                if rnnlm is not None:
+                    call('re2e_lm_add_cands', out_d[0].data_ptr(), lm_lp.data_ptr(), cand_d.data_ptr(), nh, ctc_beam, V, float(lm_weight))
+                local, cand_ptr, ncand = out_d[0], cand_d.data_ptr(), ctc_beam
+            else:
+                local, cand_ptr, ncand = (lsm if rnnlm is None else att_lm), None, V
+            call('re2e_beam_prune', seg_d.data_ptr(), nl, int(max(len(hyps[u]) for u in live)), hsc.data_ptr(), local.data_ptr(), cand_ptr, nh, ncand, beam,
+                 part[0].data_ptr(), part[1].data_ptr(), part[2].data_ptr(), part[3].data_ptr(), count_d.data_ptr(), ws.data_ptr(), ws.numel() * 4)
+            if joint:
+                at = part[0].clamp(min=0).long() * ctc_beam + part[1].clamp(min=0).long()          # (parent, column) in the scorer's outputs
+                part[4].view(torch.float32).copy_(out_d[1].reshape(-1).index_select(0, at))
+            surv_h = surv.cpu().numpy()                                       # this position's host round trip
+            sv = surv_h[:5 * nl * beam].reshape(5, nl, beam)
+            sv_f = sv.view(np.float32)
+            counts = surv_h[5 * nl * beam:]
+            keep_rows, keep_ctc, still = [], [], []
+            for j, u in enumerate(live):
+                base = int(seg[j])
+                new = []
+                for k in range(int(counts[j])):
+                    par = int(sv[0, j, k])
+                    hyp = {'score': sv_f[3, j, k], 'yseq': hyps[u][par - base]['yseq'] + [int(sv[2, j, k])], 'parent': par}
+                    if joint:
+                        hyp['ctc_row'], hyp['ctc_score'] = par * ctc_beam + int(sv[1, j, k]), sv_f[4, j, k]
+                    new.append(hyp)
+                last = i == maxlen[u] - 1
+                if last:
+                    for hyp in new:
+                        hyp['yseq'].append(eos)
+                remained = []
+                for hyp in new:
+                    if hyp['yseq'][-1] == eos:
+                        if len(hyp['yseq']) > minlen[u]:
+                            hyp['score'] = np.float32(hyp['score'] + (i + 1) * penalty)
+                            ended[u].append(hyp)
+                    else:
+                        remained.append(hyp)
+                if (end_detect(ended[u], i) and recog_args.maxlenratio == 0.0) or not remained or last:
+                    hyps[u] = []
+                    continue
+                hyps[u] = remained
+                still.append(u)
+                keep_rows.extend(hp['parent'] for hp in remained)
+                if joint:
+                    keep_ctc.extend(hp['ctc_row'] for hp in remained)
+            live = still
+            i += 1
+            if not live:
+                break
+            parents = host_to_dev(np.asarray(keep_rows, np.int64), dev, torch.int64)
+            z, c, a_prev = z_new.index_select(0, parents), c_new.index_select(0, parents), w_new.index_select(0, parents)
+            if lm_state is not None:
+                lm_state = {key: v.index_select(0, parents) for key, v in lm_state.items()}
+            if joint:
+                r_prev = r_new.index_select(0, host_to_dev(np.asarray(keep_ctc, np.int64), dev, torch.int64))
+        return [_final_nbest(ended[u], recog_args.nbest) for u in range(U)]

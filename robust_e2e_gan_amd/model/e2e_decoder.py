@@ -106,11 +106,8 @@ class Decoder(torch.nn.Module):
         self.loss = loss
         return loss, (acc if self.return_acc_tensor else float(acc))
 
-    def recognize_beam(self, h, lpz, recog_args, char_list=None, rnnlm=None, fstlm=None):
-        """e2e_decoder.py:171-369: n-best list of {'yseq', 'score'} for the encoder states ``h`` (T', eprojs) of one
-        utterance; ``lpz`` = CTC log posteriors (T', V) or None.  All live hypotheses are advanced as one GPU batch.
-        ``rnnlm``: a model.lm.ClassifierWithState over an RNNLM for shallow fusion with weight ``recog_args.lm_weight``
-        (:270-272,284-285); no other LM is supported."""
+    def _check_decode_lm(self, rnnlm, fstlm, device):
+        """What recognize_beam and recognize_beam_batch accept as a decode-time LM: an RNNLM under ClassifierWithState, shallow fusion only."""
         if fstlm is not None:
             raise Re2eError('decode-time LM: only RNNLM shallow fusion (rnnlm=ClassifierWithState(RNNLM(...))) is supported; '
                             'n-gram / FST LMs (fstlm) are out of scope')
@@ -124,15 +121,37 @@ class Decoder(torch.nn.Module):
                                 '(MultiLevelLM, LookAheadWordLM), the FS-RNN LM and %s are out of scope' % type(rnnlm).__name__)
             if rnnlm.predictor.n_vocab != self.output.weight.shape[0]:
                 raise Re2eError('the RNNLM has %d labels, the decoder %d' % (rnnlm.predictor.n_vocab, self.output.weight.shape[0]))
-            if rnnlm.predictor.lo.weight.device != h.device:
-                raise Re2eError('the RNNLM is on %s, the encoder states on %s' % (rnnlm.predictor.lo.weight.device, h.device))
+            if rnnlm.predictor.lo.weight.device != device:
+                raise Re2eError('the RNNLM is on %s, the encoder states on %s' % (rnnlm.predictor.lo.weight.device, device))
             if rnnlm.training or rnnlm.predictor.training:
                 raise Re2eError('the RNNLM must be in evaluation mode (rnnlm.eval())')
+
+    def recognize_beam(self, h, lpz, recog_args, char_list=None, rnnlm=None, fstlm=None):
+        """e2e_decoder.py:171-369: n-best list of {'yseq', 'score'} for the encoder states ``h`` (T', eprojs) of one
+        utterance; ``lpz`` = CTC log posteriors (T', V) or None.  All live hypotheses are advanced as one GPU batch.
+        ``rnnlm``: a model.lm.ClassifierWithState over an RNNLM for shallow fusion with weight ``recog_args.lm_weight``
+        (:270-272,284-285); no other LM is supported."""
+        self._check_decode_lm(rnnlm, fstlm, h.device)
         from .beam_search import recognize_beam
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
         p.update({'att.' + k: v for k, v in self.att.named_parameters()})
         lp = lpz.detach().cpu().numpy() if isinstance(lpz, torch.Tensor) else lpz
         return recognize_beam(p, h, lp, recog_args, self.eos, lpz_dev=lpz if isinstance(lpz, torch.Tensor) and lpz.is_cuda else None, rnnlm=rnnlm)
+
+    def recognize_beam_batch(self, hs, lpzs, recog_args, char_list=None, rnnlm=None, fstlm=None):
+        """``recognize_beam`` for several utterances in one search: ``hs`` = list of (T'_u, eprojs) encoder states on the GPU, ``lpzs`` = list
+        of (T'_u, V) CTC log posteriors on the same device or None.  Returns one n-best list per utterance, each what ``recognize_beam``
+        returns for that utterance alone; the live hypotheses of all unfinished utterances advance as one GPU batch and are pruned on the
+        device (model/beam_search.py recognize_beam_batch)."""
+        if len(hs) == 0:
+            return []
+        self._check_decode_lm(rnnlm, fstlm, hs[0].device)
+        if lpzs is not None and len(lpzs) != len(hs):
+            raise Re2eError('recognize_beam_batch: %d utterances but %d CTC posterior matrices' % (len(hs), len(lpzs)))
+        from .beam_search import recognize_beam_batch
+        p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
+        p.update({'att.' + k: v for k, v in self.att.named_parameters()})
+        return recognize_beam_batch(p, [h.float().contiguous() for h in hs], lpzs, recog_args, self.eos, rnnlm=rnnlm)
 
     def calculate_all_attentions(self, hpad, hlen, ys):
         """e2e_decoder.py:371-461 -- attention weights (B, Lmax+1, T').  NB the reference's pass is GREEDY: for i > 0 it

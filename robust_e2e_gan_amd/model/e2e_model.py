@@ -78,6 +78,30 @@ class E2E(ModelBase):
             if prev:
                 self.train()
 
+    def recognize_batch(self, xs, ilens, recog_args, char_list=None, rnnlm=None, fstlm=None):
+        """Beam search for U utterances at once: ``xs`` (U, Tmax, fbank_dim) zero-padded, ``ilens`` their U lengths -> a list of U n-best
+        lists, element u being what ``recognize(xs[u:u+1, :ilens[u]], ...)`` returns.  Every utterance is ENCODED on its own, exactly as
+        ``recognize`` encodes it (the VGG stack does not mask between its convolutions, so a padded batch is not known to reproduce the
+        single-utterance states at the last valid frames); the search then drives all of them together (Decoder.recognize_beam_batch)."""
+        prev = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                lens = lens_list(ilens)
+                if len(lens) != xs.shape[0]:
+                    raise Re2eError('recognize_batch: %d utterances but %d lengths' % (xs.shape[0], len(lens)))
+                hs, lpzs = [], ([] if recog_args.ctc_weight > 0.0 else None)
+                for u, T in enumerate(lens):
+                    x = to_cuda(self, xs[u:u + 1, :T])
+                    hpad, _ = self.enc(x, [x.shape[1]])
+                    hs.append(hpad[0])
+                    if lpzs is not None:
+                        lpzs.append(self.ctc.log_softmax(hpad)[0])
+                return self.dec.recognize_beam_batch(hs, lpzs, recog_args, char_list, rnnlm, fstlm)
+        finally:
+            if prev:
+                self.train()
+
     def forward(self, inputs, targets, input_sizes, target_sizes, scheduled_sampling_rate=0.0):
         """-> (loss_ctc, loss_att, acc)   (e2e_model.py:169-202)"""
         xpad = to_cuda(self, inputs)
