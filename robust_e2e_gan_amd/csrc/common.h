@@ -236,7 +236,7 @@ ConvPlan plan_conv(const ConvIn& in);
 // would be >= 97 % padding; thin_wgrad_slabs returns 0 when the shape is not covered.
 bool thin_fwd_plan(const ConvIn& in, bool no_rows, ConvPlan& p);
 void thin_conv_forward(const ConvPlan& p, const ConvGeom& g, const float* wg, int Cout, const OutMap& o, const float* bias, int act, float beta, hipStream_t st);
-int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows);
+int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows, int PW, int SX);
 void thin_wgrad(const ConvGeom& g, const float* dout, int Cout, float* slabs, int nslab, hipStream_t st);
 // conv3x3.hip: 3x3 / stride-1 / pad-1 convolutions with C % 16 == 0 and Cout % 64 == 0 (halo patch staged once per channel chunk, taps walked in LDS)
 bool halo_plan(const ConvIn& in, ConvPlan& p);

@@ -1259,7 +1259,7 @@ static void plan_wgrad(const ConvIn& in, const ConvSwitches& sw, ConvPlan& p) {
   const bool aligned = in.in16 && in.wg16;
   p.vec = aligned && in.C % 4 == 0 && Cout % 4 == 0;
   p.tile = wgrad_tile(Mrows, Cout, p.vec);
-  const int thin = (in.C == 1 || Cout == 1) && !sw.no_thin ? thin_wgrad_slabs(in.C, Cout, in.KH, in.KW, P, rows) : 0;
+  const int thin = (in.C == 1 || Cout == 1) && !sw.no_thin ? thin_wgrad_slabs(in.C, Cout, in.KH, in.KW, P, rows, in.PW, in.SX) : 0;
   const int engine = pick_splits(Mrows, Cout, (int)P, wgrad_tile(Mrows, Cout, true), in.cus);
   p.route = thin && aligned ? (in.C == 1 ? kWgradCin1 : kWgradCout1) : kWgradEngine;
   p.splits = p.route == kWgradEngine ? engine : thin;

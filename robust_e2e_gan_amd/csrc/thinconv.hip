@@ -320,8 +320,14 @@ inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 constexpr int COUT1_CHUNK = 128;   // pixels per (chunk, tap) workgroup of the Cout == 1 weight gradient
 constexpr int ROWS_TH = 16;        // output rows per workgroup of the row-tile Cout == 1 kernel
+constexpr size_t CU_LDS_BYTES = 160 * 1024;      // a gfx950 CU's LDS: the most one workgroup can ask for (a host constant: the plans stay pure)
+
+inline size_t cout1_rows_lds(int W) { return (size_t)(ROWS_TH + 2) * (W + 2) * 9 * sizeof(float); }
 
 inline int cin1_span(const ConvGeom& g) { return (g.PW - 1) * g.SX + (g.KW - 1) * g.DX + 1; }
+// dynamic LDS of wgrad_cin1_kernel: KH input rows of `span` floats, then the 4 wavefronts' taps x Cout partial sums
+inline size_t wgrad_cin1_lds(int KH, int KW, int Cout, int span) { return (size_t)(((KH * span + 3) & ~3) + 4 * KH * KW * Cout) * 4; }
+constexpr size_t PLAIN_LDS_BYTES = 64 * 1024;    // what a launch may ask for without raising the kernel's limit (wgrad_cin1_kernel does not)
 
 template <int L, int KH_T, int KW_T, int CH_T>
 void launch_cout1(const ConvGeom& g, const float* wg, int K, int M, const OutMap& o, const float* bias, int act, float beta,
@@ -389,12 +395,13 @@ bool thin_fwd_plan(const ConvIn& in, bool no_rows, ConvPlan& p) {
     return true;
   }
   if (!(Cout == 1 && in.C % 4 == 0 && K <= 16384 && in.in16 && in.wg16)) return false;
-  // 64 channels, 3x3, stride 1, taps within one pixel of the output position, dense single-channel output: row-tile kernel
+  // 64 channels, 3x3, stride 1, taps within one pixel of the output position, dense single-channel output: row-tile kernel, while its
+  // [18][W + 2][9] table fits a CU's LDS (W <= 250; wider rows go to cout1<16,3,3,1> below)
   if (!no_rows && in.C == 64 && in.KH == 3 && in.KW == 3 && in.SY == 1 && in.SX == 1 && in.PH == in.H && in.PW == in.W && !in.remap &&
-      (in.DY == 1 || in.DY == -1) && (in.DX == 1 || in.DX == -1) && in.OY0 == -in.DY && in.OX0 == -in.DX && in.W >= 16 && in.W <= 256 &&
+      (in.DY == 1 || in.DY == -1) && (in.DX == 1 || in.DX == -1) && in.OY0 == -in.DY && in.OX0 == -in.DX && in.W >= 16 && cout1_rows_lds(in.W) <= CU_LDS_BYTES &&
       (long)in.H * in.W * 256 < 0x7fffffffL) {
     p.route = kCout1Rows;
-    p.lds = (size_t)(ROWS_TH + 2) * (in.W + 2) * 9 * sizeof(float);
+    p.lds = cout1_rows_lds(in.W);
     p.grid = in.NI * cdiv(in.H, ROWS_TH);
     return true;
   }
@@ -445,9 +452,10 @@ void thin_conv_forward(const ConvPlan& p, const ConvGeom& g, const float* wg, in
 #undef RE2E_ARGS
 }
 
-// rows = NI*PH output rows (Cin == 1 path), P = pixels
-int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows) {
+// rows = NI*PH output rows (Cin == 1 path), P = pixels; PW, SX: the row of the Cin == 1 kernel's LDS stage (wider rows than it holds: 0, the engine)
+int thin_wgrad_slabs(int C, int Cout, int KH, int KW, long P, long rows, int PW, int SX) {
   if (C == 1 && Cout % 4 == 0 && pow2(Cout / 4) && Cout <= 128 && KH * KW <= MAXTAPS) {
+    if (wgrad_cin1_lds(KH, KW, Cout, (PW - 1) * SX + KW) > PLAIN_LDS_BYTES) return 0;
     long nb = (rows + 7) / 8;                                   // >= 8 rows per workgroup
     return (int)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb));
   }
@@ -459,7 +467,7 @@ void thin_wgrad(const ConvGeom& g, const float* dout, int Cout, float* slabs, in
   const int P = g.NI * g.PH * g.PW;
   if (g.C == 1) {
     const int span = cin1_span(g);
-    const size_t lds = (size_t)(((g.KH * span + 3) & ~3) + 4 * g.KH * g.KW * Cout) * 4;
+    const size_t lds = wgrad_cin1_lds(g.KH, g.KW, Cout, span);
     hipLaunchKernelGGL(wgrad_cin1_kernel, dim3(nslab), dim3(256), lds, st, g, dout, Cout, span, slabs);
   } else {
     hipLaunchKernelGGL(wgrad_cout1_kernel, dim3(nslab, g.KH * g.KW), dim3(256), 0, st, g, dout, P, COUT1_CHUNK, slabs);

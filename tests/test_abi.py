@@ -278,7 +278,7 @@ def test_conv_plan_table():
         import __graft_entry__ as g
         g.build()
     rows = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'conv_plan_table.json')))
-    assert len(rows) == 466
+    assert len(rows) == 468
     for args, want in rows:
         got = lib.conv_plan(*args[:13], flags=args[13], cus=256)
         assert got == want, (args, got, want)
