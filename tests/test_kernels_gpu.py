@@ -38,6 +38,10 @@ def rnd(*shape, seed=0, scale=1.0):
 
 
 # ---------------------------------------------------------------------------------------------
+# The dense tests below (test_gemm_nt_nn, test_gemm_nt_pipeline_and_stream_k, test_gemm_routes_no_other_shape_reaches, test_gemm_tn_splitk,
+# test_gemm_nt_rows, test_gemm_tn_rows, test_gemm_skinny2) stay as they grew, shape by shape.  Every form the dense plan can name, each at a bar of
+# 8 x an fp32 CPU evaluation (none above 1e-5) with NaN behind every leading dimension, is in tests/test_dense_kernels_gpu.py (reference and case
+# table: tests/refs64_gemm.py); tests/test_refs64_gemm_cpu.py counts what the bars here would let pass.
 # small, ragged and one-k-tile shapes on the engine; the last two (K and N multiples of 4, many rows) run on csrc/gemm_nt.hip's pipeline in the
 # x W^T form and on the engine's 128x128 tiles in the NN form.  The engine's row tail and 32x128 tile: test_gemm_routes_no_other_shape_reaches.
 @pytest.mark.parametrize('M,N,K', [(77, 257, 130), (256, 128, 64), (5, 3, 7), (300, 4233, 512), (130, 64, 257), (12800, 2048, 48),
