@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 324
+#define RE2E_ABI_VERSION 325
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -164,6 +164,18 @@ int re2e_conv3x3_wino_rows(const float* in, int NI, int H, int W, int C, const f
 int re2e_conv3x3_wino_wgrad_rows(const float* in, int NI, int H, int W, int C, const float* dout, int Cout, float* gw, float beta,
                                  const int* row_lim, void* workspace, size_t workspace_bytes, re2e_stream_t stream);
 int re2e_fill_image_rows(float* t, int N, int H, long row_floats, const int* lim, int div, int max_tail_rows, float value, re2e_stream_t stream);
+
+/* re2e_conv3x3_wino's forward over a PADDED image batch in which image n IS an image of valid_rows[n] rows (int32 on the device,
+ * 1 <= valid_rows[n] <= H) sitting in a slot of H rows -- inference over utterances of different lengths (Encoder.encode_batch).  Input rows
+ * >= valid_rows[n] are never read: they read as zero, as the rows beyond H do, whatever that memory holds (NaN, Inf, uninitialised).  Output
+ * rows < valid_rows[n] -- with pool_out: pooled rows < ceil(valid_rows[n] / 2) and their index bytes, a window that straddles the end taking
+ * its maximum over the rows inside (ceil mode) -- are bit for bit what re2e_conv3x3_wino writes for the cropped image alone.  Output rows
+ * beyond are NOT written (unspecified): a consumer is given the same lengths and never reads them, so no fill is needed between layers.
+ * Strides and allocation sizes stay those of H.  Forward only: dgrad = 1 or a mask is RE2E_EUNSUPPORTED (training keeps the reference's
+ * arithmetic, which convolves the zero-padded batch WITHOUT masking between the layers: re2e_conv3x3_wino / _rows). */
+int re2e_conv3x3_wino_valid(const float* in, int NI, int H, int W, int C, const float* w, int Cout, int dgrad, const float* bias, int relu,
+                            const float* mask, float* out, float* pool_out, unsigned char* pool_idx, const int* valid_rows, void* workspace,
+                            size_t workspace_bytes, re2e_stream_t stream);
 
 /* 4x4 / stride-1 convolution as Winograd F(2x2,4x4) (csrc/wino44.hip; the discriminator's conv4, model/networks.py NLayerDiscriminator
  * `nn.Conv2d(ndf*4, ndf*8, kernel_size=4, stride=1, padding=1)`, and its data gradient): filter / input transform, ONE K-sliced launch

@@ -56,6 +56,7 @@ struct WinoArgs {
   unsigned in_bytes, u_bytes, out_bytes, pool_bytes;
   int total, ipw;                             // pipelined form: work items of the launch (per_image * NI) and consecutive items per workgroup
   const int* row_lim;                         // optional, per image: output rows >= row_lim[n] are not computed (patches that start there exit at once)
+  const int* valid_rows;                      // VALID instantiations, per image: image n IS an image of valid_rows[n] <= H rows inside its H-row slot (re2e_conv3x3_wino_valid)
 };
 
 // U[g][chunk][pos][nt][lane][e] = sum_{a,b} G[i][a] G[j][b] k[o][c][a][b],  pos = 4i + j, o = 64 g + 32 nt + (lane & 31),
@@ -107,7 +108,9 @@ __global__ void wino_weights_kernel(const float* __restrict__ w, int Cout, int C
 //   lane-dependent, so a lane keeps TWO read addresses per pixel (the two chunks of a plane); plane and buffer are instruction immediates:
 //   no address arithmetic in the loop.  Two halves are resident (2 x 24 KB, aliased with the epilogue's exchange buffer); half h + 2 is
 //   requested when the last chunk of half h has left LDS (one workgroup barrier per half).
-template <int TXW, bool LDSIN, bool C64 = false>      // TXW = tiles per patch row: 8 (16 x 8 pixel patch) or 4 (8 x 16); C64: LDSIN with exactly 64 input channels
+// VALID: every image has its own height (WinoArgs::valid_rows, re2e_conv3x3_wino_valid) -- instantiations of their own, so that the ones the
+// training step launches are, instruction for instruction, what they were without it -- one kernel-argument offset aside (profiles/wino_valid_ab.txt).
+template <int TXW, bool LDSIN, bool C64 = false, bool VALID = false>      // TXW = tiles per patch row: 8 (16 x 8 pixel patch) or 4 (8 x 16); C64: LDSIN with exactly 64 input channels
 __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
   static_assert(LDSIN || !C64, "C64 is a variant of the LDS-staged kernel");
   constexpr int TYH = 32 / TXW;
@@ -131,6 +134,11 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
     item = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
   }
   const int n = blockIdx.y;
+  // The height every RANGE test below uses (strides and allocation sizes stay those of p.H): the image's own number of rows where the caller
+  // gives one -- a scalar load, once per workgroup; rows beyond it are never read (they get the out-of-range offset, as rows beyond p.H do)
+  // and never written.  Clamped to [0, H]: whatever the device tensor holds, no offset leaves the image's slot.
+  int Hv = p.H;
+  if constexpr (VALID) { const int v = p.valid_rows[n]; Hv = v < 0 ? 0 : (v < p.H ? v : p.H); }
 
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, p.in_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.ufrag), 0, p.u_bytes, 0x00020000);
@@ -165,12 +173,12 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
   auto set_item = [&](const Geo& g) {
     u_s0 = (unsigned)(((g.nblk * nch) * 16 + 4 * wid) * 2) * 1024u;
     const int base = lane_base + g.y0 * rowb + g.x0 * colb;
-    if (g.y0 >= 1 && g.x0 >= 1 && g.y0 + PH + 1 <= p.H && g.x0 + PW + 1 <= p.W) {
+    if (g.y0 >= 1 && g.x0 >= 1 && g.y0 + PH + 1 <= Hv && g.x0 + PW + 1 <= p.W) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) a_off[k] = (unsigned)(base + (k < 4 ? ra : rb) * rowb + (k & 3) * colb);
     } else {
       const int iy0 = g.y0 - 1 + 2 * tyi, ix0 = g.x0 - 1 + 2 * txi;
-      const bool rok0 = (unsigned)(iy0 + ra) < (unsigned)p.H, rok1 = (unsigned)(iy0 + rb) < (unsigned)p.H;
+      const bool rok0 = (unsigned)(iy0 + ra) < (unsigned)Hv, rok1 = (unsigned)(iy0 + rb) < (unsigned)Hv;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const bool ok = (k < 4 ? rok0 : rok1) & ((unsigned)(ix0 + (k & 3)) < (unsigned)p.W);
@@ -189,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
   // (the first form of this set-up cost 0.85 vector instructions per MFMA: profiles/r06_conv1_2_wino_pmc_sq.json against r05).
   auto set_item_lds = [&](const Geo& g) {
     u_s0 = (unsigned)(((g.nblk * nch) * 16 + 4 * wid) * 2) * 1024u;
-    const bool interior = g.y0 >= 1 && g.x0 >= 1 && g.y0 + PH + 1 <= p.H && g.x0 + PW + 1 <= p.W;
+    const bool interior = g.y0 >= 1 && g.x0 >= 1 && g.y0 + PH + 1 <= Hv && g.x0 + PW + 1 <= p.W;
     int slot = wid * 16 + (lane >> 2);                              // < 64
     int py = slot / IPW, rem = slot - py * IPW;
     const int gr16 = (((lane & 3) - (slot >> 1)) & 3) * 16;         // LDS position lane & 3 of a slot holds granule (position - slot / 2) mod 4
@@ -197,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
     for (int i = 0; i < 3; ++i) {
       const int px = rem < IPW / 2 ? 2 * rem : 2 * (rem - IPW / 2) + 1;
       const int iy = g.y0 - 1 + py, ix = g.x0 - 1 + px;
-      const bool ok = slot < NPIX && (interior || ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W));
+      const bool ok = slot < NPIX && (interior || ((unsigned)iy < (unsigned)Hv && (unsigned)ix < (unsigned)p.W));
       st_off[i] = ok ? (unsigned)(iy * rowb + ix * colb + gr16) : WOOB;
 #ifdef RE2E_EXPERIMENTS
       // diagnostic (RE2E_WINO_DBG bit 128, timing only): every request instruction reads 1 KB CONTIGUOUS (wrong pixels)
@@ -272,6 +280,8 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
   Geo cur = geo_of(item);
   // ragged image batches (re2e_conv3x3_wino_rows): rows the caller never reads (beyond an utterance's end + the stack's reach) are left alone
   if (p.row_lim && cur.y0 >= p.row_lim[n]) return;
+  // a per-image height: patches that start at or beyond it have nothing to compute (a patch that straddles it drops its stores beyond it)
+  if constexpr (VALID) { if (cur.y0 >= Hv) return; }
   if constexpr (LDSIN) {
     // half 0 is requested first, the first weights behind it; "at most the 8 weight loads outstanding" = half 0 has landed (vmcnt retires in order)
     set_item_lds(cur);
@@ -464,12 +474,12 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
       const int ty2 = tl / TXW, tx2 = tl - ty2 * TXW;
       const int oy = y0 + 2 * ty2, ox = x0 + 2 * tx2;
       if (p.pool_out) {
-        o_off[it][0] = (oy < p.H && ox < p.W) ? (unsigned)((((n * PH2 + (oy >> 1)) * PW2 + (ox >> 1)) * p.Cout + n0 + c4) * 4) : WOOB;
+        o_off[it][0] = (oy < Hv && ox < p.W) ? (unsigned)((((n * PH2 + (oy >> 1)) * PW2 + (ox >> 1)) * p.Cout + n0 + c4) * 4) : WOOB;
       } else {
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
           const int y = oy + (d >> 1), x = ox + (d & 1);
-          o_off[it][d] = (y < p.H && x < p.W) ? (unsigned)((((n * p.H + y) * p.W + x) * p.Cout + n0 + c4) * 4) : WOOB;
+          o_off[it][d] = (y < Hv && x < p.W) ? (unsigned)((((n * p.H + y) * p.W + x) * p.Cout + n0 + c4) * 4) : WOOB;
           if (p.mask) mk[it][d] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsM, o_off[it][d], 0, 0));
         }
       }
@@ -505,7 +515,7 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
         int bi[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int d = 1; d < 4; ++d) {
-          if (oy + (d >> 1) < p.H && ox + (d & 1) < p.W) {
+          if (oy + (d >> 1) < Hv && ox + (d & 1) < p.W) {
             const f32x4 v = Y[d >> 1][d & 1];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -539,14 +549,14 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
 }
 
 
-template <int TXW, bool LDSIN, bool C64 = false>
+template <int TXW, bool LDSIN, bool C64 = false, bool VALID = false>
 void launch_wino(const WinoArgs& a, hipStream_t st) {
   size_t lds = (size_t)8 * 32 * LDR * sizeof(float);      // the exchange buffer (LDSIN: aliases the two staged halves, 2 x 24 KB)
   static const char* lds_env = exp_env("RE2E_WINO_LDS_KB");       // experiments: a larger request = one workgroup per CU (one wavefront per SIMD)
   if (lds_env && (size_t)atoi(lds_env) * 1024 > lds) lds = (size_t)atoi(lds_env) * 1024;
   static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&wino_conv3x3_kernel<TXW, LDSIN, C64>), lds);
-  hipLaunchKernelGGL((wino_conv3x3_kernel<TXW, LDSIN, C64>), dim3((unsigned)a.per_image, (unsigned)a.NI), dim3(256), lds, st, a);
+  lim.ensure(reinterpret_cast<const void*>(&wino_conv3x3_kernel<TXW, LDSIN, C64, VALID>), lds);
+  hipLaunchKernelGGL((wino_conv3x3_kernel<TXW, LDSIN, C64, VALID>), dim3((unsigned)a.per_image, (unsigned)a.NI), dim3(256), lds, st, a);
 }
 
 }  // namespace
@@ -579,8 +589,8 @@ int wino3x3_images(int N, int H, int W, int C, int Cout) {
 }
 
 static int wino_impl(const float* in, int NI, int H, int W, int C, const float* w, int Cout, int dgrad, const float* bias, int relu,
-                     const float* mask, float* out, float* pool_out, unsigned char* pool_idx, const int* row_lim, void* workspace,
-                     size_t workspace_bytes, hipStream_t stream) {
+                     const float* mask, float* out, float* pool_out, unsigned char* pool_idx, const int* row_lim, const int* valid_rows,
+                     void* workspace, size_t workspace_bytes, hipStream_t stream) {
   RE2E_CHECK_ARG(in && w && workspace && (out || pool_out), "null operand");
   RE2E_CHECK_ARG(NI > 0 && H > 0 && W > 0 && C > 0 && Cout > 0, "bad geometry");
   RE2E_CHECK_ARG(!pool_out || (pool_idx && relu && !mask && !dgrad), "pool_out needs pool_idx, relu = 1, no mask, forward direction");
@@ -603,6 +613,7 @@ static int wino_impl(const float* in, int NI, int H, int W, int C, const float* 
   a.in = in; a.ufrag = uf; a.out = out; a.bias = bias; a.mask = mask; a.pool_out = pool_out; a.pool_idx = pool_idx;
   a.NI = NI; a.H = H; a.W = W; a.C = C; a.Cout = Cout; a.relu = relu;
   a.row_lim = row_lim;
+  a.valid_rows = valid_rows;
   const int ngn = Cout / WNT;
   a.ngn_shift = 0;
   while ((1 << a.ngn_shift) < ngn) ++a.ngn_shift;
@@ -625,7 +636,12 @@ static int wino_impl(const float* in, int NI, int H, int W, int C, const float* 
   // build): the per-lane loads of rounds 3-5
   static const bool ldsin_env = !(exp_env("RE2E_WINO_LDSIN") && atoi(exp_env("RE2E_WINO_LDSIN")) == 0);
   const bool ldsin = ldsin_env && C % 64 == 0 && !a.stamps && !(a.dbg & ~(1 | 32 | 64 | 128));
-  if (ldsin && C == 64) { if (wide) launch_wino<8, true, true>(a, stream); else launch_wino<4, true, true>(a, stream); }
+  if (valid_rows) {
+    if (ldsin && C == 64) { if (wide) launch_wino<8, true, true, true>(a, stream); else launch_wino<4, true, true, true>(a, stream); }
+    else if (ldsin) { if (wide) launch_wino<8, true, false, true>(a, stream); else launch_wino<4, true, false, true>(a, stream); }
+    else { if (wide) launch_wino<8, false, false, true>(a, stream); else launch_wino<4, false, false, true>(a, stream); }
+  }
+  else if (ldsin && C == 64) { if (wide) launch_wino<8, true, true>(a, stream); else launch_wino<4, true, true>(a, stream); }
   else if (ldsin) { if (wide) launch_wino<8, true>(a, stream); else launch_wino<4, true>(a, stream); }
   else { if (wide) launch_wino<8, false>(a, stream); else launch_wino<4, false>(a, stream); }
   RE2E_LAUNCH_CHECK();
@@ -635,7 +651,7 @@ static int wino_impl(const float* in, int NI, int H, int W, int C, const float* 
 extern "C" int re2e_conv3x3_wino(const float* in, int NI, int H, int W, int C, const float* w, int Cout, int dgrad, const float* bias, int relu,
                                  const float* mask, float* out, float* pool_out, unsigned char* pool_idx, void* workspace,
                                  size_t workspace_bytes, hipStream_t stream) {
-  return wino_impl(in, NI, H, W, C, w, Cout, dgrad, bias, relu, mask, out, pool_out, pool_idx, nullptr, workspace, workspace_bytes, stream);
+  return wino_impl(in, NI, H, W, C, w, Cout, dgrad, bias, relu, mask, out, pool_out, pool_idx, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 // The same over a RAGGED image batch: output rows y >= row_lim[n] of image n (full-resolution rows, also with the fused pool) are not computed
@@ -647,7 +663,25 @@ extern "C" int re2e_conv3x3_wino_rows(const float* in, int NI, int H, int W, int
                                       const float* mask, float* out, float* pool_out, unsigned char* pool_idx, const int* row_lim, void* workspace,
                                       size_t workspace_bytes, hipStream_t stream) {
   RE2E_CHECK_ARG(row_lim, "null row limits");
-  return wino_impl(in, NI, H, W, C, w, Cout, dgrad, bias, relu, mask, out, pool_out, pool_idx, row_lim, workspace, workspace_bytes, stream);
+  return wino_impl(in, NI, H, W, C, w, Cout, dgrad, bias, relu, mask, out, pool_out, pool_idx, row_lim, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The forward over a PADDED image batch in which image n is an image of valid_rows[n] rows (1 <= valid_rows[n] <= H, int32 on the device) that
+// merely sits in a slot of H rows: input rows >= valid_rows[n] are never read -- they read as zero, as the rows beyond H do, whatever the memory
+// holds --, output rows < valid_rows[n] (pooled rows < ceil(valid_rows[n] / 2), a pooling window that straddles the end taking its maximum over
+// the rows inside) are those of re2e_conv3x3_wino on the cropped image alone, bit for bit (a tile's arithmetic depends neither on the patch it
+// lies in nor on the image height), and output rows beyond are left as they were.  A consumer given the same lengths never reads them, so a
+// stack of these layers needs no fill between them.  Inference: the training path keeps re2e_conv3x3_wino(_rows), which convolve the
+// zero-padded batch as the reference does (rows just beyond an utterance's end hold relu(bias + ...) there and the next layer reads them).
+extern "C" int re2e_conv3x3_wino_valid(const float* in, int NI, int H, int W, int C, const float* w, int Cout, int dgrad, const float* bias, int relu,
+                                       const float* mask, float* out, float* pool_out, unsigned char* pool_idx, const int* valid_rows, void* workspace,
+                                       size_t workspace_bytes, hipStream_t stream) {
+  RE2E_CHECK_ARG(valid_rows, "null valid heights");
+  if (dgrad || mask) {
+    re2e_set_error("re2e_conv3x3_wino_valid: forward direction only (dgrad = 0, no mask): gradients keep the unmasked stack of the reference");
+    return RE2E_EUNSUPPORTED;
+  }
+  return wino_impl(in, NI, H, W, C, w, Cout, 0, bias, relu, nullptr, out, pool_out, pool_idx, nullptr, valid_rows, workspace, workspace_bytes, stream);
 }
 
 namespace {

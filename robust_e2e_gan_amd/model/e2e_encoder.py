@@ -12,7 +12,7 @@ import torch
 from .. import ops
 from .. import lib
 from ..lib import Re2eError
-from .e2e_common import ConvParams, LinearParams, LSTMParams, _get_vgg2l_odim, lens_dev, lens_list
+from .e2e_common import ConvParams, LinearParams, LSTMParams, _get_vgg2l_odim, host_to_dev, lens_dev, lens_list
 
 FUSE_RELU_POOL_BWD = lib.exp_env('RE2E_NO_RELU_POOL_FUSION') is None      # A/B switches (ops.conv2d relu_bwd_in_pool / relu_bwd_in_next)
 FUSE_RELU_CONV_BWD = lib.exp_env('RE2E_NO_RELU_CONV_FUSION') is None
@@ -166,6 +166,44 @@ class VGG2L(torch.nn.Module):
     def pooled_lens(ilens):
         return [int(math.ceil(math.ceil(l / 2.0) / 2.0)) for l in lens_list(ilens)]
 
+    @staticmethod
+    def valid_heights(ilens):
+        """Per utterance, the image heights of a padded batch in which every utterance is convolved as an image of its OWN length
+        (``conv_stack_valid``) -> (rows of conv1_2's input and output, rows of conv2_1's and conv2_2's: behind the first ceil-mode pool,
+        pooled lengths: behind the second = ``pooled_lens``)."""
+        l1 = lens_list(ilens)
+        l2 = [(l + 1) // 2 for l in l1]
+        return l1, l2, [(l + 1) // 2 for l in l2]
+
+    def valid_stack_ok(self, B, T, Fd):
+        """Whether ``conv_stack_valid`` can take a (B, T, Fd) batch: one input channel and the fused Winograd kernels -- the only ones with a
+        per-image height -- named by the plans of conv1_2, conv2_1 and conv2_2 (with the pool inside the first and the last)."""
+        if self.in_channel != 1 or not FUSE_CONV_POOL:
+            return False
+        H2, F2 = (T + 1) // 2, (Fd + 1) // 2
+        for cv, H, Wd, pool in ((self.conv1_2, T, Fd, True), (self.conv2_1, H2, F2, False), (self.conv2_2, H2, F2, True)):
+            Cout, Cin = cv.weight.shape[0], cv.weight.shape[1]
+            flags = lib.CONV_BIAS | (lib.CONV_POOL if pool else 0) | (0 if cv.weight.is_contiguous() else lib.CONV_W_STRIDED)
+            if ops.conv_plan(lib.CONV_FWD, B, H, Wd, Cin, Cout, 3, 3, 1, 1, 0, 0, lib.ACT_RELU, flags)[0] != 'wino3x3':
+                return False
+        return True
+
+    def conv_stack_valid(self, xs, lens):
+        """``conv_stack`` for inference over a padded batch, utterance u convolved as an image of ``lens[u]`` rows: pooled rows below
+        ``pooled_lens`` are, bit for bit, those of ``conv_stack(xs[u:u+1, :lens[u]])``; the rows beyond are uninitialised (``pack_tm`` cuts
+        them).  ``xs`` must hold ZEROS in rows >= lens[u]: conv1_1 (one input channel, its own kernel) convolves the whole padded image, and
+        its rows < lens[u] read input rows <= lens[u]; what it writes beyond is never read, because conv1_2, conv2_1 and conv2_2 run
+        through re2e_conv3x3_wino_valid with the heights of ``valid_heights``.  ``conv_stack`` itself -- training -- keeps the reference's
+        arithmetic, which does NOT mask between the layers (e2e_encoder.py:259-266 convolve the zero-padded batch)."""
+        B, T, Fd = xs.shape
+        l1, l2, _ = self.valid_heights(lens)
+        v1, v2 = lens_dev(l1, xs.device), lens_dev(l2, xs.device)
+        h = xs.contiguous().view(B, T, Fd, 1)
+        h = ops.conv2d(h, self.conv1_1.weight, self.conv1_1.bias, 1, 1, 'relu', relu_bwd_in_next=FUSE_RELU_CONV_BWD)
+        h, _ = ops.conv3x3_wino(h, self.conv1_2.weight, 64, bias=self.conv1_2.bias, relu=True, pool=True, valid=v1)
+        h = ops.conv3x3_wino(h, self.conv2_1.weight, 128, bias=self.conv2_1.bias, relu=True, valid=v2)
+        return ops.conv3x3_wino(h, self.conv2_2.weight, 128, bias=self.conv2_2.bias, relu=True, pool=True, valid=v2)[0]
+
     def pack_tm(self, hs, ilens_per_branch):
         """pooled NHWC branches -> ONE time-major (T', sum B_k, 128*F') tensor with the cut + zero re-pad of :272-278."""
         nls = [self.pooled_lens(il) for il in ilens_per_branch]
@@ -222,3 +260,75 @@ class Encoder(torch.nn.Module):
     def forward(self, xs, ilens):
         y, lens = self.forward_tm(xs, ilens)
         return ops.transpose01(y), lens
+
+    def encode_batch(self, xs, ilens, group=None):
+        """Inference over a padded batch: ``xs`` (U, Tmax, idim), ``ilens`` its U lengths in any order -> ``(hpad (U, T'max, eprojs), hlens)``
+        with ``hpad[u, :hlens[u]]`` what ``self(xs[u:u+1, :ilens[u]], [ilens[u]])`` returns (rows beyond hlens[u] are padding: do not read
+        them).  Works on a device copy of ``xs`` with zeros written into the rows >= ilens[u] -- the caller's tensor is neither trusted
+        there nor written.  The VGG front end runs every utterance as an image of its own length (``VGG2L.conv_stack_valid``), the
+        recurrent stack its ragged path; where the plans do not name the Winograd kernels for the three 3x3 layers the utterances are
+        encoded one by one.  Large batches go in groups (``encode_groups``) of as many utterances as keep every activation inside one launch
+        of the Winograd kernels, or of at most ``group`` utterances where the caller bounds the memory further.  No gradients: call it under ``torch.no_grad()``."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise Re2eError('Encoder.encode_batch is inference only (the VGG stack masks between its convolutions there, which the training '
+                            'path must not): call it under torch.no_grad()')
+        lens = lens_list(ilens)
+        dev = next(self.parameters()).device
+        if xs.device != dev:
+            xs = xs.to(dev, non_blocking=True)
+        U, idim = xs.shape[0], xs.shape[2]
+        if len(lens) != U or min(lens) < 1 or max(lens) > xs.shape[1]:
+            raise Re2eError('encode_batch: %d utterances of at most %d frames, lengths %r' % (U, xs.shape[1], lens))
+        vgg = self.etype in ('vggblstm', 'vggblstmp')
+        Tmax = max(lens)
+        per = U
+        if vgg:
+            if not self.enc1.valid_stack_ok(U, Tmax, idim):
+                return self._encode_each(xs, lens)
+            H2, F2 = (Tmax + 1) // 2, (idim + 1) // 2
+            per = min(ops._wino_images(U, Tmax, idim, 64, 64), ops._wino_images(U, H2, F2, 64, 128), ops._wino_images(U, H2, F2, 128, 128))
+        if group is not None:
+            per = min(per, max(1, int(group)))
+        outs = []
+        for idx, T in encode_groups(lens, per):
+            gl = [lens[u] for u in idx]
+            # the copy: the group's utterances, cut at the group's longest, zeros beyond each one's end
+            x = xs[:, :T].index_select(0, host_to_dev(idx, xs.device, torch.int64))
+            x.masked_fill_((torch.arange(T, device=x.device)[None, :] >= lens_dev(gl, x.device)[:, None]).unsqueeze(2), 0.0)
+            if vgg:
+                h_tm, nl = self.enc1.pack_tm([self.enc1.conv_stack_valid(x, gl)], [gl])
+                nd = lens_dev(nl, x.device)
+                y_tm, nl = self.enc2.forward_tm(h_tm, nd, nl) if self.etype == 'vggblstmp' else (self.enc2.forward_tm(h_tm, nd), nl)
+            else:
+                y_tm, nl = self.forward_tm(x, gl)
+            outs.append((idx, ops.transpose01(y_tm), nl))
+        hlens = [0] * U
+        for idx, y, nl in outs:
+            for u, l in zip(idx, nl):
+                hlens[u] = l
+        hpad = outs[0][1].new_zeros((U, max(hlens), outs[0][1].shape[2]))
+        for idx, y, nl in outs:
+            hpad[:, :y.shape[1]].index_copy_(0, host_to_dev(idx, y.device, torch.int64), y)
+        return hpad, hlens
+
+    def _encode_each(self, xs, lens):
+        """``encode_batch`` one utterance at a time (each on its own frames alone)."""
+        ys = [self(xs[u:u + 1, :T], [T]) for u, T in enumerate(lens)]
+        hlens = [nl[0] for _, nl in ys]
+        hpad = ys[0][0].new_zeros((len(lens), max(hlens), ys[0][0].shape[2]))
+        for u, (y, _) in enumerate(ys):
+            hpad[u, :hlens[u]] = y[0, :hlens[u]]
+        return hpad, hlens
+
+
+def encode_groups(lens, per_group):
+    """Host side of ``Encoder.encode_batch``: the utterances in groups of at most ``per_group`` -> [(indices into ``lens``, frames of the
+    group's longest utterance)].  One group keeps the caller's order (no kernel on the way needs sorted lengths).  Several groups are cut
+    from the utterances sorted by length, longest first (ties in the caller's order), so that a group pads to ITS longest utterance and not
+    to the batch's; the results go back to the caller's positions through the indices."""
+    U = len(lens)
+    per_group = max(1, int(per_group))
+    if U <= per_group:
+        return [(list(range(U)), max(lens))]
+    order = sorted(range(U), key=lambda u: -lens[u])
+    return [(order[i:i + per_group], lens[order[i]]) for i in range(0, U, per_group)]

@@ -78,11 +78,16 @@ class E2E(ModelBase):
             if prev:
                 self.train()
 
-    def recognize_batch(self, xs, ilens, recog_args, char_list=None, rnnlm=None, fstlm=None):
-        """Beam search for U utterances at once: ``xs`` (U, Tmax, fbank_dim) zero-padded, ``ilens`` their U lengths -> a list of U n-best
-        lists, element u being what ``recognize(xs[u:u+1, :ilens[u]], ...)`` returns.  Every utterance is ENCODED on its own, exactly as
-        ``recognize`` encodes it (the VGG stack does not mask between its convolutions, so a padded batch is not known to reproduce the
-        single-utterance states at the last valid frames); the search then drives all of them together (Decoder.recognize_beam_batch)."""
+    def recognize_batch(self, xs, ilens, recog_args, char_list=None, rnnlm=None, fstlm=None, encode='batch'):
+        """Beam search for U utterances at once: ``xs`` (U, Tmax, fbank_dim) padded (what the padding holds does not matter), ``ilens``
+        their U lengths -> a list of U n-best lists, element u being what ``recognize(xs[u:u+1, :ilens[u]], ...)`` returns.  The
+        utterances are ENCODED as one padded batch (``Encoder.encode_batch``: the VGG stack convolves every utterance as an image of its
+        own length, so its states are those of the utterance alone, bit for bit; the recurrent layers run their ragged path over all of
+        them, one chain of T' steps per layer instead of U) and the CTC posteriors are taken once over the batch; the search then drives
+        all of them together (Decoder.recognize_beam_batch) on each utterance's own frames.  ``encode='each'`` encodes utterance by
+        utterance, exactly as ``recognize`` does (the arm tools/bench_recog_batch.py compares against; U = 1 always takes it)."""
+        if encode not in ('batch', 'each'):
+            raise Re2eError("recognize_batch: encode is 'batch' or 'each', not %r" % (encode,))
         prev = self.training
         self.eval()
         try:
@@ -90,7 +95,14 @@ class E2E(ModelBase):
                 lens = lens_list(ilens)
                 if len(lens) != xs.shape[0]:
                     raise Re2eError('recognize_batch: %d utterances but %d lengths' % (xs.shape[0], len(lens)))
-                hs, lpzs = [], ([] if recog_args.ctc_weight > 0.0 else None)
+                joint = recog_args.ctc_weight > 0.0
+                if encode == 'batch' and len(lens) > 1:
+                    hpad, hlens = self.enc.encode_batch(to_cuda(self, xs), lens)
+                    lpz = self.ctc.log_softmax(hpad) if joint else None
+                    hs = [hpad[u, :hlens[u]] for u in range(len(lens))]            # the padding rows stay behind
+                    lpzs = [lpz[u, :hlens[u]] for u in range(len(lens))] if joint else None
+                    return self.dec.recognize_beam_batch(hs, lpzs, recog_args, char_list, rnnlm, fstlm)
+                hs, lpzs = [], ([] if joint else None)
                 for u, T in enumerate(lens):
                     x = to_cuda(self, xs[u:u + 1, :T])
                     hpad, _ = self.enc(x, [x.shape[1]])

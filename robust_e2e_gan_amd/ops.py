@@ -748,11 +748,17 @@ def _note_row_limits(row_lim, H=0, W=0):
         sys.stderr.flush()
 
 
-def conv3x3_wino(x, W, Cout, dgrad=False, bias=None, relu=False, mask=None, pool=False, row_lim=None):
+def conv3x3_wino(x, W, Cout, dgrad=False, bias=None, relu=False, mask=None, pool=False, row_lim=None, valid=None):
     """re2e_conv3x3_wino on NHWC ``x`` with the layer's weight ``W`` in PyTorch layout: forward (dgrad=False: bias / ReLU / fused
     2x2 max pool -> (pooled, index bytes)) or data gradient (dgrad=True: ``x`` is dy; ``mask``: the ReLU output in front).  Tensors of
-    2 GiB or more run as several launches over slices of the image axis (same stream, same workspace: the launches are ordered)."""
+    2 GiB or more run as several launches over slices of the image axis (same stream, same workspace: the launches are ordered).
+    ``valid`` (int32 device tensor, one height per image, 1 <= valid[n] <= H; forward only, outside autograd): image n is an image of
+    valid[n] rows -- re2e_conv3x3_wino_valid: rows beyond are neither read nor written, the result's rows beyond are uninitialised."""
     N, H, Wd, C = x.shape
+    if valid is not None and (dgrad or mask is not None or row_lim is not None):
+        raise lib.Re2eError('conv3x3_wino(valid=...) is the forward of an inference stack: no dgrad, mask or row_lim')
+    if valid is not None and (valid.dtype != torch.int32 or valid.numel() != N or valid.device != x.device):
+        raise lib.Re2eError('conv3x3_wino(valid=...): one int32 height per image on the device of x')
     wsb = query('re2e_conv3x3_wino_workspace_bytes', C, Cout)
     ws = workspace(wsb, x.device, 'wino')
     nb = _wino_images(N, H, Wd, C, Cout)
@@ -765,6 +771,9 @@ def conv3x3_wino(x, W, Cout, dgrad=False, bias=None, relu=False, mask=None, pool
             if row_lim is not None:
                 call('re2e_conv3x3_wino_rows', x[i:i + n].data_ptr(), n, H, Wd, C, W.data_ptr(), Cout, 0, ptr(bias), 1, None, None,
                      yp[i:i + n].data_ptr(), idx[i:i + n].data_ptr(), row_lim.data_ptr() + 4 * i, ws.data_ptr(), wsb)
+            elif valid is not None:
+                call('re2e_conv3x3_wino_valid', x[i:i + n].data_ptr(), n, H, Wd, C, W.data_ptr(), Cout, 0, ptr(bias), 1, None, None,
+                     yp[i:i + n].data_ptr(), idx[i:i + n].data_ptr(), valid.data_ptr() + 4 * i, ws.data_ptr(), wsb)
             else:
                 call('re2e_conv3x3_wino', x[i:i + n].data_ptr(), n, H, Wd, C, W.data_ptr(), Cout, 0, ptr(bias), 1, None, None, yp[i:i + n].data_ptr(),
                      idx[i:i + n].data_ptr(), ws.data_ptr(), wsb)
@@ -775,6 +784,9 @@ def conv3x3_wino(x, W, Cout, dgrad=False, bias=None, relu=False, mask=None, pool
         if row_lim is not None:
             call('re2e_conv3x3_wino_rows', x[i:i + n].data_ptr(), n, H, Wd, C, W.data_ptr(), Cout, int(bool(dgrad)), ptr(bias), int(bool(relu)),
                  None if mask is None else mask[i:i + n].data_ptr(), y[i:i + n].data_ptr(), None, None, row_lim.data_ptr() + 4 * i, ws.data_ptr(), wsb)
+        elif valid is not None:
+            call('re2e_conv3x3_wino_valid', x[i:i + n].data_ptr(), n, H, Wd, C, W.data_ptr(), Cout, 0, ptr(bias), int(bool(relu)), None,
+                 y[i:i + n].data_ptr(), None, None, valid.data_ptr() + 4 * i, ws.data_ptr(), wsb)
         else:
             call('re2e_conv3x3_wino', x[i:i + n].data_ptr(), n, H, Wd, C, W.data_ptr(), Cout, int(bool(dgrad)), ptr(bias), int(bool(relu)),
                  None if mask is None else mask[i:i + n].data_ptr(), y[i:i + n].data_ptr(), None, None, ws.data_ptr(), wsb)
