@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 325
+#define RE2E_ABI_VERSION 326
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -569,6 +569,42 @@ int re2e_lm_log_softmax_combine(const float* logits, int n, int V, const float* 
 /* local[k][j] += lm_weight * lm[k][cand_dev[k][j]], k < n, j < ncand (e2e_decoder.py:284-285 on re2e_ctc_prefix_score's outputs);
  * a candidate outside [0, V) gives NaN. */
 int re2e_lm_add_cands(float* local, const float* lm, const int* cand_dev, int n, int ncand, int V, float lm_weight, re2e_stream_t stream);
+
+/* ---- Word-level LMs in the beam search (model/extlm.py; extlm.py:75-216 upstream; csrc/wordlm.hip) ----
+ * The lexical tree is flat int32 arrays on the device: N nodes, node 0 the root; wid[N] the word id of a word end or -1; lo[N], hi[N] the
+ * word-set range of the node as indices into a row of cumulative word probabilities (mass = c[hi] - c[lo]; lo < 0 marks the root: mass 1);
+ * child_off[N+1], child_label[nchild], child_node[nchild]: the children of node k are entries child_off[k] .. child_off[k+1]-1, labels
+ * ascending.  A row's node is in [-1, N): -1 = no path in the tree (open-vocabulary mode).  Few-row kernels (n = the live hypotheses of a
+ * position), no workspace; every output element is written.  at_space: 1 = the row's label was <space> (or the initial position), 0 = not,
+ * -1 = the row's label or node was out of range -- such a row is NaN in re2e_wlm_lookahead / re2e_wlm_multilevel_fix; an index read from
+ * the tree that falls outside its array gives NaN as well, never an out-of-range access.
+ * Per row r < n: labels[r] == space -> node_new = 0, word_in = wid[node_prev[r]] if that node is a word end, else word_unk, at_space = 1;
+ * otherwise node_new = the child of node_prev[r] with label labels[r], or -1 (also when node_prev[r] == -1), word_in = word_unk,
+ * at_space = 0.  A label outside [0, Vc) or a node outside [-1, N): node_new = -1, at_space = -1.  node_prev == NULL: every row at the root. */
+int re2e_wlm_transition(const int* node_prev, const int* labels, int n, int Vc, int space, int word_unk, const int* wid,
+                        const int* child_off, const int* child_label, const int* child_node, int N, int nchild, int* node_new,
+                        int* word_in, int* at_space, re2e_stream_t stream);
+/* cumsum[dst_rows[j]][v] = sum_{u <= v} softmax(logits[j])[u] for the m rows of logits (m, Vw) into a (n, Vw) buffer (dst_rows == NULL: row
+ * j; an entry outside [0, n) is skipped; other rows are left as they are).  One workgroup per row.  The probabilities are fp32
+ * (expf(x - max) / sum); all running sums are fp64, rounded to fp32 once at the store.  Any Vw. */
+int re2e_wlm_softmax_cumsum(const float* logits, int m, int Vw, const int* dst_rows, int n, float* cumsum, re2e_stream_t stream);
+/* LookAheadWordLM's label log-probabilities (extlm.py:195-216), log_y (n, Vc), from cumsum (n, Vw), the rows' nodes and at_space flags:
+ * y = unk_prob * oov_penalty by default, (c[hi] - c[lo]) / sum_prob for a child label, the word's own probability (times P(<eos>)) for
+ * <space> (<eos>) at a word end, 1e-10 for both right after a <space> elsewhere; log_y = log(y), each step one fp32 operation in that
+ * order.  Node -1: a row of zeros, or of -1e10 when open_vocab == 0. */
+int re2e_wlm_lookahead(const float* cumsum, int n, int Vw, const int* node, const int* at_space, const int* wid, const int* lo,
+                       const int* hi, const int* child_off, const int* child_label, const int* child_node, int N, int nchild, int Vc,
+                       int space, int eos, int word_unk, int word_eos, float oov_penalty, int open_vocab, float* log_y,
+                       re2e_stream_t stream);
+/* MultiLevelLM's tail (extlm.py:120-143): log_y (n, Vc) = subwordlm_weight * lsm (the character LM's log-softmax rows) with, for a row not
+ * at a <space>, log_y[space] = wlm_logprobs[wid of the node] - clm (word end) or wlm_logprobs[word_unk] + log_oov_penalty, log_y[eos] =
+ * that + wlm_logprobs[word_eos]; at a <space> both are -1e10.  clm_out (n) = 0 at a <space>, else clm_prev + log_y_prev[r][labels[r]].
+ * clm_prev, log_y_prev and labels all NULL: the initial position.  Node -1 with open_vocab == 0 and not at a <space>: a row of -1e10,
+ * clm_out = 0.  log_y must not alias lsm or log_y_prev. */
+int re2e_wlm_multilevel_fix(const float* lsm, const float* wlm_logprobs, int n, int Vw, const int* node, const int* at_space,
+                            const int* wid, int N, const float* clm_prev, const float* log_y_prev, const int* labels, int Vc,
+                            int space, int eos, int word_unk, int word_eos, float subwordlm_weight, float log_oov_penalty,
+                            int open_vocab, float* log_y, float* clm_out, re2e_stream_t stream);
 
 /* ---- N3 beam pruning on the device (csrc/beamsearch.hip), several utterances per launch.  The nh rows of a position are grouped by
  * utterance: utterance u owns rows seg_off_dev[u] .. seg_off_dev[u+1]-1 (U+1 offsets; max_seg_rows = the largest group, known to the host).

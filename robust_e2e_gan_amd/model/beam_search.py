@@ -21,6 +21,9 @@ in one ``predict`` call per position, its four state tensors (nh, n_units) stay 
 same ``parents`` gather as the decoder state.  Attention-only search ranks ``att + lm_weight * lm`` over all V labels; with CTC
 the candidates are chosen on the attention scores alone and ``lm_weight * lm[cand]`` is added to their local scores -- on the
 device-CTC path by re2e_lm_add_cands before the 3 x nh x ctc_beam copy, so the LM's (nh, V) rows never cross to the host there.
+The LM may also be a word-level one (model/extlm.py: LookAheadWordLM, MultiLevelLM over a lexical tree on the device): its state is a dict of
+per-row tensors like the RNNLM's and takes the same gather; it is handed the labels of the position as the host array they were uploaded from
+(``labels=``), so that it knows which rows stand at a <space> -- the only ones its word LM advances for -- without a device->host copy.
 
 Several utterances per search (``recognize_beam_batch``, E2E.recognize_batch): one loop over output positions drives all unfinished
 utterances.  The rows of a position are their live hypotheses, grouped by utterance; an utterance whose own ``end_detect`` fires, whose
@@ -142,7 +145,8 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
         ended = []
         for i in range(maxlen):
             nh = len(hyps)
-            ids = host_to_dev(np.asarray([hp['yseq'][i] for hp in hyps], np.int32), dev)
+            ids_h = np.asarray([hp['yseq'][i] for hp in hyps], np.int32)
+            ids = host_to_dev(ids_h, dev)
             emb = torch.empty(nh, Dd, device=dev)
             call('re2e_embedding_fwd', embed.data_ptr(), ids.data_ptr(), nh, Dd, emb.data_ptr(), Dd)
             w_new, cx = torch.empty(nh, T, device=dev), torch.empty(nh, E, device=dev)
@@ -162,7 +166,7 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
             if rnnlm is not None:
                 # att + lm_weight * lm over all V labels is what an attention-only search ranks (e2e_decoder.py:272,291); with CTC only the
                 # candidates' LM scores are used (:284-285)
-                lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if lpz is None else None, lm_weight)
+                lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if lpz is None else None, lm_weight, labels=ids_h)
             if dev_ctc:
                 last = host_to_dev(np.asarray([hp['yseq'][-1] for hp in hyps], np.int32), dev)
                 if max(len(hp['yseq']) - 1 for hp in hyps) > T:
@@ -346,7 +350,7 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
             ops.gemm(z_new, out_w, logits, nh, V, D, transb=True, bias=out_b)
             call('re2e_log_softmax_rows', logits.data_ptr(), nh, V, V, lsm.data_ptr())
             if rnnlm is not None:
-                lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if not joint else None, lm_weight)
+                lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if not joint else None, lm_weight, labels=meta[0])
             # the survivors: parent row, column, label, score (and their prefix scores), one int32 buffer -> one copy to the host
             surv = torch.empty(5 * nl * beam + nl, dtype=torch.int32, device=dev)
             part = [surv[k * nl * beam:(k + 1) * nl * beam] for k in range(5)]

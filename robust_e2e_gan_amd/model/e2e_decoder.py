@@ -107,30 +107,39 @@ class Decoder(torch.nn.Module):
         return loss, (acc if self.return_acc_tensor else float(acc))
 
     def _check_decode_lm(self, rnnlm, fstlm, device):
-        """What recognize_beam and recognize_beam_batch accept as a decode-time LM: an RNNLM under ClassifierWithState, shallow fusion only."""
+        """What recognize_beam and recognize_beam_batch accept as a decode-time LM: a ClassifierWithState over an RNNLM or over a word-level LM
+        of model/extlm.py (LookAheadWordLM, MultiLevelLM), shallow fusion only."""
         if fstlm is not None:
             raise Re2eError('decode-time LM: only RNNLM shallow fusion (rnnlm=ClassifierWithState(RNNLM(...))) is supported; '
                             'n-gram / FST LMs (fstlm) are out of scope')
         if rnnlm is not None:
+            from .extlm import LookAheadWordLM, MultiLevelLM
             from .lm import RNNLM, ClassifierWithState
             if self.fusion in ('deep_fusion', 'cold_fusion'):
                 raise Re2eError("decode-time LM: only shallow fusion is supported; fusion=%r changes the trained decoder and is out of scope"
                                 % self.fusion)
-            if not isinstance(rnnlm, ClassifierWithState) or not isinstance(rnnlm.predictor, RNNLM):
-                raise Re2eError('decode-time LM: only a ClassifierWithState over an RNNLM is supported (shallow fusion); word-level LMs '
-                                '(MultiLevelLM, LookAheadWordLM), the FS-RNN LM and %s are out of scope' % type(rnnlm).__name__)
-            if rnnlm.predictor.n_vocab != self.output.weight.shape[0]:
-                raise Re2eError('the RNNLM has %d labels, the decoder %d' % (rnnlm.predictor.n_vocab, self.output.weight.shape[0]))
-            if rnnlm.predictor.lo.weight.device != device:
-                raise Re2eError('the RNNLM is on %s, the encoder states on %s' % (rnnlm.predictor.lo.weight.device, device))
-            if rnnlm.training or rnnlm.predictor.training:
-                raise Re2eError('the RNNLM must be in evaluation mode (rnnlm.eval())')
+            if not isinstance(rnnlm, ClassifierWithState) or not isinstance(rnnlm.predictor, (RNNLM, LookAheadWordLM, MultiLevelLM)):
+                raise Re2eError('decode-time LM: only a ClassifierWithState over an RNNLM, a LookAheadWordLM or a MultiLevelLM is supported '
+                                '(shallow fusion); the FS-RNN LM, n-gram LMs and %s are out of scope' % type(rnnlm).__name__)
+            pred, V = rnnlm.predictor, self.output.weight.shape[0]
+            if isinstance(pred, RNNLM):
+                labels, lm_device, what = pred.n_vocab, pred.lo.weight.device, 'RNNLM'
+            else:
+                labels, lm_device, what = pred.subword_dict_size, pred.device, type(pred).__name__
+                if any(prm.device != lm_device for prm in pred.parameters()):
+                    raise Re2eError('the language models of the %s are on different devices' % what)
+            if labels != V:
+                raise Re2eError('the %s has %d labels, the decoder %d' % (what, labels, V))
+            if lm_device != device:
+                raise Re2eError('the %s is on %s, the encoder states on %s' % (what, lm_device, device))
+            if rnnlm.training or any(mod.training for mod in pred.modules()):
+                raise Re2eError('the %s must be in evaluation mode (rnnlm.eval())' % what)
 
     def recognize_beam(self, h, lpz, recog_args, char_list=None, rnnlm=None, fstlm=None):
         """e2e_decoder.py:171-369: n-best list of {'yseq', 'score'} for the encoder states ``h`` (T', eprojs) of one
         utterance; ``lpz`` = CTC log posteriors (T', V) or None.  All live hypotheses are advanced as one GPU batch.
-        ``rnnlm``: a model.lm.ClassifierWithState over an RNNLM for shallow fusion with weight ``recog_args.lm_weight``
-        (:270-272,284-285); no other LM is supported."""
+        ``rnnlm``: a model.lm.ClassifierWithState over an RNNLM, or over a word-level LM of model/extlm.py, for shallow fusion with weight
+        ``recog_args.lm_weight`` (:270-272,284-285); no other LM is supported."""
         self._check_decode_lm(rnnlm, fstlm, h.device)
         from .beam_search import recognize_beam
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}

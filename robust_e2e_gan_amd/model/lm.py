@@ -11,8 +11,11 @@ weights through registers once.  ``COMPOSED_PATH`` swaps in the same arithmetic 
 (re2e_embedding_fwd, re2e_gemm x 5, re2e_lstm_cell_fwd x 2, re2e_log_softmax_rows): the tests' arbiter and the timing baseline
 (tools/bench_recog_lm.py), not a user option.
 
-Out of scope: training the LM (lm_train.py, lm.train, the loss of ClassifierWithState.forward), the FS-RNN LM, n-gram / FST and
-word-level LMs (MultiLevelLM, LookAheadWordLM), deep and cold fusion."""
+Word-level LMs (LookAheadWordLM, MultiLevelLM: model/extlm.py here) are predictors over one or two RNNLMs; they return log-probabilities
+(``normalized``) and take the labels the search holds on the host (``host_labels``, the ``labels=`` of ``predict_combined``).
+
+Out of scope: training the LM (lm_train.py, lm.train, the loss of ClassifierWithState.forward), the FS-RNN LM, n-gram / FST LMs
+(NgramCharacterKenLM), deep and cold fusion."""
 import numpy as np
 import torch
 
@@ -127,16 +130,20 @@ class ClassifierWithState(torch.nn.Module):
     def forward(self, state, *args, **kwargs):
         raise Re2eError('ClassifierWithState.forward is the LM training loss (lm_train.py): out of scope, use predict()')
 
-    def predict(self, state, x):
-        state, lp, _ = self.predict_combined(state, x)
+    def predict(self, state, x, labels=None):
+        state, lp, _ = self.predict_combined(state, x, labels=labels)
         return state, lp
 
-    def predict_combined(self, state, x, att=None, lm_weight=0.0):
+    def predict_combined(self, state, x, att=None, lm_weight=0.0, labels=None):
         """``predict`` plus, when ``att`` (n, V) is given, ``att + lm_weight * log_probs`` (the shallow-fusion score of
-        e2e_decoder.py:272, product and sum each rounded to fp32) from the same pass over the rows: (state, log_probs, combined)."""
-        state, z = self.predictor(state, x)
+        e2e_decoder.py:272, product and sum each rounded to fp32) from the same pass over the rows: (state, log_probs, combined).
+        ``labels``: the labels of ``x`` as a host array, for the predictors that branch on them (``host_labels``: model/extlm.py)."""
+        if labels is not None and getattr(self.predictor, 'host_labels', False):
+            state, z = self.predictor(state, x, labels=labels)
+        else:
+            state, z = self.predictor(state, x)
         if getattr(self.predictor, 'normalized', False):
-            return state, z, (att + np.float32(lm_weight) * z if att is not None else None)
+            return state, z, (att + float(np.float32(lm_weight)) * z if att is not None else None)
         n, V = z.shape
         lp = _empty(n, V, device=z.device)
         if COMPOSED_PATH or not isinstance(self.predictor, RNNLM):
