@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 326
+#define RE2E_ABI_VERSION 327
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -627,6 +627,28 @@ int re2e_adadelta_step(float* p, const float* g, float* sq_avg, float* acc_delta
                        float lr, const float* stats_dev, re2e_stream_t stream);
 int re2e_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                    float eps, int step, const float* stats_dev, re2e_stream_t stream);
+/* p -= lr * stats[1] * g (plain SGD on the clipped gradient: lm_train.py); skipped entirely when stats[2]==0.  stats_dev NULL: coefficient 1. */
+int re2e_sgd_step(float* p, const float* g, long n, float lr, const float* stats_dev, re2e_stream_t stream);
+
+/* ---- L1 unidirectional LSTM over one truncated-BPTT window (csrc/lmseq.hip): the recurrence of RNNLM training (lm_train.py).  Time-major.
+ * gates (T,B,4H) holds x W_ih^T + b_ih + b_hh (gate order i,f,g,o) on entry and the ACTIVATED gates on exit of re2e_lmseq_fwd;
+ * re2e_lmseq_bwd overwrites them with d(pre-activation gates).  hbuf / cbuf are (T+1,B,H): block 0 is the initial state, written by the
+ * caller and left untouched (the convention of re2e_dec_loop_fwd), block t+1 the state after step t.  dy (T,B,H): the gradient of every h[t];
+ * dh_last / dc_last (B,H), optional (NULL = zeros): the gradient flowing in through the final state; dh0 / dc0 (B,H), optional outputs: the
+ * gradient flowing out through the initial state.  Any H >= 1 and B >= 1; no alignment beyond 4 bytes is assumed of any operand; gates must
+ * stay below 2^31 elements.  One launch per time step on `stream` (+ one for dh0), fp32 MFMA: every product is one k-ordered fmaf chain
+ * that starts from the value it is added to.  workspace: re2e_lmseq_workspace_bytes(B, H) (the dc carry; the forward needs none). */
+size_t re2e_lmseq_workspace_bytes(int B, int H);
+int re2e_lmseq_fwd(float* gates, const float* w_hh, float* hbuf, float* cbuf, int T, int B, int H,
+                   void* workspace, size_t workspace_bytes, re2e_stream_t stream);
+int re2e_lmseq_bwd(float* gates, const float* w_hh, const float* dy, const float* dh_last, const float* dc_last,
+                   const float* cbuf, float* dh0, float* dc0, int T, int B, int H,
+                   void* workspace, size_t workspace_bytes, re2e_stream_t stream);
+/* The form re2e_lmseq_fwd (backward == 0) / re2e_lmseq_bwd runs this window with, as one line of space-separated key=value pairs in `out`;
+ * nothing is launched.   family=fwd_step|bwd_step mfma=16x16x4 rows=.. units=.. acc=.. kc=.. grid=XxYx1 lds=.. launches=.. rounds=..
+ * (rows x units: the workgroup's tile; acc: independent accumulators per wave; launches: one per step; rounds: workgroups per CU).
+ * cus > 0: plan for a chip of that many CUs (no device is touched); cus == 0: the current device's count. */
+int re2e_lmseq_plan(int T, int B, int H, int backward, int cus, char* out, size_t out_bytes);
 
 #ifdef __cplusplus
 }

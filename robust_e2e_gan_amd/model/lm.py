@@ -1,6 +1,6 @@
-"""Recurrent language model for decoding (mirror of RNNLM / ClassifierWithState, model/lm.py:26-146), decode side only.
+"""Recurrent language model (mirror of RNNLM / ClassifierWithState / train, model/lm.py:26-340): decoding and training.
 
-Shallow fusion in the beam search (Decoder.recognize_beam(..., rnnlm=...)) asks the LM for the log-probabilities of the next
+Decoding.  Shallow fusion in the beam search (Decoder.recognize_beam(..., rnnlm=...)) asks the LM for the log-probabilities of the next
 label after every live hypothesis.  Unlike upstream -- one hypothesis per ``predict`` call -- all ``n`` live hypotheses of a
 position go through ONE call: ``x`` holds their last labels, the state tensors are (n, n_units) and stay on the GPU.
 
@@ -14,8 +14,21 @@ weights through registers once.  ``COMPOSED_PATH`` swaps in the same arithmetic 
 Word-level LMs (LookAheadWordLM, MultiLevelLM: model/extlm.py here) are predictors over one or two RNNLMs; they return log-probabilities
 (``normalized``) and take the labels the search holds on the host (``host_labels``, the ``labels=`` of ``predict_combined``).
 
-Out of scope: training the LM (lm_train.py, lm.train, the loss of ClassifierWithState.forward), the FS-RNN LM, n-gram / FST LMs
-(NgramCharacterKenLM), deep and cold fusion."""
+Training (lm_train.py, ``train`` / ``evaluate`` below).  A truncated-BPTT window of T steps x B rows runs as ONE pass,
+``RNNLM.forward_seq``: embedding -> dropout -> the W_ih product of all T*B rows (both biases in its epilogue) -> the recurrence
+(ops.lm_lstm_seq: csrc/lmseq.hip, one fused product + cell launch per step, state carried in and out with its gradient) -> dropout ->
+layer 2 -> dropout -> output layer; the three dropouts are three counter-based masks over the whole (T, B, .) tensors (ops.dropout), not
+torch's RNG stream.  ``RNNLM.forward`` in training mode is that window with T = 1, so the reference's per-step loop (sum 35 losses,
+backward, detach) works and chains through the state's gradient; ``ClassifierWithState.forward_seq`` is the trainer's path.  The output
+layer, the cross-entropy and their backward run over row blocks when T*B*V would pass ``OUTPUT_MAX_ELEMS`` (the kernels address their
+operands with 32-bit element offsets).  In training ``COMPOSED_PATH`` means the same window with re2e_gemm + re2e_lstm_cell_fwd / _bwd
+per step as its recurrence (tools/bench_lm_train.py).
+
+Out of scope (refused with Re2eError where they can be asked for): the FS-RNN LM (--lm-type fsrnnlm), training on several GPUs or on the
+CPU, n-gram / FST LMs (NgramCharacterKenLM), deep and cold fusion."""
+import logging
+import os
+
 import numpy as np
 import torch
 
@@ -26,6 +39,7 @@ from .e2e_decoder import EmbeddingParams, LSTMCellParams
 
 COMPOSED_PATH = False          # tests / tools: the step over the general entry points instead of csrc/rnnlm.hip (arbiter, timing baseline)
 FUSED_MAX_ROWS = 64            # re2e_lm_*: 1 <= n <= 64; more rows take the composed path
+OUTPUT_MAX_ELEMS = 2 ** 31 - 1  # training: logits per output-layer / cross-entropy call (32-bit element offsets); more rows go in blocks
 
 STATE_KEYS = ('c1', 'h1', 'c2', 'h2')
 
@@ -72,11 +86,12 @@ class RNNLM(torch.nn.Module):
 
     def forward(self, state, x):
         """``x``: the n last labels; ``state``: {'c1', 'h1', 'c2', 'h2'} of (n, n_units) each or None (zeros) -> (state, logits (n, V))."""
-        if self.training:
-            raise Re2eError('RNNLM runs in evaluation mode only (call .eval()): training the LM is out of scope')
         if not self.lo.weight.is_cuda:
             raise Re2eError('RNNLM parameters are on %s: there is no CPU path (call .cuda())' % self.lo.weight.device)
         ids = self._ids(x)
+        if self.training:
+            state, logits = self.forward_seq(state, ids.view(1, -1))
+            return state, logits[0]
         n = ids.numel()
         if n < 1:
             raise Re2eError('RNNLM.forward needs at least one label')
@@ -85,6 +100,36 @@ class RNNLM(torch.nn.Module):
             if COMPOSED_PATH or n > FUSED_MAX_ROWS:
                 return self._forward_composed(st, ids, n)
             return self._forward_fused(st, ids, n)
+
+    def window(self, state, xs):
+        """One truncated-BPTT window up to the output layer: ``xs`` (T, B) labels -> (state, hidden (T*B, n_units) after the last
+        dropout).  ``state`` carries autograd history: detach it between windows (the trainer does)."""
+        if not self.lo.weight.is_cuda:
+            raise Re2eError('RNNLM parameters are on %s: there is no CPU path (call .cuda())' % self.lo.weight.device)
+        if not hasattr(xs, 'shape') or len(xs.shape) != 2 or xs.shape[0] < 1 or xs.shape[1] < 1:
+            raise Re2eError('RNNLM.forward_seq takes labels of shape (T, B)')
+        T, B = int(xs.shape[0]), int(xs.shape[1])
+        ids = self._ids(xs)
+        st = self._state(state, B)
+        if st is None:
+            st = (self.zero_state(B),) * 4
+        c1, h1, c2, h2 = st
+        p = self.dropout_rate if self.training else 0.0
+        H = self.n_units
+        x = ops.dropout(ops.embedding(self.embed.weight, ids), p)
+        xg = ops.linear_2bias(x, self.l1.weight_ih, self.l1.bias_ih, self.l1.bias_hh)
+        y1, h1, c1 = ops.lm_lstm_seq(xg.view(T, B, 4 * H), self.l1.weight_hh, h1, c1, composed=COMPOSED_PATH)
+        x = ops.dropout(y1.reshape(T * B, H), p)
+        xg = ops.linear_2bias(x, self.l2.weight_ih, self.l2.bias_ih, self.l2.bias_hh)
+        y2, h2, c2 = ops.lm_lstm_seq(xg.view(T, B, 4 * H), self.l2.weight_hh, h2, c2, composed=COMPOSED_PATH)
+        x = ops.dropout(y2.reshape(T * B, H), p)
+        return {'c1': c1, 'h1': h1, 'c2': c2, 'h2': h2}, x
+
+    def forward_seq(self, state, xs):
+        """``xs`` (T, B) labels, ``state`` as in ``forward`` -> (state after the window, logits (T, B, V)), differentiable."""
+        state, hid = self.window(state, xs)
+        T, B = int(xs.shape[0]), int(xs.shape[1])
+        return state, ops.linear(hid, self.lo.weight, self.lo.bias).view(T, B, self.n_vocab)
 
     def _forward_fused(self, st, ids, n):
         dev, V, I, H = ids.device, self.n_vocab, self.input_units, self.n_units
@@ -116,8 +161,10 @@ class RNNLM(torch.nn.Module):
 
 
 class ClassifierWithState(torch.nn.Module):
-    """lm.py:26-109, decode side: ``predict(state, x) -> (state, log_probs (n, V))``.  Its parameters are ``predictor.*``, so a
-    checkpoint the reference wrote loads with a strict ``load_state_dict``.  The training loss (``forward``) is out of scope."""
+    """lm.py:26-109: ``predict(state, x) -> (state, log_probs (n, V))`` for decoding, ``forward(state, x, t) -> (state, loss)`` and
+    ``forward_seq(state, xs, ts)`` for training.  Its parameters are ``predictor.*``, so a checkpoint the reference wrote loads with a
+    strict ``load_state_dict`` and the other way round."""
+    compute_accuracy = True
 
     def __init__(self, predictor, lossfun=None, accfun=None, label_key=-1):
         if not isinstance(label_key, (int, str)):
@@ -127,8 +174,62 @@ class ClassifierWithState(torch.nn.Module):
         self.y, self.loss, self.accuracy = None, None, None
         self.predictor = predictor
 
+    def _labels(self, t, dev):
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            return t.to(device=dev, dtype=torch.int32).contiguous().view(-1)
+        return host_to_dev(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, np.int32).reshape(-1), dev)
+
     def forward(self, state, *args, **kwargs):
-        raise Re2eError('ClassifierWithState.forward is the LM training loss (lm_train.py): out of scope, use predict()')
+        """The reference's contract: the argument at ``label_key`` is the labels, the others go to the predictor -> (state, loss), loss
+        = mean cross-entropy over the rows (0-dim); sets ``y``, ``loss`` and, with ``compute_accuracy``, ``accuracy``."""
+        if isinstance(self.label_key, int):
+            if not (-len(args) <= self.label_key < len(args)):
+                raise ValueError('Label key %d is out of bounds' % self.label_key)
+            t = args[self.label_key]
+            args = args[:-1] if self.label_key == -1 else args[:self.label_key] + args[self.label_key + 1:]
+        else:
+            if self.label_key not in kwargs:
+                raise ValueError('Label key "%s" is not found' % self.label_key)
+            t = kwargs.pop(self.label_key)
+        self.y, self.loss, self.accuracy = None, None, None
+        state, self.y = self.predictor(state, *args, **kwargs)
+        if self.lossfun is not None:
+            self.loss = self.lossfun(self.y, t)
+            if self.compute_accuracy and self.accfun is not None:
+                self.accuracy = self.accfun(self.y, t)
+            return state, self.loss
+        loss, stats = ops.cross_entropy(self.y, self._labels(t, self.y.device))
+        self.loss = loss.reshape(())
+        if self.compute_accuracy:
+            self.accuracy = stats[1] / stats[2]
+        return state, self.loss
+
+    def forward_seq(self, state, xs, ts):
+        """One window: ``xs``, ``ts`` (T, B) labels and targets -> (state, sum over t of the mean cross-entropy of step t), what the
+        reference's loop over T ``forward`` calls sums up.  The output layer and the loss run over blocks of whole rows when T*B*V
+        would pass OUTPUT_MAX_ELEMS; a block of R rows contributes its mean x R / B, so the total is the same sum over rows / B."""
+        rnn = self.predictor
+        state, hid = rnn.window(state, xs)
+        T, B = int(xs.shape[0]), int(xs.shape[1])
+        V, rows = rnn.n_vocab, T * B
+        tgt = self._labels(ts, hid.device)
+        if tgt.numel() != rows:
+            raise Re2eError('forward_seq: %d targets for %d x %d labels' % (tgt.numel(), T, B))
+        self.y, self.loss, self.accuracy = None, None, None
+        block = rows if rows * V <= OUTPUT_MAX_ELEMS else max(1, OUTPUT_MAX_ELEMS // V)
+        total, correct = None, None
+        for r0 in range(0, rows, block):
+            r1 = min(rows, r0 + block)
+            logits = ops.linear(hid[r0:r1], rnn.lo.weight, rnn.lo.bias)
+            loss, stats = ops.cross_entropy(logits, tgt[r0:r1], scale=(r1 - r0) / float(B))
+            total = loss if total is None else total + loss
+            correct = stats[1] if correct is None else correct + stats[1]
+            if block == rows:
+                self.y = logits.view(T, B, V)
+        self.loss = total.reshape(())
+        if self.compute_accuracy:
+            self.accuracy = correct / rows
+        return state, self.loss
 
     def predict(self, state, x, labels=None):
         state, lp, _ = self.predict_combined(state, x, labels=labels)
@@ -152,3 +253,115 @@ class ClassifierWithState(torch.nn.Module):
         comb = _empty(n, V, device=z.device) if att is not None else None
         call('re2e_lm_log_softmax_combine', z.data_ptr(), n, V, ptr(att), float(np.float32(lm_weight)), lp.data_ptr(), ptr(comb))
         return state, lp, comb
+
+
+# ---- training (lm.py:148-340, lm_train.py) -----------------------------------------------------------------------------------------------------
+def evaluate(model, iter, bproplen=100):
+    """Perplexity exp(sum of the per-step losses / steps) over one pass of a ``repeat=False`` iterator, in evaluation mode and without
+    gradients, step by step as the reference does (lm.py:240-272); leaves the predictor in training mode."""
+    rnn = model.predictor
+    rnn.eval()
+    state, total, count = None, None, 0
+    with torch.no_grad():
+        while True:
+            try:
+                batch = np.asarray(iter.__next__(), np.int32)
+            except StopIteration:
+                break
+            state, loss = model(state, batch[:, 0], batch[:, 1])
+            total = loss if total is None else total + loss
+            if count % bproplen == 0:
+                state = {k: v.detach() for k, v in state.items()}
+            count += 1
+    rnn.train()
+    return float(np.exp(float(total) / count))
+
+
+def _read_ids(path, char_list_dict):
+    with open(path, 'rb') as f:
+        return np.array([char_list_dict[c] if c in char_list_dict else char_list_dict['<unk>'] for c in f.readline().decode('utf-8').split()], dtype=np.int32)
+
+
+def _embed_vecs(path, n_vocab, char_list_dict):
+    word_dim = 0
+    with open(path, 'r', encoding='utf-8') as fid:
+        for line in fid:
+            word_dim = len(line.strip().split()[1:])
+            break
+    vecs = np.array(np.random.uniform(low=-0.05, high=0.05, size=(n_vocab, word_dim)), dtype=np.float32)
+    with open(path, 'r', encoding='utf-8') as fid:
+        for line in fid:
+            parts = line.strip().split()
+            if parts and parts[0] in char_list_dict and len(parts) == word_dim + 1:
+                vecs[char_list_dict[parts[0]]] = np.array([float(v) for v in parts[1:]], dtype=np.float32)
+    return vecs
+
+
+def train(args):
+    """The reference's training loop (lm.py:148-340) over whole windows: every iteration takes ``bproplen`` steps of the training
+    iterator as one (T, B) window, sums the per-step losses (forward_seq), back-propagates, detaches the state, clips at ``gradclip``
+    and takes an SGD step of lr 1.0; training perplexity every 100 iterations; at each epoch boundary the validation perplexity,
+    rnnlm.model.<epoch>, rnnlm.state.<epoch> and the rnnlm.model.best link.  Returns the last validation perplexity (None: no epoch ended)."""
+    from ..data.lm_data_loader import ParallelSequentialIterator
+    from ..optim import FlatOptimizer
+    if args.lm_type != 'rnnlm':
+        raise Re2eError('--lm-type %s: only rnnlm is trained here (the FS-RNN LM is out of scope)' % args.lm_type)
+    if args.ngpu > 1:
+        raise Re2eError('--ngpu %d: the LM trains on one GPU' % args.ngpu)
+    if args.ngpu < 1 or not torch.cuda.is_available():
+        raise Re2eError('the LM trains on the GPU only (--ngpu 1): there is no CPU path')
+    torch.manual_seed(args.seed)
+    ops.dropout_seed(args.seed)
+    train_ids = _read_ids(args.train_label, args.char_list_dict)
+    valid_ids = _read_ids(args.valid_label, args.char_list_dict)
+    logging.info('vocabulary: %d', args.n_vocab)
+    logging.info('training tokens: %d', len(train_ids))
+    logging.info('validation tokens: %d', len(valid_ids))
+    logging.info('windows per epoch: %d', len(train_ids) // (args.batchsize * args.bproplen))
+    train_iter = ParallelSequentialIterator(train_ids, args.batchsize)
+    valid_iter = ParallelSequentialIterator(valid_ids, args.batchsize, repeat=False)
+    embed_vecs_init = None
+    if getattr(args, 'embed_init_file', None):
+        embed_vecs_init = _embed_vecs(args.embed_init_file, args.n_vocab, args.char_list_dict)
+        args.input_unit = embed_vecs_init.shape[1]
+    model = ClassifierWithState(RNNLM(args.n_vocab, args.input_unit, args.unit, args.dropout_rate, embed_vecs_init))
+    model.compute_accuracy = False          # only the perplexity is wanted
+    path = os.path.join(args.outdir, 'rnnlm.model.best')
+    resumed = os.path.isfile(path)
+    if resumed:
+        model.load_state_dict(torch.load(path, map_location='cpu'))
+        logging.info('resuming from %s', path)
+    model.cuda(0)
+    model.train()
+    optimizer = FlatOptimizer(model.parameters(), kind='sgd', lr=1.0)
+    best_valid = evaluate(model, valid_iter) if resumed else 100000000
+    sum_perp, count, iteration, epoch_now, state, valid_perp = 0.0, 0, 0, 0, None, None
+    while train_iter.epoch < args.epoch:
+        iteration += 1
+        xs, ts = train_iter.next_window(args.bproplen)
+        state, loss = model.forward_seq(state, xs, ts)
+        count += args.bproplen
+        optimizer.zero_grad()
+        loss.backward()
+        state = {k: v.detach() for k, v in state.items()}
+        optimizer.clip_grad_norm(args.gradclip)
+        optimizer.step()
+        sum_perp = loss.detach() + sum_perp          # stays on the device: read every 100 iterations
+        if iteration % 100 == 0:
+            logging.info('iteration %d: training perplexity %.4f', iteration, np.exp(float(sum_perp) / count))
+            sum_perp, count = 0.0, 0
+        if train_iter.epoch > epoch_now:
+            valid_perp = evaluate(model, valid_iter)
+            logging.info('epoch %d: validation perplexity %.4f', train_iter.epoch, valid_perp)
+            torch.save({k: v.detach().cpu().clone() for k, v in model.state_dict().items()}, os.path.join(args.outdir, 'rnnlm.model.' + str(epoch_now)))
+            torch.save({'state': {}, 'param_groups': [dict(lr=optimizer.param_groups[0]['lr'], momentum=0, dampening=0, weight_decay=0, nesterov=False,
+                                                            params=list(range(len(optimizer.params))))]},
+                       os.path.join(args.outdir, 'rnnlm.state.' + str(epoch_now)))
+            if valid_perp < best_valid:
+                dest = os.path.join(args.outdir, 'rnnlm.model.best')
+                if os.path.lexists(dest):
+                    os.remove(dest)
+                os.symlink('rnnlm.model.' + str(epoch_now), dest)
+                best_valid = valid_perp
+            epoch_now = train_iter.epoch
+    return valid_perp

@@ -2008,3 +2008,153 @@ class MaskRowsFn(torch.autograd.Function):
 
 
 mask_rows = MaskRowsFn.apply
+
+
+# ---------------------------------------------------------------------------------------------
+# L1 unidirectional LSTM over one truncated-BPTT window (RNNLM training, csrc/lmseq.hip)
+# ---------------------------------------------------------------------------------------------
+class LmSeqFn(torch.autograd.Function):
+    """xg (T,B,4H) = x W_ih^T + b_ih + b_hh, w_hh (4H,H), h0 / c0 (B,H) -> (h_all (T,B,H), h_T, c_T), with gradients for xg, h0 and c0
+    returned and w_hh's accumulated into ``w_hh.grad`` as ONE dgates^T hbuf[0:T] product over all T*B rows.  ``composed``: the same
+    window over re2e_gemm + re2e_lstm_cell_fwd / _bwd per step (the arbiter and timing baseline of model/lm.py COMPOSED_PATH).  The
+    backward overwrites the saved gates: one backward per forward."""
+
+    @staticmethod
+    def forward(ctx, xg, w_hh, h0, c0, composed):
+        _need_gpu(xg)
+        T, B, H4 = xg.shape
+        H = H4 // 4
+        if tuple(w_hh.shape) != (H4, H) or tuple(h0.shape) != (B, H) or tuple(c0.shape) != (B, H) or not w_hh.is_contiguous():
+            raise lib.Re2eError('lm_lstm_seq: xg %s, w_hh %s, h0 %s, c0 %s do not fit together' % (tuple(xg.shape), tuple(w_hh.shape), tuple(h0.shape), tuple(c0.shape)))
+        gates = _f32(xg).clone()
+        hbuf, cbuf = empty((T + 1, B, H), xg), empty((T + 1, B, H), xg)
+        hbuf[0].copy_(h0)
+        cbuf[0].copy_(c0)
+        if composed:
+            for t in range(T):
+                gemm(hbuf[t], w_hh, gates[t], B, H4, H, transb=True, beta=1.0)
+                call('re2e_lstm_cell_fwd', gates[t].data_ptr(), cbuf[t].data_ptr(), cbuf[t + 1].data_ptr(), hbuf[t + 1].data_ptr(), B, H)
+        else:
+            call('re2e_lmseq_fwd', gates.data_ptr(), w_hh.data_ptr(), hbuf.data_ptr(), cbuf.data_ptr(), T, B, H, None, 0)
+        ctx.save_for_backward(gates, hbuf, cbuf)
+        ctx.w_hh, ctx.composed = w_hh, composed
+        return hbuf[1:], hbuf[T].clone(), cbuf[T].clone()
+
+    @staticmethod
+    def backward(ctx, d_all, d_hT, d_cT):
+        gates, hbuf, cbuf = ctx.saved_tensors
+        w_hh = ctx.w_hh
+        T, B, H4 = gates.shape
+        H = H4 // 4
+        dy = _f32(d_all) if d_all is not None else zeros((T, B, H), gates)
+        d_hT = _f32(d_hT) if d_hT is not None else None
+        d_cT = _f32(d_cT) if d_cT is not None else None
+        need_h0, need_c0 = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        dh0 = empty((B, H), gates) if need_h0 else None
+        dc0 = empty((B, H), gates) if need_c0 else None
+        if ctx.composed:
+            dc = empty((B, H), gates)
+            for t in range(T - 1, -1, -1):
+                if t == T - 1:
+                    dh, dh2 = dy[t], d_hT
+                else:
+                    dh, dh2 = empty((B, H), gates), dy[t]
+                    gemm(gates[t + 1], w_hh, dh, B, H, H4)
+                call('re2e_lstm_cell_bwd', gates[t].data_ptr(), cbuf[t].data_ptr(), cbuf[t + 1].data_ptr(), dh.data_ptr(), ptr(dh2),
+                     ptr(d_cT) if t == T - 1 else dc.data_ptr(), dc.data_ptr(), B, H)
+            if need_h0:
+                gemm(gates[0], w_hh, dh0, B, H, H4)
+            if need_c0:
+                dc0 = dc
+        else:
+            wsb = query('re2e_lmseq_workspace_bytes', B, H)
+            ws = workspace(wsb, gates.device, 'lmseq')
+            call('re2e_lmseq_bwd', gates.data_ptr(), w_hh.data_ptr(), dy.data_ptr(), ptr(d_hT), ptr(d_cT), cbuf.data_ptr(), ptr(dh0), ptr(dc0),
+                 T, B, H, ws.data_ptr(), wsb)
+        if _wants(ctx, 1, w_hh):
+            with param_grads(gates, hbuf):
+                with accumulate(w_hh) as (gw, beta):
+                    gemm(gates, hbuf, gw, H4, H, T * B, transa=True, beta=beta)          # dW_hh = dgates^T h[t-1] over all T*B rows
+        return gates, None, dh0, dc0, None
+
+
+def lm_lstm_seq(xg, w_hh, h0, c0, composed=False):
+    """One window of a unidirectional LSTM with carried state: (h_all (T,B,H), h_T, c_T); see LmSeqFn."""
+    return LmSeqFn.apply(xg, w_hh, h0, c0, bool(composed))
+
+
+EMBEDDING_BWD_MAX_TOKENS = 15000      # re2e_embedding_bwd holds the ids of one call in LDS (60 000 bytes)
+
+
+class EmbeddingFn(torch.autograd.Function):
+    """table (V,D), ids int32 (n) on the device -> (n,D); the table's gradient is accumulated into ``table.grad`` in index order (more
+    than EMBEDDING_BWD_MAX_TOKENS rows: in consecutive blocks of rows, each added to the one before -- still index order)."""
+
+    @staticmethod
+    def forward(ctx, table, ids_dev):
+        _need_gpu(table)
+        n, (V, D) = ids_dev.numel(), table.shape
+        out = empty((n, D), table)
+        call('re2e_embedding_fwd', table.data_ptr(), ids_dev.data_ptr(), n, D, out.data_ptr(), D)
+        ctx.table, ctx.ids = table, ids_dev
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        table, ids = ctx.table, ctx.ids
+        if _wants(ctx, 0, table):
+            dout = _f32(dout)
+            V, D = table.shape
+            with accumulate(table) as (gw, beta):
+                for r0 in range(0, ids.numel(), EMBEDDING_BWD_MAX_TOKENS):
+                    n = min(EMBEDDING_BWD_MAX_TOKENS, ids.numel() - r0)
+                    call('re2e_embedding_bwd', dout[r0:r0 + n].data_ptr(), D, ids[r0:r0 + n].data_ptr(), n, D, V, gw.data_ptr(), float(beta))
+                    beta = 1.0
+        return None, None
+
+
+def embedding(table, ids_dev):
+    return EmbeddingFn.apply(table, ids_dev)
+
+
+class Linear2BiasFn(torch.autograd.Function):
+    """y = x W^T + b1 + b2 in one product (nn.LSTMCell's input half over a whole window: both biases ride in its epilogue); gradients of
+    W, b1 and b2 are accumulated into their ``.grad``."""
+
+    @staticmethod
+    def forward(ctx, x, W, b1, b2):
+        _need_gpu(x)
+        x2 = _f32(x).view(-1, x.shape[-1])
+        M, K = x2.shape
+        N = W.shape[0]
+        y = empty((M, N), x)
+        gemm(x2, W, y, M, N, K, transb=True, bias=b1, bias2=b2)
+        ctx.save_for_backward(x2)
+        ctx.W, ctx.b1, ctx.b2, ctx.xshape = W, b1, b2, x.shape
+        return y.view(*x.shape[:-1], N)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, = ctx.saved_tensors
+        W = ctx.W
+        M, K = x2.shape
+        N = W.shape[0]
+        dz = _f32(dy).reshape(M, N)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = empty((M, K), x2)
+            gemm_input_grad(dz, W, dx, M, K, N)
+            dx = dx.view(ctx.xshape)
+        with param_grads(dz, x2):
+            if _wants(ctx, 1, W):
+                with accumulate(W) as (gw, beta):
+                    gemm(dz, x2, gw, N, K, M, transa=True, beta=beta)
+            for i, b in ((2, ctx.b1), (3, ctx.b2)):
+                if _wants(ctx, i, b):
+                    with accumulate(b) as (gb, beta):
+                        colsum_into(dz, M, N, gb, beta)
+        return dx, None, None, None
+
+
+def linear_2bias(x, W, b1, b2):
+    return Linear2BiasFn.apply(x, W, b1, b2)

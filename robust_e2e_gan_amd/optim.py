@@ -1,6 +1,6 @@
 """K11: fused multi-tensor optimizers on ONE flat buffer per network.
 
-Replaces torch.optim.Adadelta / Adam + clip_grad_norm_ + the NaN guard of joint_train.py:131-140,
+Replaces torch.optim.Adadelta / Adam / SGD + clip_grad_norm_ + the NaN guard of joint_train.py:131-140,
 188-193.  All parameters of a network are re-pointed into one flat fp32 buffer (each tensor 256-B
 aligned so the GEMM loaders keep their 16-B vector path), all gradients into a second one; the
 update is a single HIP launch, the global grad-norm a two-stage deterministic reduction, and the
@@ -31,8 +31,9 @@ class FlatOptimizer:
             view.copy_(p.data)
             p.data = view
         self._attach_grads()
-        self.s1 = torch.zeros(n, dtype=torch.float32, device=dev)    # Adadelta square_avg / Adam exp_avg
-        self.s2 = torch.zeros(n, dtype=torch.float32, device=dev)    # Adadelta acc_delta  / Adam exp_avg_sq
+        if kind != 'sgd':
+            self.s1 = torch.zeros(n, dtype=torch.float32, device=dev)    # Adadelta square_avg / Adam exp_avg
+            self.s2 = torch.zeros(n, dtype=torch.float32, device=dev)    # Adadelta acc_delta  / Adam exp_avg_sq
         self.stats = torch.tensor([0.0, 1.0, 1.0, 0.0, 1.0, 1.0], dtype=torch.float32, device=dev)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.step_count = 0
@@ -40,6 +41,8 @@ class FlatOptimizer:
             self.param_groups = [dict(params=self.params, rho=rho, eps=eps, lr=1.0 if lr is None else lr)]
         elif kind == 'adam':
             self.param_groups = [dict(params=self.params, betas=betas, eps=eps, lr=1e-3 if lr is None else lr)]
+        elif kind == 'sgd':          # plain SGD on the clipped gradient (lm_train.py: torch.optim.SGD(lr=1.0)); no state
+            self.param_groups = [dict(params=self.params, lr=1.0 if lr is None else lr)]
         else:
             raise ValueError(kind)
 
@@ -81,6 +84,8 @@ class FlatOptimizer:
         if self.kind == 'adadelta':
             call('re2e_adadelta_step', self.flat.data_ptr(), self.grad.data_ptr(), self.s1.data_ptr(), self.s2.data_ptr(), self.numel,
                  float(g['rho']), float(g['eps']), float(g['lr']), st.data_ptr())
+        elif self.kind == 'sgd':
+            call('re2e_sgd_step', self.flat.data_ptr(), self.grad.data_ptr(), self.numel, float(g['lr']), st.data_ptr())
         else:
             call('re2e_adam_step', self.flat.data_ptr(), self.grad.data_ptr(), self.s1.data_ptr(), self.s2.data_ptr(), self.numel,
                  float(g['lr']), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), self.step_count, st.data_ptr())
