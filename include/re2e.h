@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 327
+#define RE2E_ABI_VERSION 328
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -625,7 +625,9 @@ int re2e_clip_coef(const float* sumsq_dev, float max_norm, float* stats_dev, re2
 /* g <- coef*g applied on the fly; skipped entirely when stats[2]==0 (NaN guard, no host sync) */
 int re2e_adadelta_step(float* p, const float* g, float* sq_avg, float* acc_delta, long n, float rho, float eps,
                        float lr, const float* stats_dev, re2e_stream_t stream);
-int re2e_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+/* torch.optim.Adam's step at step count `step` (>= 1).  beta1 / beta2 are doubles: 1 - beta and the bias corrections 1 - beta^step are taken
+ * in double on the host, as torch takes them in Python floats (as floats, 1 - 0.999f alone is 1.3e-5 off). */
+int re2e_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2,
                    float eps, int step, const float* stats_dev, re2e_stream_t stream);
 /* p -= lr * stats[1] * g (plain SGD on the clipped gradient: lm_train.py); skipped entirely when stats[2]==0.  stats_dev NULL: coefficient 1. */
 int re2e_sgd_step(float* p, const float* g, long n, float lr, const float* stats_dev, re2e_stream_t stream);

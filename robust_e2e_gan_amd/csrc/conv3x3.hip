@@ -289,15 +289,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloArgs p) {
           const int t = it * 4 + prow, pr = t / PC, pc = t - pr * PC;
           const int yy = y0 + wid * WR + 2 * pr, xx = x0 + 2 * pc;
           if (yy < p.H && xx < p.W) {
-            f32x4 best = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+            // the window's first pixel is inside the image (yy < H, xx < W); a NaN wins and stays, as in maxpool2_fwd_kernel
+            f32x4 best = *reinterpret_cast<const f32x4*>(Os + ((2 * pr) * TW + 2 * pc) * LDO + c4);
             int bi[4] = {0, 0, 0, 0};
 #pragma unroll
-            for (int d = 0; d < 4; ++d) {
+            for (int d = 1; d < 4; ++d) {
               if (yy + (d >> 1) < p.H && xx + (d & 1) < p.W) {
                 const f32x4 v = *reinterpret_cast<const f32x4*>(Os + ((2 * pr + (d >> 1)) * TW + 2 * pc + (d & 1)) * LDO + c4);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                  if (v[k] > best[k]) { best[k] = v[k]; bi[k] = d; }
+                  if (v[k] > best[k] || v[k] != v[k]) { best[k] = v[k]; bi[k] = d; }
               }
             }
             const long po = ((((long)n * PH2 + (yy >> 1)) * PW2 + (xx >> 1)) * p.Cout + n0 + c4);

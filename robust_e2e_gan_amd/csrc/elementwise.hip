@@ -498,13 +498,15 @@ __global__ void maxpool2_fwd_kernel(const float* __restrict__ in, int NI, int H,
   long tot = (long)NI * OH * OW * C;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
     int c = (int)(i % C); long r = i / C; int ox = (int)(r % OW); r /= OW; int oy = (int)(r % OH); int n = (int)(r / OH);
-    float best = -3.0e38f; int bi = 0;
+    // the running maximum starts from the window's first pixel, which is always inside the image (so a window of -inf pools to -inf);
+    // a NaN wins and stays (torch.max_pool2d: `val > maxval || isnan(val)`), so that it reaches the NaN gate of the joint step
+    float best = in[(((long)n * H + oy * 2) * W + ox * 2) * C + c]; int bi = 0;
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
+    for (int d = 1; d < 4; ++d) {
       int iy = oy * 2 + (d >> 1), ix = ox * 2 + (d & 1);
       if (iy < H && ix < W) {
         float v = in[(((long)n * H + iy) * W + ix) * C + c];
-        if (v > best) { best = v; bi = d; }     // first max wins (PyTorch order: row-major scan)
+        if (v > best || v != v) { best = v; bi = d; }     // first max wins (PyTorch order: row-major scan)
       }
     }
     out[i] = best; idx[i] = (unsigned char)((relu_in && !(best > 0.f)) ? 4 : bi);
@@ -520,16 +522,16 @@ __global__ void maxpool2_fwd_vec_kernel(const float* __restrict__ in, int NI, in
   const f32x4* in4 = reinterpret_cast<const f32x4*>(in);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (long)gridDim.x * blockDim.x) {
     int c = (int)(i % C4); long r = i / C4; int ox = (int)(r % OW); r /= OW; int oy = (int)(r % OH); int n = (int)(r / OH);
-    f32x4 best = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+    f32x4 best = in4[(((long)n * H + oy * 2) * W + ox * 2) * C4 + c];      // the first pixel is inside the image; a NaN wins (see above)
     int bi[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
+    for (int d = 1; d < 4; ++d) {
       int iy = oy * 2 + (d >> 1), ix = ox * 2 + (d & 1);
       if (iy < H && ix < W) {
         const f32x4 v = in4[(((long)n * H + iy) * W + ix) * C4 + c];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-          if (v[k] > best[k]) { best[k] = v[k]; bi[k] = d; }     // first max wins (PyTorch order: row-major scan)
+          if (v[k] > best[k] || v[k] != v[k]) { best[k] = v[k]; bi[k] = d; }     // first max wins (PyTorch order: row-major scan)
       }
     }
     reinterpret_cast<f32x4*>(out)[i] = best;
@@ -1045,25 +1047,30 @@ extern "C" int re2e_adadelta_step(float* p, const float* g, float* sq_avg, float
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }
-__global__ void adam_kernel(float* p, const float* __restrict__ g, float* m, float* v, long n, float lr, float b1, float b2, float eps,
-                            float bc1, float bc2, const float* __restrict__ stats) {
+// b1 / omb1 = beta1 and 1 - beta1 (b2 / omb2 alike), step_size = lr / (1 - beta1^step), sqrt_bc2 = sqrt(1 - beta2^step): all taken in double
+// on the host and rounded once, as torch.optim.Adam takes them in Python floats
+__global__ void adam_kernel(float* p, const float* __restrict__ g, float* m, float* v, long n, float step_size, float b1, float omb1, float b2,
+                            float omb2, float eps, float sqrt_bc2, const float* __restrict__ stats) {
   float coef = 1.f;
   if (stats) { if (stats[2] == 0.f) return; coef = stats[1]; }
-  float step_size = lr / bc1;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     float gr = g[i] * coef;
-    float mi = m[i] * b1 + (1.f - b1) * gr;
-    float vi = v[i] * b2 + (1.f - b2) * gr * gr;
+    float mi = m[i] * b1 + omb1 * gr;
+    float vi = v[i] * b2 + omb2 * gr * gr;
     m[i] = mi; v[i] = vi;
-    float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+    float denom = sqrtf(vi) / sqrt_bc2 + eps;
     p[i] -= step_size * mi / denom;
   }
 }
-extern "C" int re2e_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+// beta1 / beta2 are doubles: 1 - (float)0.999 is 1.3e-5 off 1 - 0.999, which was the relative error of exp_avg_sq after the first step, and
+// 1 - powf(beta, step) in float put the update 2e-6 off (tests/test_feat_kernels_gpu.py)
+extern "C" int re2e_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, double beta1, double beta2, float eps,
                               int step, const float* stats, hipStream_t stream) {
   RE2E_CHECK_ARG(p && g && m && v && n > 0 && step >= 1, "bad args");
-  float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(TPB), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, bc1, bc2, stats);
+  RE2E_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "betas must be in [0, 1)");
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(TPB), 0, stream, p, g, m, v, n, (float)((double)lr / bc1), (float)beta1, (float)(1.0 - beta1),
+                     (float)beta2, (float)(1.0 - beta2), eps, (float)sqrt(bc2), stats);
   RE2E_LAUNCH_CHECK();
   return RE2E_OK;
 }

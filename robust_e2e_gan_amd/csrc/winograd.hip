@@ -508,7 +508,8 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
       if (p.pool_out) {
         // a tile is one 2x2 / stride-2 pooling window (y0, x0 even).  max and ReLU commute: the ReLU is applied to the pooled value.
         // Index byte: first maximum in row-major order among the pixels inside the image (ceil mode), 4 when the maximum is <= 0
-        // (re2e_maxpool2_fwd with relu_in)
+        // (re2e_maxpool2_fwd with relu_in).  A NaN wins and stays a NaN through the ReLU, as in torch's max_pool2d(relu(.)): the NaN gate
+        // of the joint step must see it whichever pool ran
         const int ty2 = tl / TXW, tx2 = tl - ty2 * TXW;
         const int oy = y0 + 2 * ty2, ox = x0 + 2 * tx2;
         f32x4 best = Y[0][0];
@@ -519,12 +520,12 @@ __global__ __launch_bounds__(256, 2) void wino_conv3x3_kernel(WinoArgs p) {
             const f32x4 v = Y[d >> 1][d & 1];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-              if (v[k] > best[k]) { best[k] = v[k]; bi[k] = d; }
+              if (v[k] > best[k] || v[k] != v[k]) { best[k] = v[k]; bi[k] = d; }
           }
         }
         unsigned b4 = 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { b4 |= (unsigned)(best[k] > 0.f ? bi[k] : 4) << (8 * k); best[k] = best[k] > 0.f ? best[k] : 0.f; }
+        for (int k = 0; k < 4; ++k) { b4 |= (unsigned)(best[k] > 0.f ? bi[k] : 4) << (8 * k); best[k] = best[k] <= 0.f ? 0.f : best[k]; }
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, best), rsO, o_off[it][0], 0, 0);
         __builtin_amdgcn_raw_buffer_store_b32(b4, rsI, o_off[it][0] == WOOB ? WOOB : o_off[it][0] >> 2, 0, 0);
       } else {

@@ -7,21 +7,21 @@ on a CPU-only box for the build/ABI checks); the first kernel call needs a GPU.
 import atexit
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint, c_ulonglong, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint, c_ulonglong, c_void_p
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 327      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 328      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
 EUNSUPPORTED = -2      # RE2E_EUNSUPPORTED
 STREAM_DEFAULT, STREAM_FILLER = 0, 1
 
-P, I, L, F, Z = c_void_p, c_int, c_long, c_float, c_size_t
+P, I, L, F, Z, D = c_void_p, c_int, c_long, c_float, c_size_t, c_double
 
 # name -> (restype, argtypes).  Must list every symbol of include/re2e.h (tests/test_abi.py).
 SIGNATURES = {
@@ -147,7 +147,7 @@ SIGNATURES = {
     're2e_beam_prune': (I, [P, I, I, P, P, P, I, I, I, P, P, P, P, P, P, Z, P]),
     're2e_clip_coef': (I, [P, F, P, P]),
     're2e_adadelta_step': (I, [P, P, P, P, L, F, F, F, P, P]),
-    're2e_adam_step': (I, [P, P, P, P, L, F, F, F, F, I, P, P]),
+    're2e_adam_step': (I, [P, P, P, P, L, F, D, D, F, I, P, P]),
     're2e_sgd_step': (I, [P, P, L, F, P, P]),
 }
 
