@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 328
+#define RE2E_ABI_VERSION 329
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -560,6 +560,12 @@ int re2e_attloc_denc(const float* w_all, const float* dc_all, int L1, int B, int
 int re2e_lm_lstm_cell(const float* x, long ldx, const int* ids_dev, int n_embed, int I, const float* w_ih, const float* w_hh,
                       const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float* h_out,
                       float* c_out, re2e_stream_t stream);
+/* re2e_lm_lstm_cell followed by zoneout in evaluation mode (the FS-RNN LM's cells, fsrnn.py:15-32): h_out = keep_h h' + (1 - keep_h) h_prev,
+ * c_out = keep_c c' + (1 - keep_c) c_prev.  x == NULL (then ids_dev is NULL too; ldx, I and w_ih are ignored): a cell without input, only
+ * b_ih contributes.  Every output element is written. */
+int re2e_lm_lstm_cell_zo(const float* x, long ldx, const int* ids_dev, int n_embed, int I, const float* w_ih, const float* w_hh,
+                         const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float keep_h,
+                         float keep_c, float* h_out, float* c_out, re2e_stream_t stream);
 /* logits (n, V) = h (n, H) w (V, H)^T + b */
 int re2e_lm_output(const float* h, const float* w, const float* b, int n, int V, int H, float* logits, re2e_stream_t stream);
 /* lsm (n, V) = log_softmax(logits) row-wise and, with att / comb (both or neither), comb = att + lm_weight * lsm in the same pass
@@ -651,6 +657,35 @@ int re2e_lmseq_bwd(float* gates, const float* w_hh, const float* dy, const float
  * (rows x units: the workgroup's tile; acc: independent accumulators per wave; launches: one per step; rounds: workgroups per CU).
  * cus > 0: plan for a chip of that many CUs (no device is touched); cus == 0: the current device's count. */
 int re2e_lmseq_plan(int T, int B, int H, int backward, int cus, char* out, size_t out_bytes);
+
+/* ---- L2 fast-slow RNN over one truncated-BPTT window (csrc/fsrnn.hip): the recurrence of the FS-RNN LM (model/fsrnn.py; fsrnn.py:96-127).
+ * One step is a chain of L + 1 LSTM cells of width H, each followed by zoneout: F0 (input hoisted into gates[0]) -> S (input d1 . F0) ->
+ * F1 (input d2 . S) -> F2 .. F(L-1) (no input) -> F0 of the next step.  Cell index 0 .. L-1 = fast cells, L = the slow cell.  Time-major:
+ *   gates (L+1,T,B,4H)   gates[0] holds x W_ih^T + b_ih + b_hh of F0 (gate order i,f,g,o) on entry; every cell's ACTIVATED gates on exit of
+ *                        re2e_fsrnn_fwd; re2e_fsrnn_bwd overwrites them with d(pre-activation gates) (gates[0]: the gradient of its input)
+ *   hbuf, cbuf (L+1,T+1,B,H)   block t+1 of cell c: its state after zoneout at step t.  Block 0 of cells L-1 and L is the initial fast /
+ *                        slow state, written by the caller and left untouched; block 0 of the other cells is unused (never read or written)
+ *   hd (2,T,B,H)         with dm: d1 . hbuf[0][t+1] and d2 . hbuf[L][t+1], the inputs of S and F1 (written by the forward)
+ *   mh, mc (L+1,T,B,H)   zoneout masks per cell and step: new = mask . new + (1 - mask) . old; NULL: the scalars keep_h / keep_c
+ *   dm (2,T,B,H)         the dropout masks d1 and d2 with their scale 1 / (1 - p) in them; NULL (then hd is NULL too): no dropout
+ * w_ih, w_hh, b_ih, b_hh: HOST arrays of L+1 device pointers, (4H,H) / (4H) each; w_ih[1], w_ih[L] and every w_hh are read, the biases of
+ * cells 1 .. L are read by the forward only, everything else may be NULL.  dy (T,B,H): the gradient of hbuf[L-1][1:]; d_fh / d_fc / d_sh /
+ * d_sc (B,H), optional (NULL = zeros): the gradient flowing in through the final state; d_fh0 .. d_sc0 (B,H), optional outputs: the gradient
+ * flowing out through the initial state.  Any H >= 1, B >= 1, 2 <= L <= 64; nothing beyond 4-byte alignment is assumed; one cell's gates
+ * (T,B,4H) must stay below 2^31 elements.  L + 1 launches per time step on `stream`, the backward one more for each of d_fh0 / d_sh0.
+ * workspace: re2e_fsrnn_workspace_bytes(B, H) (the backward's four carries; the forward needs none). */
+size_t re2e_fsrnn_workspace_bytes(int B, int H);
+int re2e_fsrnn_fwd(float* gates, float* hbuf, float* cbuf, float* hd, const float* const* w_ih, const float* const* w_hh,
+                   const float* const* b_ih, const float* const* b_hh, const float* mh, const float* mc, const float* dm, float keep_h,
+                   float keep_c, int T, int B, int H, int L, void* workspace, size_t workspace_bytes, re2e_stream_t stream);
+int re2e_fsrnn_bwd(float* gates, const float* cbuf, const float* const* w_ih, const float* const* w_hh, const float* mh, const float* mc,
+                   const float* dm, float keep_h, float keep_c, const float* dy, const float* d_fh, const float* d_fc, const float* d_sh,
+                   const float* d_sc, float* d_fh0, float* d_fc0, float* d_sh0, float* d_sc0, int T, int B, int H, int L, void* workspace,
+                   size_t workspace_bytes, re2e_stream_t stream);
+/* The form re2e_fsrnn_fwd (backward == 0) / re2e_fsrnn_bwd runs this window with, as one line of space-separated key=value pairs in `out`;
+ * nothing is launched.   family=fsrnn_fwd_step|fsrnn_bwd_step mfma=16x16x4 rows=.. units=.. acc=.. kc=.. grid=XxYx1 lds=.. cells=.. launches=..
+ * rounds=..   (launches: cells x T; rounds: workgroups per CU and launch).  cus > 0: a chip of that many CUs (no device is touched). */
+int re2e_fsrnn_plan(int T, int B, int H, int L, int backward, int cus, char* out, size_t out_bytes);
 
 #ifdef __cplusplus
 }

@@ -98,12 +98,14 @@ __device__ __forceinline__ float reduce_block(float (&v)[NV], int wave, int lane
 
 // LSTMCell for n rows (torch gate order i, f, g, o).  x: dense rows (ids == nullptr) or an embedding table gathered by ids
 // (an id outside [0, n_embed) gives a NaN row, never an out-of-bounds read).  h_prev / c_prev == nullptr: zeros.
-template <int R, int VI, int VH>
+// ZO (re2e_lm_lstm_cell_zo): x == nullptr is no input (b_ih alone contributes), and the new state is blended with the previous one,
+// h = keep_h h' + (1 - keep_h) h_prev, c likewise (zoneout in evaluation mode, fsrnn.py:15-32).
+template <int R, int VI, int VH, bool ZO>
 __global__ __launch_bounds__(64 * LM_WAVES) void lm_cell_kernel(const float* __restrict__ x, long ldx, const int* __restrict__ ids, int n_embed, int I,
                                                       const float* __restrict__ w_ih, const float* __restrict__ w_hh,
                                                       const float* __restrict__ b_ih, const float* __restrict__ b_hh,
                                                       const float* __restrict__ h_prev, const float* __restrict__ c_prev, int n, int H,
-                                                      float* __restrict__ h_out, float* __restrict__ c_out) {
+                                                      float keep_h, float keep_c, float* __restrict__ h_out, float* __restrict__ c_out) {
   __shared__ float part[LM_WAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int j = blockIdx.x;                               // one workgroup per hidden unit
@@ -135,13 +137,14 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_cell_kernel(const float* __r
     const bool fin = wave == 0 && lane < nr;
     const long o = (long)(row0 + (fin ? lane : 0)) * H + j;
     const float cp = (fin && c_prev) ? c_prev[o] : 0.f;
+    const float hp = (ZO && fin && h_prev) ? h_prev[o] : 0.f;
     float bias[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) bias[g] = fin ? b_ih[g * H + j] + b_hh[g * H + j] : 0.f;
     float acc[4 * R];
 #pragma unroll
     for (int i = 0; i < 4 * R; ++i) acc[i] = 0.f;
-    dot4<R, VI>(wi, I, x, xoff, wave, lane, acc);
+    if (!ZO || x) dot4<R, VI>(wi, I, x, xoff, wave, lane, acc);
     if (h_prev) dot4<R, VH>(wh, H, h_prev, hoff, wave, lane, acc);
     const float s = reduce_block<4 * R>(acc, wave, lane, part);
     constexpr int REP = 64 / (4 * R);                     // lanes that hold one (gate, row) total
@@ -155,6 +158,10 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_cell_kernel(const float* __r
       const float go = sigmoidf_(gate[3] + bias[3]);
       float c = gi * gg + gf * cp;
       float h = go * tanhf_(c);
+      if (ZO) {
+        h = h * keep_h + (1.f - keep_h) * hp;
+        c = c * keep_c + (1.f - keep_c) * cp;
+      }
       if (bad) c = h = __builtin_nanf("");
       c_out[o] = c;
       h_out[o] = h;
@@ -248,13 +255,13 @@ inline int vec_width(const void* p, long ld) {
   return 1;
 }
 
-template <int R>
+template <int R, bool ZO>
 void launch_cell(int vi, int vh, dim3 grid, hipStream_t st, const float* x, long ldx, const int* ids, int n_embed, int I, const float* w_ih,
-                 const float* w_hh, const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float* h_out,
-                 float* c_out) {
+                 const float* w_hh, const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float keep_h,
+                 float keep_c, float* h_out, float* c_out) {
 #define RE2E_LM_CELL(VI, VH)                                                                                                             \
-  hipLaunchKernelGGL((lm_cell_kernel<R, VI, VH>), grid, dim3(64 * LM_WAVES), 0, st, x, ldx, ids, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, \
-                     n, H, h_out, c_out)
+  hipLaunchKernelGGL((lm_cell_kernel<R, VI, VH, ZO>), grid, dim3(64 * LM_WAVES), 0, st, x, ldx, ids, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, \
+                     n, H, keep_h, keep_c, h_out, c_out)
   if (vi == 4 && vh == 4) RE2E_LM_CELL(4, 4);
   else if (vi == 4 && vh == 2) RE2E_LM_CELL(4, 2);
   else if (vi >= 2 && vh >= 2) RE2E_LM_CELL(2, 2);
@@ -269,26 +276,41 @@ void launch_out(int vec, dim3 grid, hipStream_t st, const float* h, const float*
   else hipLaunchKernelGGL((lm_out_kernel<R, 1>), grid, dim3(64 * LM_WAVES), 0, st, h, w, b, n, V, H, logits);
 }
 
+template <bool ZO>
+int lm_cell_entry(const float* x, long ldx, const int* ids_dev, int n_embed, int I, const float* w_ih, const float* w_hh, const float* b_ih,
+                  const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float keep_h, float keep_c, float* h_out, float* c_out,
+                  hipStream_t stream) {
+  RE2E_CHECK_ARG((x || ZO) && (w_ih || !x) && w_hh && b_ih && b_hh && h_out && c_out, "null operand");
+  RE2E_CHECK_ARG(x || !ids_dev, "ids without a table");
+  if (!x) { I = 1; ldx = 1; }
+  RE2E_CHECK_ARG(n > 0 && n <= 64 && I > 0 && H > 0 && ldx >= I, "bad shape (1 <= n <= 64)");
+  RE2E_CHECK_ARG(!ids_dev || n_embed > 0, "embedding gather needs the table's row count");
+  RE2E_CHECK_ARG((long)(ids_dev ? n_embed : n) * ldx < (1L << 31) && (long)n * H < (1L << 31), "operand beyond 32-bit element offsets");
+  RE2E_CHECK_ARG(h_out != h_prev && c_out != h_prev, "h_prev is read by every workgroup: the outputs must not alias it");
+  const int vi = x ? min(vec_width(w_ih, I), vec_width(x, ldx)) : 1;
+  const int vh = min(vec_width(w_hh, H), vec_width(h_prev, H));
+  const dim3 grid(H);
+#define RE2E_LM_ARGS vi, vh, grid, stream, x, ldx, ids_dev, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, n, H, keep_h, keep_c, h_out, c_out
+  if (n <= 4) launch_cell<4, ZO>(RE2E_LM_ARGS);
+  else if (n <= 8) launch_cell<8, ZO>(RE2E_LM_ARGS);
+  else launch_cell<16, ZO>(RE2E_LM_ARGS);
+#undef RE2E_LM_ARGS
+  RE2E_LAUNCH_CHECK();
+  return RE2E_OK;
+}
+
 }  // namespace
 
 extern "C" int re2e_lm_lstm_cell(const float* x, long ldx, const int* ids_dev, int n_embed, int I, const float* w_ih, const float* w_hh,
                                  const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float* h_out,
                                  float* c_out, hipStream_t stream) {
-  RE2E_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && h_out && c_out, "null operand");
-  RE2E_CHECK_ARG(n > 0 && n <= 64 && I > 0 && H > 0 && ldx >= I, "bad shape (1 <= n <= 64)");
-  RE2E_CHECK_ARG(!ids_dev || n_embed > 0, "embedding gather needs the table's row count");
-  RE2E_CHECK_ARG((long)(ids_dev ? n_embed : n) * ldx < (1L << 31) && (long)n * H < (1L << 31), "operand beyond 32-bit element offsets");
-  RE2E_CHECK_ARG(h_out != h_prev && c_out != h_prev, "h_prev is read by every workgroup: the outputs must not alias it");
-  const int vi = min(vec_width(w_ih, I), vec_width(x, ldx));
-  const int vh = min(vec_width(w_hh, H), vec_width(h_prev, H));
-  const dim3 grid(H);
-#define RE2E_LM_ARGS vi, vh, grid, stream, x, ldx, ids_dev, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, n, H, h_out, c_out
-  if (n <= 4) launch_cell<4>(RE2E_LM_ARGS);
-  else if (n <= 8) launch_cell<8>(RE2E_LM_ARGS);
-  else launch_cell<16>(RE2E_LM_ARGS);
-#undef RE2E_LM_ARGS
-  RE2E_LAUNCH_CHECK();
-  return RE2E_OK;
+  return lm_cell_entry<false>(x, ldx, ids_dev, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, n, H, 1.f, 1.f, h_out, c_out, stream);
+}
+
+extern "C" int re2e_lm_lstm_cell_zo(const float* x, long ldx, const int* ids_dev, int n_embed, int I, const float* w_ih, const float* w_hh,
+                                    const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float keep_h,
+                                    float keep_c, float* h_out, float* c_out, hipStream_t stream) {
+  return lm_cell_entry<true>(x, ldx, ids_dev, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, n, H, keep_h, keep_c, h_out, c_out, stream);
 }
 
 extern "C" int re2e_lm_output(const float* h, const float* w, const float* b, int n, int V, int H, float* logits, hipStream_t stream) {

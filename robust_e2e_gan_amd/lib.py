@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 328      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 329      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -133,12 +133,17 @@ SIGNATURES = {
     're2e_attloc_dpre': (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, Z, P]),
     're2e_attloc_denc': (I, [P, P, I, I, I, I, P, F, P]),
     're2e_lm_lstm_cell': (I, [P, L, P, I, I, P, P, P, P, P, P, I, I, P, P, P]),
+    're2e_lm_lstm_cell_zo': (I, [P, L, P, I, I, P, P, P, P, P, P, I, I, F, F, P, P, P]),
     're2e_lm_output': (I, [P, P, P, I, I, I, P, P]),
     're2e_lm_log_softmax_combine': (I, [P, I, I, P, F, P, P, P]),
     're2e_lmseq_workspace_bytes': (Z, [I, I]),
     're2e_lmseq_fwd': (I, [P, P, P, P, I, I, I, P, Z, P]),
     're2e_lmseq_bwd': (I, [P, P, P, P, P, P, P, P, I, I, I, P, Z, P]),
     're2e_lmseq_plan': (I, [I, I, I, I, I, P, Z]),
+    're2e_fsrnn_workspace_bytes': (Z, [I, I]),
+    're2e_fsrnn_fwd': (I, [P, P, P, P, P, P, P, P, P, P, P, F, F, I, I, I, I, P, Z, P]),
+    're2e_fsrnn_bwd': (I, [P, P, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P, I, I, I, I, P, Z, P]),
+    're2e_fsrnn_plan': (I, [I, I, I, I, I, I, P, Z]),
     're2e_lm_add_cands': (I, [P, P, P, I, I, I, F, P]),
     're2e_wlm_transition': (I, [P, P, I, I, I, I, P, P, P, P, I, I, P, P, P, P]),
     're2e_wlm_softmax_cumsum': (I, [P, I, I, P, I, P, P]),
@@ -279,6 +284,22 @@ def lmseq_plan(T, B, H, backward=False, cus=0):
     if rc != 0:
         raise Re2eError('re2e_lmseq_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
     return dict(kv.split('=') for kv in buf.value.decode().split())
+
+
+def fsrnn_plan(T, B, H, L, backward=False, cus=0):
+    """re2e_fsrnn_plan as a dict of strings: the cell-step kernel, its tile, grid, static LDS and launches re2e_fsrnn_fwd / _bwd run a window
+    with (cus > 0: on a chip of that many CUs, no device needed; 0: the current device)."""
+    buf = ctypes.create_string_buffer(220)
+    lib = load()
+    rc = lib.re2e_fsrnn_plan(T, B, H, L, int(backward), cus, buf, len(buf))
+    if rc != 0:
+        raise Re2eError('re2e_fsrnn_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    return dict(kv.split('=') for kv in buf.value.decode().split())
+
+
+def pointer_array(tensors):
+    """Host array of device pointers (None -> NULL) for the entry points that take per-cell operands (re2e_fsrnn_fwd / _bwd)."""
+    return (c_void_p * len(tensors))(*[ptr(t) for t in tensors])
 
 
 def gemm_plan(transa, transb, M, N, K, act=ACT_NONE, aligned=(True, True, True), rowmap=False, filler=False, cus=0):

@@ -1,5 +1,5 @@
 """Train the recurrent language model the beam search decodes with (mirror of lm_train.py): the reference's flags and defaults, then
-model/lm.py train().  python -m robust_e2e_gan_amd.lm_train --ngpu 1 --outdir exp/lm --dict data/dict.txt --train-label .. --valid-label .."""
+model/lm.py train() (--lm-type rnnlm) or model/fsrnn.py train() (--lm-type fsrnnlm).  python -m robust_e2e_gan_amd.lm_train --ngpu 1 --outdir exp/lm --dict data/dict.txt --train-label .. --valid-label .."""
 import argparse
 import logging
 import random
@@ -21,7 +21,7 @@ def get_parser():
     # task related
     parser.add_argument('--train-label', type=str, required=True, help='training text: one line of blank-separated tokens')
     parser.add_argument('--valid-label', type=str, required=True, help='validation text: one line of blank-separated tokens')
-    parser.add_argument('--lm-type', type=str, default='rnnlm', help='rnnlm (fsrnnlm is refused)')
+    parser.add_argument('--lm-type', type=str, default='rnnlm', help='rnnlm or fsrnnlm')
     # LSTMLM training configuration
     parser.add_argument('--batchsize', '-b', type=int, default=2048, help='rows of a batch: parallel positions in the corpus')
     parser.add_argument('--bproplen', '-l', type=int, default=35, help='steps per truncated-BPTT window')
@@ -30,7 +30,7 @@ def get_parser():
     parser.add_argument('--input-unit', type=int, default=650, help='width of the embedding')
     parser.add_argument('--unit', '-u', type=int, default=650, help='LSTM units per layer')
     parser.add_argument('--dropout-rate', type=float, default=0.2, help='rate of the three dropouts')
-    # FSLSTMLM training configuration (parsed for command-line compatibility; --lm-type fsrnnlm is refused)
+    # FSLSTMLM training configuration (--lm-type fsrnnlm)
     parser.add_argument('--fast_cell_size', type=int, default=650, help='FS-RNN only')
     parser.add_argument('--slow_cell_size', type=int, default=650, help='FS-RNN only')
     parser.add_argument('--fast_layers', type=int, default=2, help='FS-RNN only')
@@ -51,6 +51,9 @@ def main(argv=None):
     char_list.append('<eos>')
     args.char_list_dict = {x: i for i, x in enumerate(char_list)}
     args.n_vocab = len(char_list)
+    if args.lm_type == 'fsrnnlm':
+        from .model import fsrnn
+        return fsrnn.train(args)
     from .model import lm
     return lm.train(args)
 

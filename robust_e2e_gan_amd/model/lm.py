@@ -24,8 +24,9 @@ layer, the cross-entropy and their backward run over row blocks when T*B*V would
 operands with 32-bit element offsets).  In training ``COMPOSED_PATH`` means the same window with re2e_gemm + re2e_lstm_cell_fwd / _bwd
 per step as its recurrence (tools/bench_lm_train.py).
 
-Out of scope (refused with Re2eError where they can be asked for): the FS-RNN LM (--lm-type fsrnnlm), training on several GPUs or on the
-CPU, n-gram / FST LMs (NgramCharacterKenLM), deep and cold fusion."""
+Out of scope (refused with Re2eError where they can be asked for): the FS-RNN LM in ``train`` (--lm-type fsrnnlm is trained by
+model/fsrnn.py, not by this function; ``ClassifierWithState`` and ``evaluate`` take an FSRNNLM predictor as they take an RNNLM), training on
+several GPUs or on the CPU, n-gram / FST LMs (NgramCharacterKenLM), deep and cold fusion."""
 import logging
 import os
 
@@ -209,6 +210,7 @@ class ClassifierWithState(torch.nn.Module):
         reference's loop over T ``forward`` calls sums up.  The output layer and the loss run over blocks of whole rows when T*B*V
         would pass OUTPUT_MAX_ELEMS; a block of R rows contributes its mean x R / B, so the total is the same sum over rows / B."""
         rnn = self.predictor
+        lo = rnn.lo if isinstance(rnn, RNNLM) else rnn.out          # (model/fsrnn.py FSRNNLM names its output layer ``out``)
         state, hid = rnn.window(state, xs)
         T, B = int(xs.shape[0]), int(xs.shape[1])
         V, rows = rnn.n_vocab, T * B
@@ -220,7 +222,7 @@ class ClassifierWithState(torch.nn.Module):
         total, correct = None, None
         for r0 in range(0, rows, block):
             r1 = min(rows, r0 + block)
-            logits = ops.linear(hid[r0:r1], rnn.lo.weight, rnn.lo.bias)
+            logits = ops.linear(hid[r0:r1], lo.weight, lo.bias)
             loss, stats = ops.cross_entropy(logits, tgt[r0:r1], scale=(r1 - r0) / float(B))
             total = loss if total is None else total + loss
             correct = stats[1] if correct is None else correct + stats[1]
@@ -247,7 +249,7 @@ class ClassifierWithState(torch.nn.Module):
             return state, z, (att + float(np.float32(lm_weight)) * z if att is not None else None)
         n, V = z.shape
         lp = _empty(n, V, device=z.device)
-        if COMPOSED_PATH or not isinstance(self.predictor, RNNLM):
+        if COMPOSED_PATH or not (isinstance(self.predictor, RNNLM) or getattr(self.predictor, 'fused_combine', False)):
             call('re2e_log_softmax_rows', z.data_ptr(), n, V, V, lp.data_ptr())
             return state, lp, (att + float(np.float32(lm_weight)) * lp if att is not None else None)
         comb = _empty(n, V, device=z.device) if att is not None else None
@@ -305,7 +307,7 @@ def train(args):
     from ..data.lm_data_loader import ParallelSequentialIterator
     from ..optim import FlatOptimizer
     if args.lm_type != 'rnnlm':
-        raise Re2eError('--lm-type %s: only rnnlm is trained here (the FS-RNN LM is out of scope)' % args.lm_type)
+        raise Re2eError('--lm-type %s: only rnnlm is trained here (the FS-RNN LM is trained by model/fsrnn.py train)' % args.lm_type)
     if args.ngpu > 1:
         raise Re2eError('--ngpu %d: the LM trains on one GPU' % args.ngpu)
     if args.ngpu < 1 or not torch.cuda.is_available():

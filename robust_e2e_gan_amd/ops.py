@@ -2083,7 +2083,164 @@ def lm_lstm_seq(xg, w_hh, h0, c0, composed=False):
     return LmSeqFn.apply(xg, w_hh, h0, c0, bool(composed))
 
 
-EMBEDDING_BWD_MAX_TOKENS = 15000      # re2e_embedding_bwd holds the ids of one call in LDS (60 000 bytes)
+# ---------------------------------------------------------------------------------------------
+# L2 fast-slow RNN over one truncated-BPTT window (FS-RNN LM, csrc/fsrnn.hip)
+# ---------------------------------------------------------------------------------------------
+class FsrnnSeqFn(torch.autograd.Function):
+    """One window of the fast-slow recurrence (model/fsrnn.py; the contract of re2e_fsrnn_fwd / _bwd in include/re2e.h).  xg (T,B,4H) =
+    x W_ih^T + b_ih + b_hh of fast cell 0; the initial state F_h, F_c, S_h, S_c (B,H); mh, mc (L+1,T,B,H) zoneout masks or None (the
+    scalars keep_h / keep_c); dm (2,T,B,H) dropout masks or None; weights: (w_ih, w_hh, b_ih, b_hh) of fast cells 0 .. L-1, then of the slow
+    cell -> (the last fast output of every step (T,B,H), F_h, F_c, S_h, S_c after the window).  Gradients are returned for xg and the initial
+    state; the weights' are accumulated into their ``.grad`` after the loop as products over all T*B rows: dW_ih = dgates^T x_in, dW_hh =
+    dgates^T h_prev, both biases = column sums of dgates (fast cell 0's w_ih and biases belong to the caller's linear_2bias; the w_ih of
+    cells 2 .. L-1 sees a zero input: its gradient is exactly zero).  ``composed``: the same window over re2e_gemm, re2e_lstm_cell_fwd / _bwd
+    and element-wise torch ops (the arbiter and timing baseline).  The backward overwrites the saved gates: one backward per forward."""
+
+    @staticmethod
+    def forward(ctx, xg, Fh0, Fc0, Sh0, Sc0, mh, mc, dm, keep_h, keep_c, L, composed, *weights):
+        _need_gpu(xg)
+        T, B, H4 = xg.shape
+        H = H4 // 4
+        W = [weights[4 * c:4 * c + 4] for c in range(L + 1)]
+        ok = len(weights) == 4 * (L + 1) and L >= 2 and all(tuple(s.shape) == (B, H) for s in (Fh0, Fc0, Sh0, Sc0))
+        ok = ok and all(tuple(w[1].shape) == (H4, H) and w[1].is_contiguous() for w in W) and all(tuple(W[c][0].shape) == (H4, H) and W[c][0].is_contiguous() for c in (1, L))
+        ok = ok and all(m is None or (tuple(m.shape) == (L + 1, T, B, H) and m.is_contiguous()) for m in (mh, mc))
+        ok = ok and (dm is None or (tuple(dm.shape) == (2, T, B, H) and dm.is_contiguous()))
+        if not ok:
+            raise lib.Re2eError('fsrnn_seq: xg %s, %d cells, state %s, masks and weights do not fit together' % (tuple(xg.shape), L + 1, tuple(Fh0.shape)))
+        gates = empty((L + 1, T, B, H4), xg)
+        gates[0].copy_(xg)
+        hbuf, cbuf = empty((L + 1, T + 1, B, H), xg), empty((L + 1, T + 1, B, H), xg)
+        hbuf[L - 1, 0].copy_(Fh0)
+        cbuf[L - 1, 0].copy_(Fc0)
+        hbuf[L, 0].copy_(Sh0)
+        cbuf[L, 0].copy_(Sc0)
+        hd = empty((2, T, B, H), xg) if dm is not None else None
+        if composed:
+            def cell(c, t, x, hp, cp):
+                g = gates[c, t]
+                if c > 0:
+                    g.copy_((W[c][2] + W[c][3]).expand(B, H4))
+                if x is not None:
+                    gemm(x, W[c][0], g, B, H4, H, transb=True, beta=1.0)
+                gemm(hp, W[c][1], g, B, H4, H, transb=True, beta=1.0)
+                cn, hn = empty((B, H), xg), empty((B, H), xg)
+                call('re2e_lstm_cell_fwd', g.data_ptr(), cp.data_ptr(), cn.data_ptr(), hn.data_ptr(), B, H)
+                a, b = (mh[c, t] if mh is not None else keep_h), (mc[c, t] if mc is not None else keep_c)
+                hbuf[c, t + 1].copy_(hn * a + (1.0 - a) * hp)
+                cbuf[c, t + 1].copy_(cn * b + (1.0 - b) * cp)
+            for t in range(T):
+                cell(0, t, None, hbuf[L - 1, t], cbuf[L - 1, t])
+                if dm is not None:
+                    hd[0, t].copy_(hbuf[0, t + 1] * dm[0, t])
+                cell(L, t, hd[0, t] if dm is not None else hbuf[0, t + 1], hbuf[L, t], cbuf[L, t])
+                if dm is not None:
+                    hd[1, t].copy_(hbuf[L, t + 1] * dm[1, t])
+                for k in range(1, L):
+                    cell(k, t, (hd[1, t] if dm is not None else hbuf[L, t + 1]) if k == 1 else None, hbuf[k - 1, t + 1], cbuf[k - 1, t + 1])
+        else:
+            # per-cell operands as host arrays of device pointers; what the kernels never read (fast cell 0's w_ih and biases: they are in xg;
+            # the w_ih of the cells without input) is passed as NULL
+            arrays = [lib.pointer_array([None if (i != 1 and c == 0) or (i == 0 and 2 <= c < L) else W[c][i] for c in range(L + 1)]) for i in range(4)]
+            call('re2e_fsrnn_fwd', gates.data_ptr(), hbuf.data_ptr(), cbuf.data_ptr(), ptr(hd), arrays[0], arrays[1], arrays[2], arrays[3], ptr(mh), ptr(mc),
+                 ptr(dm), float(keep_h), float(keep_c), T, B, H, L, None, 0)
+        ctx.save_for_backward(gates, hbuf, cbuf, hd, mh, mc, dm)
+        ctx.W, ctx.cfg = W, (float(keep_h), float(keep_c), L, composed)
+        return hbuf[L - 1, 1:], hbuf[L - 1, T].clone(), cbuf[L - 1, T].clone(), hbuf[L, T].clone(), cbuf[L, T].clone()
+
+    @staticmethod
+    def backward(ctx, d_all, d_fh, d_fc, d_sh, d_sc):
+        gates, hbuf, cbuf, hd, mh, mc, dm = ctx.saved_tensors
+        W = ctx.W
+        keep_h, keep_c, L, composed = ctx.cfg
+        T, B, H4 = gates.shape[1:]
+        H = H4 // 4
+        dy = _f32(d_all) if d_all is not None else zeros((T, B, H), gates)
+        d_last = [(_f32(d) if d is not None else None) for d in (d_fh, d_fc, d_sh, d_sc)]
+        d0 = [empty((B, H), gates) if ctx.needs_input_grad[i] else None for i in (1, 2, 3, 4)]
+        if composed:
+            def cell(c, t, dH, dC, cp):
+                """zoneout and cell backward of cell c at step t -> (pass-through of dH, whole gradient of the previous c)"""
+                a, b = (mh[c, t] if mh is not None else keep_h), (mc[c, t] if mc is not None else keep_c)
+                dC = dC if dC is not None else zeros((B, H), gates)
+                g = gates[c, t]
+                gi, gf, gg, _ = g.chunk(4, 1)
+                cn = (gf * cp + gi * gg).contiguous()
+                dh, dc, dcp = (a * dH).contiguous(), (b * dC).contiguous(), empty((B, H), gates)
+                call('re2e_lstm_cell_bwd', g.data_ptr(), cp.data_ptr(), cn.data_ptr(), dh.data_ptr(), None, dc.data_ptr(), dcp.data_ptr(), B, H)
+                return (1.0 - a) * dH, dcp + (1.0 - b) * dC
+
+            def prod(c, t, w):
+                out = empty((B, H), gates)
+                gemm(gates[c, t], w, out, B, H, H4)
+                return out
+            f_dhp, f_dcp, s_dhp, s_dcp = d_last
+            for t in range(T - 1, -1, -1):
+                last = t == T - 1
+                for k in range(L - 1, 0, -1):
+                    if k == L - 1:
+                        dH = dy[t] if last else dy[t] + prod(0, t + 1, W[0][1])
+                    else:
+                        dH = prod(k + 1, t, W[k + 1][1])
+                    if f_dhp is not None:
+                        dH = dH + f_dhp
+                    f_dhp, f_dcp = cell(k, t, dH, f_dcp, cbuf[k - 1, t + 1])
+                dH = prod(1, t, W[1][0])
+                if dm is not None:
+                    dH = dH * dm[1, t]
+                if not last:
+                    dH = dH + prod(L, t + 1, W[L][1])
+                if s_dhp is not None:
+                    dH = dH + s_dhp
+                s_dhp, s_dcp = cell(L, t, dH, s_dcp, cbuf[L, t])
+                dH = prod(L, t, W[L][0])
+                if dm is not None:
+                    dH = dH * dm[0, t]
+                f_dhp, f_dcp = cell(0, t, dH + prod(1, t, W[1][1]) + f_dhp, f_dcp, cbuf[L - 1, t])
+            if d0[0] is not None:
+                d0[0] = prod(0, 0, W[0][1]) + f_dhp
+            if d0[2] is not None:
+                d0[2] = prod(L, 0, W[L][1]) + s_dhp
+            d0[1] = f_dcp if d0[1] is not None else None
+            d0[3] = s_dcp if d0[3] is not None else None
+        else:
+            arrays = [lib.pointer_array([None if (i == 0 and (c == 0 or 2 <= c < L)) else W[c][i] for c in range(L + 1)]) for i in range(2)]
+            wsb = query('re2e_fsrnn_workspace_bytes', B, H)
+            ws = workspace(wsb, gates.device, 'fsrnn')
+            call('re2e_fsrnn_bwd', gates.data_ptr(), cbuf.data_ptr(), arrays[0], arrays[1], ptr(mh), ptr(mc), ptr(dm), keep_h, keep_c, dy.data_ptr(),
+                 ptr(d_last[0]), ptr(d_last[1]), ptr(d_last[2]), ptr(d_last[3]), ptr(d0[0]), ptr(d0[1]), ptr(d0[2]), ptr(d0[3]), T, B, H, L,
+                 ws.data_ptr(), wsb)
+        M = T * B
+        with param_grads(gates, hbuf, hd):
+            for c in range(L + 1):
+                G2 = gates[c].view(M, H4)
+                x_in = None if c == 0 or 2 <= c < L else (hd[0 if c == L else 1] if hd is not None else hbuf[0 if c == L else L, 1:])
+                h_prev = hbuf[L - 1, :T] if c == 0 else hbuf[L, :T] if c == L else hbuf[c - 1, 1:]
+                base = 12 + 4 * c
+                if c > 0 and _wants(ctx, base, W[c][0]):
+                    with accumulate(W[c][0]) as (gw, beta):
+                        if x_in is not None:
+                            gemm(G2, x_in.reshape(M, H), gw, H4, H, M, transa=True, beta=beta)
+                        elif beta == 0.0:
+                            gw.zero_()
+                if _wants(ctx, base + 1, W[c][1]):
+                    with accumulate(W[c][1]) as (gw, beta):
+                        gemm(G2, h_prev.reshape(M, H), gw, H4, H, M, transa=True, beta=beta)
+                for i in (2, 3):
+                    if c > 0 and _wants(ctx, base + i, W[c][i]):
+                        with accumulate(W[c][i]) as (gb, beta):
+                            colsum_into(G2, M, H4, gb, beta)
+        return (gates[0], d0[0], d0[1], d0[2], d0[3]) + (None,) * (7 + 4 * (L + 1))
+
+
+def fsrnn_seq(xg, state, weights, L, mh=None, mc=None, dm=None, keep_h=1.0, keep_c=1.0, composed=False):
+    """One window of the fast-slow recurrence: ``state`` = (F_h, F_c, S_h, S_c), ``weights`` = L + 1 tuples (w_ih, w_hh, b_ih, b_hh), fast cells
+    first, the slow cell last -> (y (T,B,H), F_h, F_c, S_h, S_c); see FsrnnSeqFn."""
+    flat = [w for cell in weights for w in cell]
+    return FsrnnSeqFn.apply(xg, state[0], state[1], state[2], state[3], mh, mc, dm, float(keep_h), float(keep_c), int(L), bool(composed), *flat)
+
+
+EMBEDDING_BWD_MAX_TOKENS = 15000     # re2e_embedding_bwd holds the ids of one call in LDS (60 000 bytes)
 
 
 class EmbeddingFn(torch.autograd.Function):
