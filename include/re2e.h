@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 329
+#define RE2E_ABI_VERSION 330
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -549,6 +549,53 @@ int re2e_attloc_dpre(const float* pre, const float* conv_all, const float* dp_al
 /* d_enc[b,t,:] = beta*d_enc + sum_i w_all[i,b,t] * dc_all[i,b,:]  (w_all (L1,B,T), dc_all (L1,B,eprojs)) */
 int re2e_attloc_denc(const float* w_all, const float* dc_all, int L1, int B, int T, int eprojs, float* d_enc, float beta,
                      re2e_stream_t stream);
+
+/* ---- K7b content-based and coverage attention steps (AttDot, AttAdd, AttCov, AttCovLoc; csrc/attstep.hip) ----
+ * The step of K7 with another energy term, selected by `kind`:
+ *   RE2E_ATT_ADD       e = gvec . tanh(pre[b,t] + W_dec z[b]) + gb
+ *   RE2E_ATT_COVERAGE  e = gvec . tanh(wvec_w cov[b,t] + wvec_b + pre[b,t] + W_dec z[b]) + gb
+ *   RE2E_ATT_DOT       e = sum_a pre[b,t,a] q[b,a], q = tanh(W_dec z[b] + dec_b); pre is tanh(mlp_enc(enc)), made by the caller
+ * w = softmax over all T frames of 2 e, c = sum_t w[t] enc[b,t].  Coverage state: cov_0[b,t] = 1/hlen_b for t < hlen_b, else 0 (cov_in == NULL
+ * stands for it); the step writes cov_out = cov_in + w (B,T), padded frames included.  RE2E_ATT_COVERAGE_LOCATION is K7 with cov as att_prev:
+ * re2e_attloc_fwd / _bwd / _dpre plus re2e_attstep_cov_add; these entry points refuse it, and RE2E_ATT_LOCATION, with a message.
+ * Parameters a kind does not have are NULL (dot: dec_b only; add: gvec, gvec_b; coverage: wvec_w (adim), wvec_b (adim), gvec, gvec_b).
+ * dp_out (B,adim) = W_dec z (dot: q), saved for the backward; e_scratch (B,T) is scratch; cov_out is written for coverage only.
+ * Limits: adim <= 320, dunits <= 1024, eprojs % 4 == 0, T <= ~39000 (LDS of the softmax pass): RE2E_EUNSUPPORTED / RE2E_EINVAL otherwise. */
+#define RE2E_ATT_LOCATION 0
+#define RE2E_ATT_DOT 1
+#define RE2E_ATT_ADD 2
+#define RE2E_ATT_COVERAGE 3
+#define RE2E_ATT_COVERAGE_LOCATION 4
+int re2e_attstep_fwd(int kind, const float* pre, const float* enc, const float* z, const float* cov_in, const int* hlens_dev,
+                     const float* w_decT, const float* dec_b, const float* wvec_w, const float* wvec_b, const float* gvec,
+                     const float* gvec_b, int B, int T, int eprojs, int dunits, int adim, float* w_out, float* c_out, long ldc_out,
+                     float* cov_out, float* dp_out, float* e_scratch, re2e_stream_t stream);
+/* The same step for `nh` rows over U utterances, as re2e_attloc_fwd_rows: pre (U,T,adim) and enc (U,T,eprojs) are read through utt_dev (nh),
+ * a row has only the T_u = hlens_dev[utt] frames of its utterance (cov_in reads as cov_0 of T_u frames when NULL; w_out and cov_out at
+ * t >= T_u are written as 0), and gets bit for bit what re2e_attstep_fwd gives for T = T_u on its utterance alone. */
+int re2e_attstep_fwd_rows(int kind, const float* pre, const float* enc, int U, const int* hlens_dev, const int* utt_dev, const float* z,
+                          const float* cov_in, const float* w_decT, const float* dec_b, const float* wvec_w, const float* wvec_b,
+                          const float* gvec, const float* gvec_b, int nh, int T, int eprojs, int dunits, int adim, float* w_out,
+                          float* c_out, long ldc_out, float* cov_out, float* dp_out, float* e_scratch, re2e_stream_t stream);
+/* cov_out (rows,T) = cov_in + w; cov_in == NULL: cov_0 of each row's utterance (utt_dev == NULL: row b is utterance b; hlens_dev (U)). */
+int re2e_attstep_cov_add(const float* cov_in, const float* w, const int* hlens_dev, const int* utt_dev, int U, int rows, int T,
+                         float* cov_out, re2e_stream_t stream);
+/* floats of a row of the weight-gradient partials (B, .): [gvec(adim) | gvec_b(1) | wvec_w(adim) | wvec_b(adim)] (add: the first two; dot: 0) */
+size_t re2e_attstep_partial_floats(int kind, int adim);
+size_t re2e_attstep_workspace_bytes(int kind, int B, int T, int adim);
+/* backward of one step: de_out (B,T) = d(energy) (kept for re2e_attstep_dpre), d_cov (B,T) = the gradient at cov_in (coverage; may be NULL),
+ * d_decproj (B,adim) = the gradient at W_dec z (dot: at W_dec z + dec_b).  cov_in / dp_in / cx_in: what the forward read and saved; dw_in (B,T)
+ * or NULL: the gradient arriving at this step's w from outside its own softmax / context path. */
+int re2e_attstep_bwd(int kind, const float* pre, const float* enc, const float* cov_in, const float* w_cur, const int* hlens_dev,
+                     const float* wvec_w, const float* wvec_b, const float* gvec, const float* dp_in, const float* cx_in, const float* dc,
+                     long ld_dc, const float* dw_in, int B, int T, int eprojs, int adim, float* de_out, float* d_cov, float* d_decproj,
+                     void* workspace, size_t workspace_bytes, re2e_stream_t stream);
+/* after the loop: d_pre (B,T,adim) = sum over the L1 steps (overwritten; dot: the gradient at tanh(mlp_enc(enc))) and the partials (+=).
+ * cov_all (L1,B,T): cov_out of every step, stacked (step s reads cov_all[s-1], step 0 cov_0); dp_all (L1,B,adim), de_all (L1,B,T).
+ * d_enc: re2e_attloc_denc. */
+int re2e_attstep_dpre(int kind, const float* pre, const float* cov_all, const int* hlens_dev, const float* dp_all, const float* de_all,
+                      const float* wvec_w, const float* wvec_b, const float* gvec, int L1, int B, int T, int adim, float* d_pre,
+                      float* partials, void* workspace, size_t workspace_bytes, re2e_stream_t stream);
 
 /* ---- RNNLM shallow fusion at decode time (model/lm.py:125-146, e2e_decoder.py:270-285; csrc/rnnlm.hip) ----
  * Few-row kernels: n = the live hypotheses of a beam-search position, 1 <= n <= 64; any widths (the loads are as wide as the

@@ -14,12 +14,14 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 329      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 330      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
 EUNSUPPORTED = -2      # RE2E_EUNSUPPORTED
 STREAM_DEFAULT, STREAM_FILLER = 0, 1
+ATT_LOCATION, ATT_DOT, ATT_ADD, ATT_COVERAGE, ATT_COVERAGE_LOCATION = range(5)      # RE2E_ATT_*
+ATT_KINDS = {'location': ATT_LOCATION, 'dot': ATT_DOT, 'add': ATT_ADD, 'coverage': ATT_COVERAGE, 'coverage_location': ATT_COVERAGE_LOCATION}
 
 P, I, L, F, Z, D = c_void_p, c_int, c_long, c_float, c_size_t, c_double
 
@@ -132,6 +134,13 @@ SIGNATURES = {
     're2e_attloc_bwd': (I, [P, P, P, P, P, P, P, P, P, P, P, P, L, P, I, I, I, I, I, I, P, P, P, P, P, Z, P]),
     're2e_attloc_dpre': (I, [P, P, P, P, P, P, I, I, I, I, I, I, P, P, P, Z, P]),
     're2e_attloc_denc': (I, [P, P, I, I, I, I, P, F, P]),
+    're2e_attstep_fwd': (I, [I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, L, P, P, P, P]),
+    're2e_attstep_fwd_rows': (I, [I, P, P, I, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, L, P, P, P, P]),
+    're2e_attstep_cov_add': (I, [P, P, P, P, I, I, I, P, P]),
+    're2e_attstep_partial_floats': (Z, [I, I]),
+    're2e_attstep_workspace_bytes': (Z, [I, I, I, I]),
+    're2e_attstep_bwd': (I, [I, P, P, P, P, P, P, P, P, P, P, P, L, P, I, I, I, I, P, P, P, P, Z, P]),
+    're2e_attstep_dpre': (I, [I, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, Z, P]),
     're2e_lm_lstm_cell': (I, [P, L, P, I, I, P, P, P, P, P, P, I, I, P, P, P]),
     're2e_lm_lstm_cell_zo': (I, [P, L, P, I, I, P, P, P, P, P, P, I, I, F, F, P, P, P]),
     're2e_lm_output': (I, [P, P, P, I, I, I, P, P]),

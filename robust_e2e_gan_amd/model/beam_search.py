@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..lib import call
+from ..lib import ATT_KINDS, call
 from .e2e_common import host_to_dev, lens_dev
 
 CTC_SCORING_RATIO = 1.5          # e2e_decoder.py:20
@@ -104,6 +104,54 @@ DEVICE_CTC_MAX_BEAM = 64        # re2e_ctc_prefix_score: one thread per candidat
 HOST_CTC_SCORER = False         # tests: upstream's numpy CTCPrefixScore on the host instead (the arbiter of the device scorers)
 
 
+def _att_setup(p, prefix):
+    """The attention type of the parameter dict and its step's parameters (None where the type has none)."""
+    from .e2e_decoder import att_kind, att_params
+    kind = att_kind(p, prefix)
+    ap = att_params(p, prefix, kind)
+    return kind, ap
+
+
+def _att_step(kind, ap, pre, enc, z, state, hl, w_decT, nh, T, E, D, A, utt=None, U=0):
+    """One attention step for the ``nh`` live rows -> (context (nh,E), the rows' new attention state).  The state is what the search
+    gathers by ``parents`` beside z and c: the attention weights for ``location``, the row's own cov = cov_0 + w_0 + ... for the coverage
+    types (None = the uniform first row, made by the kernels), nothing for ``dot`` and ``add``.  ``utt`` (nh) / ``U``: the rows share U
+    utterances (re2e_*_fwd_rows) and ``hl`` (U) holds their frame counts; without it row r reads pre[r] / enc[r]."""
+    dev = z.device
+    w_new, cx = torch.empty(nh, T, device=dev), torch.empty(nh, E, device=dev)
+    dpj, e_scr = torch.empty(nh, A, device=dev), torch.empty(nh, T, device=dev)
+    st = state.data_ptr() if state is not None else None
+    if kind in ('location', 'coverage_location'):
+        C, Fh = ap['loc_conv'].shape[0], (ap['loc_conv'].shape[3] - 1) // 2
+        conv = torch.empty(nh, T, C, device=dev)
+        if utt is None:
+            call('re2e_attloc_fwd', pre.data_ptr(), enc.data_ptr(), z.data_ptr(), st, hl.data_ptr(), w_decT.data_ptr(), ap['mlp_att'].data_ptr(),
+                 ap['loc_conv'].data_ptr(), ap['gvec_w'].data_ptr(), ap['gvec_b'].data_ptr(), nh, T, E, D, A, C, Fh, w_new.data_ptr(), cx.data_ptr(), E,
+                 conv.data_ptr(), dpj.data_ptr(), e_scr.data_ptr())
+        else:
+            call('re2e_attloc_fwd_rows', pre.data_ptr(), enc.data_ptr(), U, hl.data_ptr(), utt.data_ptr(), z.data_ptr(), st, w_decT.data_ptr(),
+                 ap['mlp_att'].data_ptr(), ap['loc_conv'].data_ptr(), ap['gvec_w'].data_ptr(), ap['gvec_b'].data_ptr(), nh, T, E, D, A, C, Fh,
+                 w_new.data_ptr(), cx.data_ptr(), E, conv.data_ptr(), dpj.data_ptr(), e_scr.data_ptr())
+        if kind == 'location':
+            return cx, w_new
+        cov = torch.empty(nh, T, device=dev)
+        call('re2e_attstep_cov_add', st, w_new.data_ptr(), hl.data_ptr(), utt.data_ptr() if utt is not None else None, U if utt is not None else nh,
+             nh, T, cov.data_ptr())
+        return cx, cov
+    K = ATT_KINDS[kind]
+    opt = lambda k: ap[k].data_ptr() if k in ap else None
+    cov = torch.empty(nh, T, device=dev) if kind == 'coverage' else None
+    if utt is None:
+        call('re2e_attstep_fwd', K, pre.data_ptr(), enc.data_ptr(), z.data_ptr(), st, hl.data_ptr(), w_decT.data_ptr(), opt('mlp_dec_b'), opt('wvec_w'),
+             opt('wvec_b'), opt('gvec_w'), opt('gvec_b'), nh, T, E, D, A, w_new.data_ptr(), cx.data_ptr(), E, cov.data_ptr() if cov is not None else None,
+             dpj.data_ptr(), e_scr.data_ptr())
+    else:
+        call('re2e_attstep_fwd_rows', K, pre.data_ptr(), enc.data_ptr(), U, hl.data_ptr(), utt.data_ptr(), z.data_ptr(), st, w_decT.data_ptr(),
+             opt('mlp_dec_b'), opt('wvec_w'), opt('wvec_b'), opt('gvec_w'), opt('gvec_b'), nh, T, E, D, A, w_new.data_ptr(), cx.data_ptr(), E,
+             cov.data_ptr() if cov is not None else None, dpj.data_ptr(), e_scr.data_ptr())
+    return cx, cov
+
+
 def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=None):
     """``p``: reference-named decoder / attention Parameters; ``h``: (T, eprojs) encoder states of ONE utterance on the
     GPU; ``lpz``: (T, V) CTC log posteriors (numpy) or None; ``rnnlm``: a model.lm.ClassifierWithState on the same device or None
@@ -114,15 +162,15 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
     embed, w_ih, w_hh = p[prefix + 'dec.embed.weight'], p[prefix + 'dec.decoder.0.weight_ih'], p[prefix + 'dec.decoder.0.weight_hh']
     b_ih, b_hh = p[prefix + 'dec.decoder.0.bias_ih'], p[prefix + 'dec.decoder.0.bias_hh']
     out_w, out_b = p[prefix + 'dec.output.weight'], p[prefix + 'dec.output.bias']
-    mlp_dec, mlp_att = p[prefix + 'att.mlp_dec.weight'], p[prefix + 'att.mlp_att.weight']
-    loc_conv, gvec_w, gvec_b = p[prefix + 'att.loc_conv.weight'], p[prefix + 'att.gvec.weight'], p[prefix + 'att.gvec.bias']
+    kind, ap = _att_setup(p, prefix)
+    mlp_dec = ap['mlp_dec']
     V, Dd, D, A = out_w.shape[0], embed.shape[1], w_hh.shape[1], mlp_dec.shape[0]
-    C, Fh = loc_conv.shape[0], (loc_conv.shape[3] - 1) // 2
     ldw = Dd + E
     lm_weight = np.float32(recog_args.lm_weight) if rnnlm is not None else None
     lm_state = None
     with torch.no_grad():
-        pre1 = ops.linear(h.unsqueeze(0), p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'])   # (1,T,A)
+        pre1 = ops.linear(h.unsqueeze(0), p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'],
+                          act='tanh' if kind == 'dot' else None)                                               # (1,T,A)
         h_rep = h.unsqueeze(0).expand(beam, T, E).contiguous()          # every hypothesis attends over the same utterance
         pre_rep = pre1.expand(beam, T, A).contiguous()
         hl = lens_dev([T] * beam, dev)
@@ -149,11 +197,7 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
             ids = host_to_dev(ids_h, dev)
             emb = torch.empty(nh, Dd, device=dev)
             call('re2e_embedding_fwd', embed.data_ptr(), ids.data_ptr(), nh, Dd, emb.data_ptr(), Dd)
-            w_new, cx = torch.empty(nh, T, device=dev), torch.empty(nh, E, device=dev)
-            conv, dpj, e_scr = torch.empty(nh, T, C, device=dev), torch.empty(nh, A, device=dev), torch.empty(nh, T, device=dev)
-            call('re2e_attloc_fwd', pre_rep.data_ptr(), h_rep.data_ptr(), z.data_ptr(), a_prev.data_ptr() if a_prev is not None else None,
-                 hl.data_ptr(), w_decT.data_ptr(), mlp_att.data_ptr(), loc_conv.data_ptr(), gvec_w.data_ptr(), gvec_b.data_ptr(), nh, T, E, D, A,
-                 C, Fh, w_new.data_ptr(), cx.data_ptr(), E, conv.data_ptr(), dpj.data_ptr(), e_scr.data_ptr())
+            cx, a_new = _att_step(kind, ap, pre_rep, h_rep, z, a_prev, hl, w_decT, nh, T, E, D, A)
             gates = torch.empty(nh, 4 * D, device=dev)
             ops.gemm(emb, w_ih, gates, nh, 4 * D, Dd, transb=True, ldb=ldw, bias=b_ih, bias2=b_hh)
             ops.gemm(cx, w_ctx, gates, nh, 4 * D, E, transb=True, ldb=ldw, beta=1.0, dev=dev)
@@ -242,7 +286,8 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
             if not hyps:
                 break
             parents = host_to_dev(np.asarray([hp['parent'] for hp in hyps], np.int64), dev, torch.int64)
-            z, c, a_prev = z_new.index_select(0, parents), c_new.index_select(0, parents), w_new.index_select(0, parents)
+            z, c = z_new.index_select(0, parents), c_new.index_select(0, parents)
+            a_prev = a_new.index_select(0, parents) if a_new is not None else None
             if lm_state is not None:
                 lm_state = {key: v.index_select(0, parents) for key, v in lm_state.items()}
             if dev_ctc:                                                   # the survivors' CTC states, gathered on the device
@@ -284,10 +329,9 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
     embed, w_ih, w_hh = p[prefix + 'dec.embed.weight'], p[prefix + 'dec.decoder.0.weight_ih'], p[prefix + 'dec.decoder.0.weight_hh']
     b_ih, b_hh = p[prefix + 'dec.decoder.0.bias_ih'], p[prefix + 'dec.decoder.0.bias_hh']
     out_b = p[prefix + 'dec.output.bias']
-    mlp_dec, mlp_att = p[prefix + 'att.mlp_dec.weight'], p[prefix + 'att.mlp_att.weight']
-    loc_conv, gvec_w, gvec_b = p[prefix + 'att.loc_conv.weight'], p[prefix + 'att.gvec.weight'], p[prefix + 'att.gvec.bias']
+    kind, ap = _att_setup(p, prefix)
+    mlp_dec = ap['mlp_dec']
     Dd, D, A = embed.shape[1], w_hh.shape[1], mlp_dec.shape[0]
-    C, Fh = loc_conv.shape[0], (loc_conv.shape[3] - 1) // 2
     ldw = Dd + E
     lm_weight = np.float32(recog_args.lm_weight) if rnnlm is not None else None
     lm_state = None
@@ -298,7 +342,8 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
         enc, pre = torch.zeros(U, Tmax, E, device=dev), torch.zeros(U, Tmax, A, device=dev)
         for u, h in enumerate(hs):
             enc[u, :Ts[u]] = h
-            pre[u, :Ts[u]] = ops.linear(h.unsqueeze(0), p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'])[0]
+            pre[u, :Ts[u]] = ops.linear(h.unsqueeze(0), p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'],
+                                        act='tanh' if kind == 'dot' else None)[0]
         tl = lens_dev(Ts, dev)
         w_decT = torch.empty(D, A, device=dev)
         call('re2e_transpose01', mlp_dec.data_ptr(), w_decT.data_ptr(), A, D, 1)
@@ -335,11 +380,7 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
             hsc = host_to_dev(np.asarray([hp['score'] for _, hp in rows], np.float32), dev, torch.float32)
             emb = torch.empty(nh, Dd, device=dev)
             call('re2e_embedding_fwd', embed.data_ptr(), ids.data_ptr(), nh, Dd, emb.data_ptr(), Dd)
-            w_new, cx = torch.empty(nh, Tmax, device=dev), torch.empty(nh, E, device=dev)
-            conv, dpj, e_scr = torch.empty(nh, Tmax, C, device=dev), torch.empty(nh, A, device=dev), torch.empty(nh, Tmax, device=dev)
-            call('re2e_attloc_fwd_rows', pre.data_ptr(), enc.data_ptr(), U, tl.data_ptr(), utt.data_ptr(), z.data_ptr(),
-                 a_prev.data_ptr() if a_prev is not None else None, w_decT.data_ptr(), mlp_att.data_ptr(), loc_conv.data_ptr(), gvec_w.data_ptr(),
-                 gvec_b.data_ptr(), nh, Tmax, E, D, A, C, Fh, w_new.data_ptr(), cx.data_ptr(), E, conv.data_ptr(), dpj.data_ptr(), e_scr.data_ptr())
+            cx, a_new = _att_step(kind, ap, pre, enc, z, a_prev, tl, w_decT, nh, Tmax, E, D, A, utt=utt, U=U)
             gates = torch.empty(nh, 4 * D, device=dev)
             ops.gemm(emb, w_ih, gates, nh, 4 * D, Dd, transb=True, ldb=ldw, bias=b_ih, bias2=b_hh)
             ops.gemm(cx, w_ctx, gates, nh, 4 * D, E, transb=True, ldb=ldw, beta=1.0, dev=dev)
@@ -419,7 +460,8 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
             if not live:
                 break
             parents = host_to_dev(np.asarray(keep_rows, np.int64), dev, torch.int64)
-            z, c, a_prev = z_new.index_select(0, parents), c_new.index_select(0, parents), w_new.index_select(0, parents)
+            z, c = z_new.index_select(0, parents), c_new.index_select(0, parents)
+            a_prev = a_new.index_select(0, parents) if a_new is not None else None
             if lm_state is not None:
                 lm_state = {key: v.index_select(0, parents) for key, v in lm_state.items()}
             if joint:

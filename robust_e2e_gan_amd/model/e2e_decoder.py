@@ -27,6 +27,29 @@ class EmbeddingParams(torch.nn.Module):
         self.weight = torch.nn.Parameter(torch.randn(n, d))
 
 
+# the decoder loop's names (ops.DecoderLoopFn) of an attention's parameters <- their state_dict names under ``att.``
+ATT_PARAMS = {
+    'location': dict(mlp_dec='mlp_dec.weight', mlp_att='mlp_att.weight', loc_conv='loc_conv.weight', gvec_w='gvec.weight', gvec_b='gvec.bias'),
+    'coverage_location': dict(mlp_dec='mlp_dec.weight', mlp_att='mlp_att.weight', loc_conv='loc_conv.weight', gvec_w='gvec.weight', gvec_b='gvec.bias'),
+    'add': dict(mlp_dec='mlp_dec.weight', gvec_w='gvec.weight', gvec_b='gvec.bias'),
+    'coverage': dict(mlp_dec='mlp_dec.weight', wvec_w='wvec.weight', wvec_b='wvec.bias', gvec_w='gvec.weight', gvec_b='gvec.bias'),
+    'dot': dict(mlp_dec='mlp_dec.weight', mlp_dec_b='mlp_dec.bias'),
+}
+ATT_KIND = 'att.kind'        # key of the attention type in a parameter dict handed to decoder_forward_hip / the beam search
+
+
+def att_kind(p, prefix=''):
+    """The attention type of a parameter dict: what its owner wrote under ATT_KIND, ``location`` without it (callers from before the
+    other types existed)."""
+    return p.get(prefix + ATT_KIND, 'location')
+
+
+def att_params(p, prefix, kind):
+    if kind not in ATT_PARAMS:
+        raise Re2eError('attention type %r has no decoder step here (location, dot, add, coverage, coverage_location)' % (kind,))
+    return {k: p[prefix + 'att.' + name] for k, name in ATT_PARAMS[kind].items()}
+
+
 def decoder_forward_hip(p, hpad, hlens, ys, eos, ss_rate=0.0, return_att=False, prefix='', greedy=False, labeldist=None, lsm_weight=0.0):
     """Decoder pass on the GPU.  ``p`` maps reference state_dict names (att.* / dec.*) to Parameters; ``ys`` is a
     list of 1-D label tensors (host or device).  Teacher forced, except at the steps where scheduled sampling
@@ -47,11 +70,12 @@ def decoder_forward_hip(p, hpad, hlens, ys, eos, ss_rate=0.0, return_att=False, 
     ids_tm = host_to_dev(np.ascontiguousarray(ids_in.T).reshape(-1), dev)
     tgt_tm = host_to_dev(np.ascontiguousarray(ids_out.T).reshape(-1), dev)
     hmask = ops.mask_rows(hpad, hl_dev)                                            # :85
-    pre = ops.linear(hmask, p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'])
+    kind = att_kind(p, prefix)
+    # dot: the encoder side of the product is tanh(mlp_enc(h)), once per batch (AttDot.forward :111-112)
+    pre = ops.linear(hmask, p[prefix + 'att.mlp_enc.weight'], p[prefix + 'att.mlp_enc.bias'], act='tanh' if kind == 'dot' else None)
     Pm = dict(embed=p[prefix + 'dec.embed.weight'], w_ih=p[prefix + 'dec.decoder.0.weight_ih'], w_hh=p[prefix + 'dec.decoder.0.weight_hh'],
-              b_ih=p[prefix + 'dec.decoder.0.bias_ih'], b_hh=p[prefix + 'dec.decoder.0.bias_hh'], mlp_dec=p[prefix + 'att.mlp_dec.weight'],
-              mlp_att=p[prefix + 'att.mlp_att.weight'], loc_conv=p[prefix + 'att.loc_conv.weight'], gvec_w=p[prefix + 'att.gvec.weight'],
-              gvec_b=p[prefix + 'att.gvec.bias'])
+              b_ih=p[prefix + 'dec.decoder.0.bias_ih'], b_hh=p[prefix + 'dec.decoder.0.bias_hh'])
+    Pm.update(att_params(p, prefix, kind))
     if greedy:
         sample_steps = tuple(i > 0 for i in range(L1))
     else:
@@ -62,7 +86,7 @@ def decoder_forward_hip(p, hpad, hlens, ys, eos, ss_rate=0.0, return_att=False, 
         sample_steps = None
     ops.mark_grad(pre, 'pre (decoder loop bwd done)')
     ops.mark('decoder loop starts')
-    z_all, w_all = ops.decoder_loop(hmask, pre, ids_tm, hl_dev, L1, Pm, sample_steps)   # (L1,B,D), (L1,B,T)
+    z_all, w_all = ops.decoder_loop(hmask, pre, ids_tm, hl_dev, L1, Pm, sample_steps, False, kind)   # (L1,B,D), (L1,B,T)
     ops.mark('decoder loop fwd done')
     ops.mark_grad(z_all, 'decoder states (output layer + CE bwd done: loop bwd starts)')
     D = z_all.shape[2]
@@ -99,6 +123,7 @@ class Decoder(torch.nn.Module):
     def forward(self, hpad, hlen, ys, scheduled_sampling_rate=0.0, att_params=None):
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
         p.update({'att.' + k: v for k, v in self.att.named_parameters()})
+        p[ATT_KIND] = getattr(self.att, 'kind', 'location')
         if self.labeldist is not None and (self.vlabeldist is None or self.vlabeldist.device != hpad.device):
             self.vlabeldist = torch.as_tensor(np.asarray(self.labeldist), dtype=torch.float32).to(hpad.device).contiguous()
         loss, acc = decoder_forward_hip(p, hpad, hlen, ys, self.eos, scheduled_sampling_rate, labeldist=self.vlabeldist,
@@ -147,6 +172,7 @@ class Decoder(torch.nn.Module):
         from .beam_search import recognize_beam
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
         p.update({'att.' + k: v for k, v in self.att.named_parameters()})
+        p[ATT_KIND] = getattr(self.att, 'kind', 'location')
         lp = lpz.detach().cpu().numpy() if isinstance(lpz, torch.Tensor) else lpz
         return recognize_beam(p, h, lp, recog_args, self.eos, lpz_dev=lpz if isinstance(lpz, torch.Tensor) and lpz.is_cuda else None, rnnlm=rnnlm)
 
@@ -163,6 +189,7 @@ class Decoder(torch.nn.Module):
         from .beam_search import recognize_beam_batch
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
         p.update({'att.' + k: v for k, v in self.att.named_parameters()})
+        p[ATT_KIND] = getattr(self.att, 'kind', 'location')
         return recognize_beam_batch(p, [h.float().contiguous() for h in hs], lpzs, recog_args, self.eos, rnnlm=rnnlm)
 
     def calculate_all_attentions(self, hpad, hlen, ys):
@@ -170,6 +197,7 @@ class Decoder(torch.nn.Module):
         feeds the arg-max of its own previous output (:408-412), the labels only fix the number of steps."""
         p = {'dec.' + k: v for k, v in self.named_parameters() if not k.startswith('att.')}
         p.update({'att.' + k: v for k, v in self.att.named_parameters()})
+        p[ATT_KIND] = getattr(self.att, 'kind', 'location')
         with torch.no_grad():
             _, _, att = decoder_forward_hip(p, hpad, hlen, ys, self.eos, 0.0, return_att=True, greedy=True)
         return att.cpu().numpy()

@@ -8,7 +8,7 @@ import torch
 
 from .. import ops
 from ..lib import Re2eError
-from .e2e_attention import AttLoc
+from .e2e_attention import AttAdd, AttCov, AttCovLoc, AttDot, AttLoc
 from .e2e_common import ModelBase, host_to_dev, lecun_normal_init_parameters, lens_dev, lens_list, set_forget_bias_to_one, to_cuda
 from .e2e_ctc import CTC
 from .e2e_decoder import Decoder
@@ -36,9 +36,18 @@ class E2E(ModelBase):
         self.ctc = CTC(odim, args.eprojs, args.dropout_rate)
         if args.atype == 'location':
             self.att = AttLoc(args.eprojs, args.dunits, args.adim, args.aconv_chans, args.aconv_filts, 'softmax')
-        elif args.atype in ('noatt', 'dot', 'add', 'location2d', 'location_recurrent', 'coverage', 'coverage_location', 'multi_head_dot',
-                            'multi_head_add', 'multi_head_loc', 'multi_head_multi_res_loc'):
-            raise Re2eError('atype %s is out of scope: only the default location-aware attention is on the hot path' % args.atype)
+        elif args.atype == 'dot':
+            self.att = AttDot(args.eprojs, args.dunits, args.adim)
+        elif args.atype == 'add':
+            self.att = AttAdd(args.eprojs, args.dunits, args.adim)
+        elif args.atype == 'coverage':
+            self.att = AttCov(args.eprojs, args.dunits, args.adim)
+        elif args.atype == 'coverage_location':
+            self.att = AttCovLoc(args.eprojs, args.dunits, args.adim, args.aconv_chans, args.aconv_filts)
+        elif args.atype in ('noatt', 'location2d', 'location_recurrent', 'multi_head_dot', 'multi_head_add', 'multi_head_loc',
+                            'multi_head_multi_res_loc'):
+            raise Re2eError('atype %s is out of scope: location, dot, add, coverage and coverage_location (softmax attention activation) are '
+                            'the attention types on the hot path' % args.atype)
         else:
             logging.error('Error: need to specify an appropriate attention archtecture')
             sys.exit()

@@ -1794,12 +1794,20 @@ class DecoderLoopFn(torch.autograd.Function):
     ``w_grad``: the attention weights (L1,B,T), the second output, are only displayed by the model and leave the loop as a
     non-differentiable tensor.  With ``w_grad=True`` they are a differentiable output: an upstream gradient on them enters each
     step's softmax backward beside the recurrence's own (re2e_attloc_bwd's ``dw_in``), on the launch-per-step backward -- the
-    persistent reverse loop has no input for it."""
+    persistent reverse loop has no input for it.
+
+    ``kind``: the attention type of the step -- ``location`` (the default; the only one with a persistent form), ``dot``, ``add``,
+    ``coverage`` or ``coverage_location`` (csrc/attstep.hip; ``_att_loop_forward`` / ``_att_loop_backward`` below).  Their ``P`` holds the
+    type's own attention parameters: add: mlp_dec, gvec_w, gvec_b; coverage: these and wvec_w (A,1), wvec_b (A); dot: mlp_dec, mlp_dec_b
+    (and ``pre`` = tanh(mlp_enc(hmask))); coverage_location: location's."""
 
     @staticmethod
-    def forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps=None, w_grad=False):
+    def forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps=None, w_grad=False, kind='location'):
         _need_gpu(hmask)
         hmask, pre = _f32(hmask), _f32(pre)
+        ctx.kind = kind
+        if kind != 'location':
+            return _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, w_grad, kind)
         dev = hmask.device
         B, T, E = hmask.shape
         A = pre.shape[2]
@@ -1871,6 +1879,8 @@ class DecoderLoopFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dZ, dW):
+        if ctx.kind != 'location':
+            return _att_loop_backward(ctx, dZ, dW)
         hmask, pre, emb, cx, z, c, w, gates, conv, dpj = ctx.saved_tensors
         Pm = ctx.Pm
         B, T, E, A, Dd, D, C, Fh, L1 = ctx.dims
@@ -1980,7 +1990,199 @@ class DecoderLoopFn(torch.autograd.Function):
                     with accumulate(Pm[k]) as (gt, beta):
                         call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
                     off += n
-        return d_enc, d_pre, None, None, None, None, None, None
+        return d_enc, d_pre, None, None, None, None, None, None, None
+
+
+def _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, w_grad, kind):
+    """DecoderLoopFn.forward for the attention types other than ``location``: the launch-per-step sequence with the type's own step
+    (re2e_attstep_fwd; coverage_location: re2e_attloc_fwd reading cov as att_prev, then cov + w).  cov (L1,B,T) holds cov_{i+1} at
+    index i: step i reads cov[i-1], step 0 the uniform cov_0 the kernels make themselves."""
+    if kind not in lib.ATT_KINDS:
+        raise lib.Re2eError('DecoderLoopFn: unknown attention kind %r' % (kind,))
+    K = lib.ATT_KINDS[kind]
+    dev = hmask.device
+    B, T, E = hmask.shape
+    A = pre.shape[2]
+    Dd = Pm['embed'].shape[1]
+    D = Pm['w_hh'].shape[1]
+    covloc = kind == 'coverage_location'
+    C, Fh = (Pm['loc_conv'].shape[0], (Pm['loc_conv'].shape[3] - 1) // 2) if covloc else (0, 0)
+    M = L1 * B
+    w_ih = Pm['w_ih']
+    ldw = Dd + E
+    emb = empty((L1, B, Dd), hmask)
+    call('re2e_embedding_fwd', Pm['embed'].data_ptr(), ids_tm.data_ptr(), M, Dd, emb.data_ptr(), Dd)
+    gates = empty((L1, B, 4 * D), hmask)
+    gemm(emb, w_ih, gates, M, 4 * D, Dd, transb=True, ldb=ldw, bias=Pm['b_ih'], bias2=Pm['b_hh'])
+    cx = empty((L1, B, E), hmask)
+    z = zeros((L1 + 1, B, D), hmask)
+    c = zeros((L1 + 1, B, D), hmask)
+    w = empty((L1, B, T), hmask)
+    w_ctx = w_ih.data_ptr() + 4 * Dd
+    w_decT = empty((D, A), hmask)
+    call('re2e_transpose01', Pm['mlp_dec'].data_ptr(), w_decT.data_ptr(), A, D, 1)
+    has_cov = kind in ('coverage', 'coverage_location')
+    cov = empty((L1, B, T), hmask) if has_cov else None
+    conv = empty((L1, B, T, C), hmask) if covloc else None
+    dpj = empty((L1, B, A), hmask)
+    e_scr = empty((B, T), hmask)
+    fused = DECODER_FUSED and E % 4 == 0 and D % 4 == 0 and ldw % 4 == 0
+    sampled = sample_steps is not None and any(sample_steps[1:])
+    if sampled:
+        ids_tm = ids_tm.clone()                 # becomes the list of tokens actually fed
+        V = Pm['out_w'].shape[0]
+        logits = empty((B, V), hmask)
+    opt = lambda k: Pm[k].data_ptr() if k in Pm else None
+    for i in range(L1):
+        if sampled and i > 0 and sample_steps[i]:
+            gemm(z[i], Pm['out_w'], logits, B, V, D, transb=True, bias=Pm['out_b'])
+            ids_i = ids_tm.data_ptr() + 4 * i * B
+            call('re2e_argmax_rows', logits.data_ptr(), B, V, V, ids_i)
+            call('re2e_embedding_fwd', Pm['embed'].data_ptr(), ids_i, B, Dd, emb[i].data_ptr(), Dd)
+            gemm(emb[i], w_ih, gates[i], B, 4 * D, Dd, transb=True, ldb=ldw, bias=Pm['b_ih'], bias2=Pm['b_hh'])
+        cov_in = cov[i - 1].data_ptr() if (has_cov and i > 0) else None
+        if covloc:
+            call('re2e_attloc_fwd', pre.data_ptr(), hmask.data_ptr(), z[i].data_ptr(), cov_in, hlens_dev.data_ptr(), w_decT.data_ptr(),
+                 Pm['mlp_att'].data_ptr(), Pm['loc_conv'].data_ptr(), Pm['gvec_w'].data_ptr(), Pm['gvec_b'].data_ptr(), B, T, E, D, A, C, Fh,
+                 w[i].data_ptr(), cx[i].data_ptr(), E, conv[i].data_ptr(), dpj[i].data_ptr(), e_scr.data_ptr())
+            call('re2e_attstep_cov_add', cov_in, w[i].data_ptr(), hlens_dev.data_ptr(), None, B, B, T, cov[i].data_ptr())
+        else:
+            call('re2e_attstep_fwd', K, pre.data_ptr(), hmask.data_ptr(), z[i].data_ptr(), cov_in, hlens_dev.data_ptr(), w_decT.data_ptr(),
+                 opt('mlp_dec_b'), opt('wvec_w'), opt('wvec_b'), opt('gvec_w'), opt('gvec_b'), B, T, E, D, A, w[i].data_ptr(), cx[i].data_ptr(), E,
+                 cov[i].data_ptr() if has_cov else None, dpj[i].data_ptr(), e_scr.data_ptr())
+        if fused:
+            call('re2e_dec_gates_cell_fwd', cx[i].data_ptr(), z[i].data_ptr(), w_ctx, ldw, Pm['w_hh'].data_ptr(), gates[i].data_ptr(),
+                 c[i].data_ptr(), c[i + 1].data_ptr(), z[i + 1].data_ptr(), B, E, D)
+        else:
+            gemm(cx[i], w_ctx, gates[i], B, 4 * D, E, transb=True, ldb=ldw, beta=1.0, dev=dev)
+            gemm(z[i], Pm['w_hh'], gates[i], B, 4 * D, D, transb=True, beta=1.0)
+            call('re2e_lstm_cell_fwd', gates[i].data_ptr(), c[i].data_ptr(), c[i + 1].data_ptr(), z[i + 1].data_ptr(), B, D)
+    ctx.Pm, ctx.ids, ctx.hlens = Pm, ids_tm, hlens_dev
+    ctx.persist = False
+    ctx.dims = (B, T, E, A, Dd, D, C, Fh, L1)
+    ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, dpj, *([cov] if has_cov else []), *([conv] if covloc else []))
+    ctx.w_grad = bool(w_grad)
+    if w_grad:
+        ctx.set_materialize_grads(False)
+    else:
+        ctx.mark_non_differentiable(w)
+    return z[1:], w
+
+
+def _att_loop_backward(ctx, dZ, dW):
+    """The reverse loop of ``_att_loop_forward``.  Coverage types: step k hands back d cov_k, which reaches every w_j with j < k, so the
+    loop carries G = sum_{k > i} d cov_k as the ``dw_in`` of step i (plus dW[i] under w_grad); d cov_0 is dropped, cov_0 is a constant."""
+    kind = ctx.kind
+    K = lib.ATT_KINDS[kind]
+    covloc, has_cov = kind == 'coverage_location', kind in ('coverage', 'coverage_location')
+    saved = list(ctx.saved_tensors)
+    hmask, pre, emb, cx, z, c, w, gates, dpj = saved[:9]
+    cov = saved[9] if has_cov else None
+    conv = saved[10] if covloc else None
+    Pm = ctx.Pm
+    B, T, E, A, Dd, D, C, Fh, L1 = ctx.dims
+    dev = hmask.device
+    dZ = _f32(dZ) if dZ is not None else zeros((L1, B, D), hmask)
+    dW = _f32(dW) if (ctx.w_grad and dW is not None) else None
+    w_ih = Pm['w_ih']
+    ldw = Dd + E
+    w_ctx = w_ih.data_ptr() + 4 * Dd
+    d_pre = empty((B, T, A), hmask)
+    de_all = empty((L1, B, T), hmask)
+    d_enc = empty((B, T, E), hmask)
+    if covloc:
+        npart = query('re2e_attloc_partial_floats', A, C, Fh)
+        awsb = query('re2e_attloc_workspace_bytes', B, T, A, C)
+    else:
+        npart = query('re2e_attstep_partial_floats', K, A)
+        awsb = query('re2e_attstep_workspace_bytes', K, B, T, A)
+    partials = zeros((B, max(npart, 1)), hmask)
+    ddp = empty((L1, B, A), hmask)
+    d_cx_all = empty((L1, B, E), hmask)
+    aws = workspace(awsb, dev, 'attloc')
+    dz_carry = zeros((B, D), hmask)
+    dc_a, dc_b = zeros((B, D), hmask), empty((B, D), hmask)
+    G = zeros((B, T), hmask) if has_cov else None              # sum of the d cov_k of the steps already done
+    d_cov = empty((B, T), hmask) if has_cov else None
+    dw_sum = empty((B, T), hmask) if (has_cov and dW is not None) else None
+    fused = DECODER_FUSED and B <= 32
+    opt = lambda k: Pm[k].data_ptr() if k in Pm else None
+    for i in range(L1 - 1, -1, -1):
+        d_cx = d_cx_all[i]
+        if fused:
+            call('re2e_lstm_cell_bwd', gates[i].data_ptr(), c[i].data_ptr(), c[i + 1].data_ptr(), dz_carry.data_ptr(), dZ[i].data_ptr(),
+                 dc_a.data_ptr(), dc_b.data_ptr(), B, D)
+            dc_a, dc_b = dc_b, dc_a
+            call('re2e_gemm_skinny2', B, 4 * D, gates[i].data_ptr(), 4 * D, w_ctx, ldw, E, d_cx.data_ptr(), E, Pm['w_hh'].data_ptr(), D, D,
+                 dz_carry.data_ptr(), D)
+        else:
+            call('re2e_axpby', 1.0, dZ[i].data_ptr(), 1.0, dz_carry.data_ptr(), B * D)
+            call('re2e_lstm_cell_bwd', gates[i].data_ptr(), c[i].data_ptr(), c[i + 1].data_ptr(), dz_carry.data_ptr(), None, dc_a.data_ptr(),
+                 dc_b.data_ptr(), B, D)
+            dc_a, dc_b = dc_b, dc_a
+            gemm(gates[i], w_ctx, d_cx, B, E, 4 * D, ldb=ldw, dev=dev)
+            gemm(gates[i], Pm['w_hh'], dz_carry, B, D, 4 * D)
+        if not has_cov:
+            dw_in = dW[i].data_ptr() if dW is not None else None
+        elif dW is None:
+            dw_in = G.data_ptr() if i < L1 - 1 else None       # (nothing has been added to G before the last step)
+        else:
+            call('re2e_axpby', 1.0, dW[i].data_ptr(), 0.0, dw_sum.data_ptr(), B * T)
+            call('re2e_axpby', 1.0, G.data_ptr(), 1.0, dw_sum.data_ptr(), B * T)
+            dw_in = dw_sum.data_ptr()
+        cov_in = cov[i - 1].data_ptr() if (has_cov and i > 0) else None
+        d_cov_out = d_cov.data_ptr() if (has_cov and i > 0) else None
+        if covloc:
+            call('re2e_attloc_bwd', pre.data_ptr(), hmask.data_ptr(), cov_in, w[i].data_ptr(), ctx.hlens.data_ptr(), Pm['mlp_att'].data_ptr(),
+                 Pm['loc_conv'].data_ptr(), Pm['gvec_w'].data_ptr(), conv[i].data_ptr(), dpj[i].data_ptr(), cx[i].data_ptr(), d_cx.data_ptr(), E,
+                 dw_in, B, T, E, A, C, Fh, de_all[i].data_ptr(), d_cov_out, ddp[i].data_ptr(), partials.data_ptr(), aws.data_ptr(), awsb)
+        else:
+            call('re2e_attstep_bwd', K, pre.data_ptr(), hmask.data_ptr(), cov_in, w[i].data_ptr(), ctx.hlens.data_ptr(), opt('wvec_w'),
+                 opt('wvec_b'), opt('gvec_w'), dpj[i].data_ptr(), cx[i].data_ptr(), d_cx.data_ptr(), E, dw_in, B, T, E, A,
+                 de_all[i].data_ptr(), d_cov_out, ddp[i].data_ptr(), aws.data_ptr(), awsb)
+        if d_cov_out is not None:
+            call('re2e_axpby', 1.0, d_cov.data_ptr(), 1.0, G.data_ptr(), B * T)
+        gemm(ddp[i], Pm['mlp_dec'], dz_carry, B, D, A, beta=1.0)
+    call('re2e_attloc_denc', w.data_ptr(), d_cx_all.data_ptr(), L1, B, T, E, d_enc.data_ptr(), 0.0)
+    if covloc:
+        call('re2e_attloc_dpre', pre.data_ptr(), conv.data_ptr(), dpj.data_ptr(), de_all.data_ptr(), Pm['mlp_att'].data_ptr(), Pm['gvec_w'].data_ptr(),
+             L1, B, T, A, C, Fh, d_pre.data_ptr(), partials.data_ptr(), aws.data_ptr(), awsb)
+        plist = (('gvec_w', A), ('gvec_b', 1), ('mlp_att', A * C), ('loc_conv', C * (2 * Fh + 1)))
+    else:
+        call('re2e_attstep_dpre', K, pre.data_ptr(), cov.data_ptr() if has_cov else None, ctx.hlens.data_ptr(), dpj.data_ptr(), de_all.data_ptr(),
+             opt('wvec_w'), opt('wvec_b'), opt('gvec_w'), L1, B, T, A, d_pre.data_ptr(), partials.data_ptr(), aws.data_ptr(), awsb)
+        plist = {'dot': (), 'add': (('gvec_w', A), ('gvec_b', 1)), 'coverage': (('gvec_w', A), ('gvec_b', 1), ('wvec_w', A), ('wvec_b', A))}[kind]
+    M = L1 * B
+    G2, zp2 = gates.view(M, 4 * D), z[:L1].reshape(M, D)
+    if w_ih.requires_grad:
+        with param_grads(gates, z, emb, cx, ddp, partials):
+            with accumulate(w_ih) as (gw, beta):
+                gemm(G2, emb.view(M, Dd), gw, 4 * D, Dd, M, transa=True, ldc=ldw, beta=beta)
+                gemm(G2, cx.view(M, E), gw.data_ptr() + 4 * Dd, 4 * D, E, M, transa=True, ldc=ldw, beta=beta)
+            with accumulate(Pm['w_hh']) as (gw, beta):
+                gemm(G2, zp2, gw, 4 * D, D, M, transa=True, beta=beta)
+            for k in ('b_ih', 'b_hh'):
+                with accumulate(Pm[k]) as (gb, beta):
+                    colsum_into(G2, M, 4 * D, gb, beta)
+            with accumulate(Pm['mlp_dec']) as (gw, beta):
+                gemm(ddp.view(M, A), zp2, gw, A, D, M, transa=True, beta=beta)
+            if kind == 'dot':
+                with accumulate(Pm['mlp_dec_b']) as (gb, beta):
+                    colsum_into(ddp.view(M, A), M, A, gb, beta)
+            d_emb = empty((M, Dd), hmask)
+            gemm(G2, w_ih, d_emb, M, Dd, 4 * D, ldb=ldw)
+            V = Pm['embed'].shape[0]
+            with accumulate(Pm['embed']) as (gw, beta):
+                call('re2e_embedding_bwd', d_emb.data_ptr(), Dd, ctx.ids.data_ptr(), M, Dd, V, gw.data_ptr(), beta)
+            if plist:
+                tot = empty((npart,), hmask)
+                colsum_into(partials, B, npart, tot, 0.0)
+                off = 0
+                for k, n in plist:
+                    with accumulate(Pm[k]) as (gt, beta):
+                        call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
+                    off += n
+    return d_enc, d_pre, None, None, None, None, None, None, None
 
 
 decoder_loop = DecoderLoopFn.apply
