@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 330
+#define RE2E_ABI_VERSION 331
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -413,6 +413,25 @@ int re2e_lstm_cell_bwd(float* gates, const float* c_prev, const float* c_cur, co
  * activated gates out, c_prev -> c_out, h_out.  E, D, ldw multiples of 4. */
 int re2e_dec_gates_cell_fwd(const float* cx, const float* z_prev, const float* w_ctx, long ldw, const float* w_hh, float* gates,
                             const float* c_prev, float* c_out, float* h_out, int B, int E, int D, re2e_stream_t stream);
+/* ---- upper layers of a multi-layer decoder (dlayers > 1, e2e_decoder.py:121-152; csrc/decstack.hip) ----
+ * Layer l >= 1 is an LSTMCell (D -> D, torch gate order) on the state of the layer below at the same token and on its own previous state.  fp32;
+ * D % 4 == 0 and D <= 1024, any row count: RE2E_EUNSUPPORTED beyond.  No kernel waits on another workgroup.
+ * re2e_dec_upper_step: one token for n rows in one launch: gates = b_ih + b_hh + x W_ih^T + z_prev W_hh^T, then the cell -> z_out, c_out (n,D) and,
+ * if gates != NULL, the activated gates (n,4D).  A row's result does not depend on the other rows of the launch (bit for bit).
+ * re2e_dec_gates_cell_fwd was not reused for it: it needs the gates pre-filled with the biases by another launch. */
+int re2e_dec_upper_step(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* z_prev,
+                        const float* c_prev, float* gates, float* z_out, float* c_out, int n, int D, re2e_stream_t stream);
+/* Teacher-forced recurrence of one upper layer over L1 tokens, one launch per token: gates (L1,B,4D) holds z_below W_ih^T + b_ih + b_hh on entry
+ * (ONE re2e_gemm over all L1 * B rows) and the activated gates on return; per token gates[i] += z[i] W_hh^T, then the cell -> z[i+1], c[i+1].
+ * z, c (L1+1,B,D) with block 0 = the initial state (zeros). */
+int re2e_dec_upper_seq_fwd(float* gates, const float* w_hh, float* z, float* c, int L1, int B, int D, re2e_stream_t stream);
+/* Its backward, tokens L1-1 .. 0, one launch per token: the cell backward (dh = carried + dZ[i], dc) -> dG[i] (pre-activation d gates, a buffer
+ * of its own: every workgroup reads gates[i]), dc_prev, and the carried dz_prev = dG[i] W_hh in the same launch.  w_hhT (D,4D) = W_hh transposed
+ * (re2e_transpose01).  The products over the whole sequence (d z_below = dG W_ih, d W_ih = dG^T z_below, d W_hh = dG^T z[0:L1], d b = column sums
+ * of dG) are the caller's, on re2e_gemm / re2e_colsum.  Workspace: re2e_dec_upper_bwd_workspace_bytes(B, D). */
+size_t re2e_dec_upper_bwd_workspace_bytes(int B, int D);
+int re2e_dec_upper_seq_bwd(const float* gates, const float* c, const float* dZ, const float* w_hhT, float* dG, int L1, int B, int D, void* workspace,
+                           size_t workspace_bytes, re2e_stream_t stream);
 /* The whole teacher-forced decoder loop (e2e_decoder.py:113-152: AttLoc.forward e2e_attention.py:259-299 + LSTMCell per output token) as ONE
  * persistent launch (csrc/decloop.hip).  re2e_dec_loop_workspace_bytes returns 0 when the shape is outside the resident form's limits
  * (forward: B <= 32, D <= 320, E <= 512, D, E, A multiples of 4, C <= 12, T <= 2048; backward: E <= 512 and a multiple of 16, C <= 16,

@@ -5,7 +5,9 @@ is what the MFMA pipes are asked to do by the launch the step REALLY makes: prod
 (re2e_gemm_nt_rows / _tn_rows), row-limited Winograd launches count the rows below their limits, Winograd launches count the transformed-domain
 products (F(2x2,3x3): 16 multiply-adds per 2x2 outputs instead of 36; F(2x2,4x4): 25 instead of 64), recurrences count h W_hh^T per live-or-not
 (t, b) (the chains multiply all B rows at every step).  Not counted (together < 0.5 % of a config-4 step): the decoder loop's per-token products,
-AttLoc, the tile padding of edge tiles.  Cross-check: profiles/r06_step_pmc.json (SQ_VALU_MFMA_BUSY_CYCLES x 64 FLOP per cycle and SIMD)."""
+AttLoc, the tile padding of edge tiles.  A decoder of more than one layer (dlayers > 1) adds, per upper layer, the input projection and the four
+whole-sequence gradient products, counted as the re2e_gemm calls they are; its per-token recurrent products (csrc/decstack.hip) run on the vector
+ALUs and are not matrix-core work.  Cross-check: profiles/r06_step_pmc.json (SQ_VALU_MFMA_BUSY_CYCLES x 64 FLOP per cycle and SIMD)."""
 import contextlib
 
 from . import lib

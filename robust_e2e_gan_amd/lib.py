@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 330      # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 331     # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -107,6 +107,10 @@ SIGNATURES = {
     're2e_lstm_cell_fwd': (I, [P, P, P, P, I, I, P]),
     're2e_lstm_cell_bwd': (I, [P, P, P, P, P, P, P, I, I, P]),
     're2e_dec_gates_cell_fwd': (I, [P, P, P, L, P, P, P, P, P, I, I, I, P]),
+    're2e_dec_upper_step': (I, [P, P, P, P, P, P, P, P, P, P, I, I, P]),
+    're2e_dec_upper_seq_fwd': (I, [P, P, P, P, I, I, I, P]),
+    're2e_dec_upper_bwd_workspace_bytes': (Z, [I, I]),
+    're2e_dec_upper_seq_bwd': (I, [P, P, P, P, P, I, I, I, P, Z, P]),
     're2e_gemm_skinny2': (I, [I, I, P, L, P, L, I, P, L, P, L, I, P, L, P]),
     're2e_dec_loop_workspace_bytes': (Z, [I, I, I, I, I, I, I, I]),
     're2e_dec_loop_bwd_workspace_bytes': (Z, [I, I, I, I, I, I, I, I]),

@@ -25,6 +25,10 @@ The LM may also be a word-level one (model/extlm.py: LookAheadWordLM, MultiLevel
 per-row tensors like the RNNLM's and takes the same gather; it is handed the labels of the position as the host array they were uploaded from
 (``labels=``), so that it knows which rows stand at a <space> -- the only ones its word LM advances for -- without a device->host copy.
 
+Decoders of more than one layer (dlayers > 1): the attention step and the first LSTMCell are layer 0's, as for one layer; the layers above advance
+by one launch each per position (ops.dec_upper_step: re2e_dec_upper_step, whose rows do not depend on each other bit for bit), the output layer reads
+the top one, and every layer's (z_l, c_l) follows the survivors through the ``parents`` gather.  With one layer nothing is launched that was not.
+
 Several utterances per search (``recognize_beam_batch``, E2E.recognize_batch): one loop over output positions drives all unfinished
 utterances.  The rows of a position are their live hypotheses, grouped by utterance; an utterance whose own ``end_detect`` fires, whose
 hypotheses run out or that reaches its own ``maxlen`` leaves and its rows are compacted away.  The encoder states and ``mlp_enc`` projections
@@ -152,6 +156,25 @@ def _att_step(kind, ap, pre, enc, z, state, hl, w_decT, nh, T, E, D, A, utt=None
     return cx, cov
 
 
+def _upper_setup(p, prefix):
+    """The decoder layers above layer 0 (dlayers > 1): one dict of w_ih, w_hh, b_ih, b_hh per layer; empty for a single-layer decoder."""
+    from .e2e_decoder import upper_layers
+    return upper_layers(p, prefix)
+
+
+def _upper_step(upper, state, z0, nh, D):
+    """One position of the upper layers for the ``nh`` live rows, one launch per layer (ops.dec_upper_step: re2e_dec_upper_step): layer l reads
+    the new state of the layer below and its own (z_l, c_l) of ``state`` -> the rows' new [(z_l, c_l)], gathered by ``parents`` beside the
+    attention state."""
+    new, x = [], z0
+    for lay, (zl, cl) in zip(upper, state):
+        zn, cn = torch.empty(nh, D, device=z0.device), torch.empty(nh, D, device=z0.device)
+        ops.dec_upper_step(lay, x, zl, cl, zn, cn, nh, D)
+        new.append((zn, cn))
+        x = zn
+    return new
+
+
 def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=None):
     """``p``: reference-named decoder / attention Parameters; ``h``: (T, eprojs) encoder states of ONE utterance on the
     GPU; ``lpz``: (T, V) CTC log posteriors (numpy) or None; ``rnnlm``: a model.lm.ClassifierWithState on the same device or None
@@ -163,6 +186,7 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
     b_ih, b_hh = p[prefix + 'dec.decoder.0.bias_ih'], p[prefix + 'dec.decoder.0.bias_hh']
     out_w, out_b = p[prefix + 'dec.output.weight'], p[prefix + 'dec.output.bias']
     kind, ap = _att_setup(p, prefix)
+    upper = _upper_setup(p, prefix)
     mlp_dec = ap['mlp_dec']
     V, Dd, D, A = out_w.shape[0], embed.shape[1], w_hh.shape[1], mlp_dec.shape[0]
     ldw = Dd + E
@@ -190,6 +214,7 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
                 lpz_d = lpz_dev.float().contiguous() if lpz_dev is not None else torch.from_numpy(np.ascontiguousarray(lpz, np.float32)).to(dev)
                 r_prev = torch.from_numpy(hyps[0].pop('ctc_state')).to(dev).view(1, T, 2)      # states stay on the device from here on
         z, c, a_prev = torch.zeros(1, D, device=dev), torch.zeros(1, D, device=dev), None
+        up_state = [(torch.zeros(1, D, device=dev), torch.zeros(1, D, device=dev)) for _ in upper]
         ended = []
         for i in range(maxlen):
             nh = len(hyps)
@@ -204,8 +229,10 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
             ops.gemm(z, w_hh, gates, nh, 4 * D, D, transb=True, beta=1.0)
             z_new, c_new = torch.empty(nh, D, device=dev), torch.empty(nh, D, device=dev)
             call('re2e_lstm_cell_fwd', gates.data_ptr(), c.data_ptr(), c_new.data_ptr(), z_new.data_ptr(), nh, D)
+            up_new = _upper_step(upper, up_state, z_new, nh, D)
+            z_top = up_new[-1][0] if upper else z_new
             logits, lsm = torch.empty(nh, V, device=dev), torch.empty(nh, V, device=dev)
-            ops.gemm(z_new, out_w, logits, nh, V, D, transb=True, bias=out_b)
+            ops.gemm(z_top, out_w, logits, nh, V, D, transb=True, bias=out_b)
             call('re2e_log_softmax_rows', logits.data_ptr(), nh, V, V, lsm.data_ptr())
             if rnnlm is not None:
                 # att + lm_weight * lm over all V labels is what an attention-only search ranks (e2e_decoder.py:272,291); with CTC only the
@@ -288,6 +315,7 @@ def recognize_beam(p, h, lpz, recog_args, eos, prefix='', lpz_dev=None, rnnlm=No
             parents = host_to_dev(np.asarray([hp['parent'] for hp in hyps], np.int64), dev, torch.int64)
             z, c = z_new.index_select(0, parents), c_new.index_select(0, parents)
             a_prev = a_new.index_select(0, parents) if a_new is not None else None
+            up_state = [(zl.index_select(0, parents), cl.index_select(0, parents)) for zl, cl in up_new]
             if lm_state is not None:
                 lm_state = {key: v.index_select(0, parents) for key, v in lm_state.items()}
             if dev_ctc:                                                   # the survivors' CTC states, gathered on the device
@@ -330,6 +358,7 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
     b_ih, b_hh = p[prefix + 'dec.decoder.0.bias_ih'], p[prefix + 'dec.decoder.0.bias_hh']
     out_b = p[prefix + 'dec.output.bias']
     kind, ap = _att_setup(p, prefix)
+    upper = _upper_setup(p, prefix)
     mlp_dec = ap['mlp_dec']
     Dd, D, A = embed.shape[1], w_hh.shape[1], mlp_dec.shape[0]
     ldw = Dd + E
@@ -364,6 +393,7 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
             r_prev = torch.from_numpy(r0).to(dev)
         live = list(range(U))
         z, c, a_prev = torch.zeros(U, D, device=dev), torch.zeros(U, D, device=dev), None
+        up_state = [(torch.zeros(U, D, device=dev), torch.zeros(U, D, device=dev)) for _ in upper]
         i = 0
         while live:
             rows = [(u, hp) for u in live for hp in hyps[u]]
@@ -387,8 +417,10 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
             ops.gemm(z, w_hh, gates, nh, 4 * D, D, transb=True, beta=1.0)
             z_new, c_new = torch.empty(nh, D, device=dev), torch.empty(nh, D, device=dev)
             call('re2e_lstm_cell_fwd', gates.data_ptr(), c.data_ptr(), c_new.data_ptr(), z_new.data_ptr(), nh, D)
+            up_new = _upper_step(upper, up_state, z_new, nh, D)
+            z_top = up_new[-1][0] if upper else z_new
             logits, lsm = torch.empty(nh, V, device=dev), torch.empty(nh, V, device=dev)
-            ops.gemm(z_new, out_w, logits, nh, V, D, transb=True, bias=out_b)
+            ops.gemm(z_top, out_w, logits, nh, V, D, transb=True, bias=out_b)
             call('re2e_log_softmax_rows', logits.data_ptr(), nh, V, V, lsm.data_ptr())
             if rnnlm is not None:
                 lm_state, lm_lp, att_lm = rnnlm.predict_combined(lm_state, ids, lsm if not joint else None, lm_weight, labels=meta[0])
@@ -462,6 +494,7 @@ def recognize_beam_batch(p, hs, lpzs, recog_args, eos, prefix='', rnnlm=None):
             parents = host_to_dev(np.asarray(keep_rows, np.int64), dev, torch.int64)
             z, c = z_new.index_select(0, parents), c_new.index_select(0, parents)
             a_prev = a_new.index_select(0, parents) if a_new is not None else None
+            up_state = [(zl.index_select(0, parents), cl.index_select(0, parents)) for zl, cl in up_new]
             if lm_state is not None:
                 lm_state = {key: v.index_select(0, parents) for key, v in lm_state.items()}
             if joint:

@@ -50,11 +50,24 @@ def att_params(p, prefix, kind):
     return {k: p[prefix + 'att.' + name] for k, name in ATT_PARAMS[kind].items()}
 
 
+def upper_layers(p, prefix=''):
+    """The decoder layers above layer 0 of a parameter dict, as ops.DecoderLoopFn / DecoderUpperFn / the beam search take them: one dict
+    (w_ih, w_hh, b_ih, b_hh) per ``dec.decoder.{l}``, l = 1, 2, ... as far as the dict has them (none: a single-layer decoder)."""
+    lays, l = [], 1
+    while prefix + 'dec.decoder.%d.weight_ih' % l in p:
+        q = prefix + 'dec.decoder.%d.' % l
+        lays.append(dict(w_ih=p[q + 'weight_ih'], w_hh=p[q + 'weight_hh'], b_ih=p[q + 'bias_ih'], b_hh=p[q + 'bias_hh']))
+        l += 1
+    return lays
+
+
 def decoder_forward_hip(p, hpad, hlens, ys, eos, ss_rate=0.0, return_att=False, prefix='', greedy=False, labeldist=None, lsm_weight=0.0):
     """Decoder pass on the GPU.  ``p`` maps reference state_dict names (att.* / dec.*) to Parameters; ``ys`` is a
     list of 1-D label tensors (host or device).  Teacher forced, except at the steps where scheduled sampling
     fires (e2e_decoder.py:123: ``random.random() < rate and i > 0`` -- one draw of Python's RNG per step, for the
-    whole batch) or, with ``greedy`` (calculate_all_attentions :408-412), at every step i > 0."""
+    whole batch) or, with ``greedy`` (calculate_all_attentions :408-412), at every step i > 0.  With ``dec.decoder.1.*`` ... in ``p`` (dlayers > 1)
+    the layers above layer 0 follow the loop (teacher forced: ops.DecoderUpperFn on the loop's states) or run inside it (sampled steps: the fed
+    token is the arg-max of the output layer on the TOP layer's state); logits, loss and accuracy read the top layer."""
     dev = hpad.device
     B, T, E = hpad.shape
     hl = lens_list(hlens)
@@ -86,7 +99,14 @@ def decoder_forward_hip(p, hpad, hlens, ys, eos, ss_rate=0.0, return_att=False, 
         sample_steps = None
     ops.mark_grad(pre, 'pre (decoder loop bwd done)')
     ops.mark('decoder loop starts')
-    z_all, w_all = ops.decoder_loop(hmask, pre, ids_tm, hl_dev, L1, Pm, sample_steps, False, kind)   # (L1,B,D), (L1,B,T)
+    upper = upper_layers(p, prefix)
+    if not upper:
+        z_all, w_all = ops.decoder_loop(hmask, pre, ids_tm, hl_dev, L1, Pm, sample_steps, False, kind)   # (L1,B,D), (L1,B,T)
+    elif sample_steps is None:
+        z0, w_all = ops.decoder_loop(hmask, pre, ids_tm, hl_dev, L1, Pm, None, False, kind)              # layer 0 keeps its loop
+        z_all = ops.decoder_upper(z0, upper)
+    else:
+        z_all, w_all = ops.decoder_loop(hmask, pre, ids_tm, hl_dev, L1, Pm, sample_steps, False, kind, upper)
     ops.mark('decoder loop fwd done')
     ops.mark_grad(z_all, 'decoder states (output layer + CE bwd done: loop bwd starts)')
     D = z_all.shape[2]
@@ -106,12 +126,12 @@ class Decoder(torch.nn.Module):
     def __init__(self, eprojs, odim, dlayers, dunits, sos, eos, att, verbose=0, char_list=None, labeldist=None, lsm_weight=0.,
                  fusion=None, rnnlm=None, model_unit='char', space_loss_weight=0.1):
         super(Decoder, self).__init__()
-        if dlayers != 1:
-            raise Re2eError('dlayers > 1 is outside the round-1 hot path')
+        if dlayers < 1:
+            raise Re2eError('dlayers = %r: the decoder needs at least one layer' % (dlayers,))
         self.labeldist, self.lsm_weight, self.vlabeldist = labeldist, lsm_weight, None
         self.dunits, self.dlayers = dunits, dlayers
         self.embed = EmbeddingParams(odim, dunits)
-        self.decoder = torch.nn.ModuleList([LSTMCellParams(dunits + eprojs, dunits)])
+        self.decoder = torch.nn.ModuleList([LSTMCellParams(dunits + eprojs, dunits)] + [LSTMCellParams(dunits, dunits) for _ in range(1, dlayers)])
         self.output = LinearParams(dunits, odim)
         self.att = att
         self.sos, self.eos = sos, eos

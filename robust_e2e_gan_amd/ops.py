@@ -1777,6 +1777,142 @@ _DECLOOP_BWS_READ = {}     # workspace address -> event behind the last re2e_dec
 DECODER_PERSIST = os.environ.get('RE2E_DEC_PERSIST', '1') != '0'     # the teacher-forced loop as one persistent launch (csrc/decloop.hip)
 
 
+# ---- upper layers of a multi-layer decoder (dlayers > 1; csrc/decstack.hip) -----------------------------------------------------------
+# Layer l >= 1 is an LSTMCell (D -> D) on the state of the layer below at the same token and on its own previous state; the attention reads
+# layer 0 only (e2e_decoder.py:121-152).  ``upper``: a sequence of dicts of Parameters w_ih (4D,D), w_hh (4D,D), b_ih, b_hh (4D), one per
+# layer from layer 1 up.  Per layer the helpers keep (gates (L1,B,4D) activated, z (L1+1,B,D), c (L1+1,B,D)) with block 0 the zero state.
+_UPPER_KEYS = ('w_ih', 'w_hh', 'b_ih', 'b_hh')
+
+
+def _upper_layers(upper, D):
+    lays = list(upper) if upper else []
+    for l, lay in enumerate(lays):
+        if any(k not in lay for k in _UPPER_KEYS):
+            raise lib.Re2eError('decoder layer %d: needs w_ih, w_hh, b_ih, b_hh' % (l + 1))
+        if tuple(lay['w_ih'].shape) != (4 * D, D) or tuple(lay['w_hh'].shape) != (4 * D, D) or tuple(lay['b_ih'].shape) != (4 * D,) \
+                or tuple(lay['b_hh'].shape) != (4 * D,):
+            raise lib.Re2eError('decoder layer %d: w_ih %s, w_hh %s, b_ih %s, b_hh %s do not fit dunits = %d'
+                                % (l + 1, tuple(lay['w_ih'].shape), tuple(lay['w_hh'].shape), tuple(lay['b_ih'].shape), tuple(lay['b_hh'].shape), D))
+        if not all(lay[k].is_contiguous() for k in _UPPER_KEYS):
+            raise lib.Re2eError('decoder layer %d: parameters must be contiguous' % (l + 1))
+    return lays
+
+
+def _upper_alloc(lays, L1, B, D, like):
+    return [(empty((L1, B, 4 * D), like), zeros((L1 + 1, B, D), like), zeros((L1 + 1, B, D), like)) for _ in lays]
+
+
+def _upper_fused(D):
+    """The widths csrc/decstack.hip takes (rows read as float4, a row tile of d(gates) in LDS).  Other widths run the same steps over the general
+    entry points (re2e_gemm + re2e_lstm_cell_fwd / _bwd per token), as the decoder loop's own cell does at such widths."""
+    return D % 4 == 0 and D <= 1024
+
+
+def dec_upper_step(lay, x, z_prev, c_prev, z_out, c_out, n, D, gates=None):
+    """One token of one upper layer for n rows: x (n,D) the state of the layer below, (z_prev, c_prev) the layer's own -> z_out, c_out (and the
+    activated gates (n,4D) if a buffer is given)."""
+    if _upper_fused(D):
+        call('re2e_dec_upper_step', x.data_ptr(), lay['w_ih'].data_ptr(), lay['w_hh'].data_ptr(), lay['b_ih'].data_ptr(), lay['b_hh'].data_ptr(),
+             z_prev.data_ptr(), c_prev.data_ptr(), ptr(gates), z_out.data_ptr(), c_out.data_ptr(), n, D)
+        return
+    g = gates if gates is not None else empty((n, 4 * D), x)
+    gemm(x, lay['w_ih'], g, n, 4 * D, D, transb=True, bias=lay['b_ih'], bias2=lay['b_hh'])
+    gemm(z_prev, lay['w_hh'], g, n, 4 * D, D, transb=True, beta=1.0)
+    call('re2e_lstm_cell_fwd', g.data_ptr(), c_prev.data_ptr(), c_out.data_ptr(), z_out.data_ptr(), n, D)
+
+
+def _upper_token_step(lays, bufs, below, i, n, D):
+    """Token i of every upper layer for the n rows, one launch per layer: ``below`` (L1,n,D) holds layer 0's state of this token at [i]."""
+    x = below[i]
+    for lay, (g, zl, cl) in zip(lays, bufs):
+        dec_upper_step(lay, x, zl[i], cl[i], zl[i + 1], cl[i + 1], n, D, g[i])
+        x = zl[i + 1]
+
+
+def _upper_seq_forward(lays, bufs, below, L1, B, D):
+    """All tokens of every upper layer, teacher forced: per layer ONE input projection over the L1 * B rows, then one launch per token."""
+    for lay, (g, zl, cl) in zip(lays, bufs):
+        gemm(below, lay['w_ih'], g, L1 * B, 4 * D, D, transb=True, bias=lay['b_ih'], bias2=lay['b_hh'])
+        if _upper_fused(D):
+            call('re2e_dec_upper_seq_fwd', g.data_ptr(), lay['w_hh'].data_ptr(), zl.data_ptr(), cl.data_ptr(), L1, B, D)
+        else:
+            for i in range(L1):
+                gemm(zl[i], lay['w_hh'], g[i], B, 4 * D, D, transb=True, beta=1.0)
+                call('re2e_lstm_cell_fwd', g[i].data_ptr(), cl[i].data_ptr(), cl[i + 1].data_ptr(), zl[i + 1].data_ptr(), B, D)
+        below = zl[1:]
+
+
+def _upper_backward(lays, bufs, below0, dZ, L1, B, D):
+    """dZ (L1,B,D): gradient of the top layer's states -> gradient of ``below0`` (layer 0's states); the layers' parameter gradients go into
+    their ``.grad`` on the weight-gradient stream.  Top layer first; per layer one launch per token (cell backward + dgates W_hh), then the
+    products over the whole sequence."""
+    M = L1 * B
+    dev = dZ.device
+    for l in range(len(lays) - 1, -1, -1):
+        lay, (g, zl, cl) = lays[l], bufs[l]
+        below = bufs[l - 1][1][1:] if l > 0 else below0
+        if _upper_fused(D):
+            w_hhT = empty((D, 4 * D), dZ)
+            call('re2e_transpose01', lay['w_hh'].data_ptr(), w_hhT.data_ptr(), 4 * D, D, 1)
+            dG = empty((L1, B, 4 * D), dZ)
+            wsb = query('re2e_dec_upper_bwd_workspace_bytes', B, D)
+            ws = workspace(wsb, dev, 'decstack')
+            call('re2e_dec_upper_seq_bwd', g.data_ptr(), cl.data_ptr(), dZ.data_ptr(), w_hhT.data_ptr(), dG.data_ptr(), L1, B, D, ws.data_ptr(), wsb)
+        else:
+            dG = g                                   # the saved gates become d(gates) in place: one backward per forward
+            dz_carry = zeros((B, D), dZ)
+            dc_a, dc_b = zeros((B, D), dZ), empty((B, D), dZ)
+            for i in range(L1 - 1, -1, -1):
+                call('re2e_lstm_cell_bwd', g[i].data_ptr(), cl[i].data_ptr(), cl[i + 1].data_ptr(), dz_carry.data_ptr(), dZ[i].data_ptr(),
+                     dc_a.data_ptr(), dc_b.data_ptr(), B, D)
+                dc_a, dc_b = dc_b, dc_a
+                gemm(g[i], lay['w_hh'], dz_carry, B, D, 4 * D)
+        dG2 = dG.view(M, 4 * D)
+        d_below = empty((L1, B, D), dZ)
+        gemm(dG2, lay['w_ih'], d_below, M, D, 4 * D)                                      # d z_below = dgates W_ih
+        if lay['w_ih'].requires_grad:
+            with param_grads(dG, below, zl):
+                with accumulate(lay['w_ih']) as (gw, beta):
+                    gemm(dG2, below, gw, 4 * D, D, M, transa=True, beta=beta)
+                with accumulate(lay['w_hh']) as (gw, beta):
+                    gemm(dG2, zl, gw, 4 * D, D, M, transa=True, beta=beta)             # z[0:L1]: the states the recurrent product read
+                for k in ('b_ih', 'b_hh'):
+                    with accumulate(lay[k]) as (gb, beta):
+                        colsum_into(dG2, M, 4 * D, gb, beta)
+        dZ = d_below
+    return dZ
+
+
+class DecoderUpperFn(torch.autograd.Function):
+    """z0 (L1,B,D), the states of decoder layer 0 over a teacher-forced loop -> the top layer's states (L1,B,D) of the layers ``upper`` stacked on
+    it (see ``_upper_layers``).  The backward returns d z0; the layers' parameter gradients are accumulated into their ``.grad``."""
+
+    @staticmethod
+    def forward(ctx, z0, upper):
+        _need_gpu(z0)
+        z0 = _f32(z0)
+        L1, B, D = z0.shape
+        lays = _upper_layers(upper, D)
+        if not lays:
+            raise lib.Re2eError('DecoderUpperFn: no upper layers (dlayers == 1 has nothing above the decoder loop)')
+        bufs = _upper_alloc(lays, L1, B, D, z0)
+        _upper_seq_forward(lays, bufs, z0, L1, B, D)
+        ctx.lays, ctx.dims = lays, (L1, B, D)
+        ctx.save_for_backward(z0, *[t for b in bufs for t in b])
+        return bufs[-1][1][1:]
+
+    @staticmethod
+    def backward(ctx, dZ):
+        saved = ctx.saved_tensors
+        z0, flat = saved[0], saved[1:]
+        bufs = [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))]
+        L1, B, D = ctx.dims
+        return _upper_backward(ctx.lays, bufs, z0, _f32(dZ), L1, B, D), None
+
+
+decoder_upper = DecoderUpperFn.apply
+
+
 class DecoderLoopFn(torch.autograd.Function):
     """hmask (B,T,E) masked encoder states, pre (B,T,A) = mlp_enc(hmask) -> decoder states (L1,B,D) step-major.
 
@@ -1799,15 +1935,21 @@ class DecoderLoopFn(torch.autograd.Function):
     ``kind``: the attention type of the step -- ``location`` (the default; the only one with a persistent form), ``dot``, ``add``,
     ``coverage`` or ``coverage_location`` (csrc/attstep.hip; ``_att_loop_forward`` / ``_att_loop_backward`` below).  Their ``P`` holds the
     type's own attention parameters: add: mlp_dec, gvec_w, gvec_b; coverage: these and wvec_w (A,1), wvec_b (A); dot: mlp_dec, mlp_dec_b
-    (and ``pre`` = tanh(mlp_enc(hmask))); coverage_location: location's."""
+    (and ``pre`` = tanh(mlp_enc(hmask))); coverage_location: location's.
+
+    ``upper`` (optional, see ``_upper_layers``): the decoder layers above layer 0.  The first output is then the TOP layer's states, and a sampled
+    token is the arg-max of the output layer on the top layer's previous state: at runs with sampled steps the upper layers' token step
+    (re2e_dec_upper_step) follows each step of this loop; without sampled steps they run over the finished loop's states as ``DecoderUpperFn``
+    does.  The backward is two-phase either way: the upper layers in reverse, then this loop's reverse with the resulting d z0.  Without
+    ``upper`` nothing here is different from the single-layer loop."""
 
     @staticmethod
-    def forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps=None, w_grad=False, kind='location'):
+    def forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps=None, w_grad=False, kind='location', upper=None):
         _need_gpu(hmask)
         hmask, pre = _f32(hmask), _f32(pre)
         ctx.kind = kind
         if kind != 'location':
-            return _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, w_grad, kind)
+            return _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, w_grad, kind, upper)
         dev = hmask.device
         B, T, E = hmask.shape
         A = pre.shape[2]
@@ -1838,6 +1980,9 @@ class DecoderLoopFn(torch.autograd.Function):
             ids_tm = ids_tm.clone()                 # becomes the list of tokens actually fed
             V = Pm['out_w'].shape[0]
             logits = empty((B, V), hmask)
+        lays = _upper_layers(upper, D)
+        ubufs = _upper_alloc(lays, L1, B, D, hmask)
+        z_top = ubufs[-1][1] if lays else z         # the states the output layer reads
         # the whole loop as ONE persistent launch (csrc/decloop.hip) when no step's token depends on the previous step's output
         # and the shape is inside the resident form's limits (0 bytes = not); the launch-per-step sequence below otherwise
         lwsb = 0 if (sampled or not fused or not DECODER_PERSIST) else query('re2e_dec_loop_workspace_bytes', L1, B, T, E, D, A, C, Fh)
@@ -1849,7 +1994,7 @@ class DecoderLoopFn(torch.autograd.Function):
                  lws.data_ptr(), lwsb)
         for i in range(0 if not lwsb else L1, L1):
             if sampled and i > 0 and sample_steps[i]:
-                gemm(z[i], Pm['out_w'], logits, B, V, D, transb=True, bias=Pm['out_b'])          # y_{i-1} = output(z_{i-1})
+                gemm(z_top[i], Pm['out_w'], logits, B, V, D, transb=True, bias=Pm['out_b'])      # y_{i-1} = output(z_{i-1})
                 ids_i = ids_tm.data_ptr() + 4 * i * B
                 call('re2e_argmax_rows', logits.data_ptr(), B, V, V, ids_i)
                 call('re2e_embedding_fwd', Pm['embed'].data_ptr(), ids_i, B, Dd, emb[i].data_ptr(), Dd)
@@ -1866,26 +2011,34 @@ class DecoderLoopFn(torch.autograd.Function):
                 gemm(cx[i], w_ctx, gates[i], B, 4 * D, E, transb=True, ldb=ldw, beta=1.0, dev=dev)
                 gemm(z[i], Pm['w_hh'], gates[i], B, 4 * D, D, transb=True, beta=1.0)
                 call('re2e_lstm_cell_fwd', gates[i].data_ptr(), c[i].data_ptr(), c[i + 1].data_ptr(), z[i + 1].data_ptr(), B, D)
+            if lays and sampled:
+                _upper_token_step(lays, ubufs, z[1:], i, B, D)
+        if lays and not sampled:
+            _upper_seq_forward(lays, ubufs, z[1:], L1, B, D)
         ctx.Pm, ctx.ids, ctx.hlens = Pm, ids_tm, hlens_dev
         ctx.persist = bool(lwsb)
         ctx.dims = (B, T, E, A, Dd, D, C, Fh, L1)
-        ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, conv, dpj)
+        ctx.lays = lays
+        ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, conv, dpj, *[t for b in ubufs for t in b])
         ctx.w_grad = bool(w_grad)
         if w_grad:
             ctx.set_materialize_grads(False)        # the gradient of an output nothing downstream used arrives as None, not as zeros
         else:
             ctx.mark_non_differentiable(w)
-        return z[1:], w
+        return z_top[1:], w
 
     @staticmethod
     def backward(ctx, dZ, dW):
         if ctx.kind != 'location':
             return _att_loop_backward(ctx, dZ, dW)
-        hmask, pre, emb, cx, z, c, w, gates, conv, dpj = ctx.saved_tensors
+        hmask, pre, emb, cx, z, c, w, gates, conv, dpj = ctx.saved_tensors[:10]
         Pm = ctx.Pm
         B, T, E, A, Dd, D, C, Fh, L1 = ctx.dims
         dev = hmask.device
         dZ = _f32(dZ) if dZ is not None else zeros((L1, B, D), hmask)
+        if ctx.lays:
+            flat = ctx.saved_tensors[10:]
+            dZ = _upper_backward(ctx.lays, [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))], z[1:], dZ, L1, B, D)
         dW = _f32(dW) if (getattr(ctx, 'w_grad', False) and dW is not None) else None      # upstream gradient on the attention weights
         w_ih = Pm['w_ih']
         ldw = Dd + E
@@ -1990,10 +2143,10 @@ class DecoderLoopFn(torch.autograd.Function):
                     with accumulate(Pm[k]) as (gt, beta):
                         call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
                     off += n
-        return d_enc, d_pre, None, None, None, None, None, None, None
+        return d_enc, d_pre, None, None, None, None, None, None, None, None
 
 
-def _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, w_grad, kind):
+def _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, w_grad, kind, upper=None):
     """DecoderLoopFn.forward for the attention types other than ``location``: the launch-per-step sequence with the type's own step
     (re2e_attstep_fwd; coverage_location: re2e_attloc_fwd reading cov as att_prev, then cov + w).  cov (L1,B,T) holds cov_{i+1} at
     index i: step i reads cov[i-1], step 0 the uniform cov_0 the kernels make themselves."""
@@ -2032,10 +2185,13 @@ def _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, 
         ids_tm = ids_tm.clone()                 # becomes the list of tokens actually fed
         V = Pm['out_w'].shape[0]
         logits = empty((B, V), hmask)
+    lays = _upper_layers(upper, D)
+    ubufs = _upper_alloc(lays, L1, B, D, hmask)
+    z_top = ubufs[-1][1] if lays else z             # the states the output layer reads
     opt = lambda k: Pm[k].data_ptr() if k in Pm else None
     for i in range(L1):
         if sampled and i > 0 and sample_steps[i]:
-            gemm(z[i], Pm['out_w'], logits, B, V, D, transb=True, bias=Pm['out_b'])
+            gemm(z_top[i], Pm['out_w'], logits, B, V, D, transb=True, bias=Pm['out_b'])
             ids_i = ids_tm.data_ptr() + 4 * i * B
             call('re2e_argmax_rows', logits.data_ptr(), B, V, V, ids_i)
             call('re2e_embedding_fwd', Pm['embed'].data_ptr(), ids_i, B, Dd, emb[i].data_ptr(), Dd)
@@ -2057,16 +2213,22 @@ def _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, 
             gemm(cx[i], w_ctx, gates[i], B, 4 * D, E, transb=True, ldb=ldw, beta=1.0, dev=dev)
             gemm(z[i], Pm['w_hh'], gates[i], B, 4 * D, D, transb=True, beta=1.0)
             call('re2e_lstm_cell_fwd', gates[i].data_ptr(), c[i].data_ptr(), c[i + 1].data_ptr(), z[i + 1].data_ptr(), B, D)
+        if lays and sampled:
+            _upper_token_step(lays, ubufs, z[1:], i, B, D)
+    if lays and not sampled:
+        _upper_seq_forward(lays, ubufs, z[1:], L1, B, D)
     ctx.Pm, ctx.ids, ctx.hlens = Pm, ids_tm, hlens_dev
     ctx.persist = False
     ctx.dims = (B, T, E, A, Dd, D, C, Fh, L1)
-    ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, dpj, *([cov] if has_cov else []), *([conv] if covloc else []))
+    ctx.lays = lays
+    ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, dpj, *([cov] if has_cov else []), *([conv] if covloc else []),
+                          *[t for b in ubufs for t in b])
     ctx.w_grad = bool(w_grad)
     if w_grad:
         ctx.set_materialize_grads(False)
     else:
         ctx.mark_non_differentiable(w)
-    return z[1:], w
+    return z_top[1:], w
 
 
 def _att_loop_backward(ctx, dZ, dW):
@@ -2083,6 +2245,9 @@ def _att_loop_backward(ctx, dZ, dW):
     B, T, E, A, Dd, D, C, Fh, L1 = ctx.dims
     dev = hmask.device
     dZ = _f32(dZ) if dZ is not None else zeros((L1, B, D), hmask)
+    if ctx.lays:
+        flat = saved[len(saved) - 3 * len(ctx.lays):]
+        dZ = _upper_backward(ctx.lays, [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))], z[1:], dZ, L1, B, D)
     dW = _f32(dW) if (ctx.w_grad and dW is not None) else None
     w_ih = Pm['w_ih']
     ldw = Dd + E
@@ -2182,7 +2347,7 @@ def _att_loop_backward(ctx, dZ, dW):
                     with accumulate(Pm[k]) as (gt, beta):
                         call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
                     off += n
-    return d_enc, d_pre, None, None, None, None, None, None, None
+    return d_enc, d_pre, None, None, None, None, None, None, None, None
 
 
 decoder_loop = DecoderLoopFn.apply
