@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 331
+#define RE2E_ABI_VERSION 332
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -641,6 +641,19 @@ int re2e_lm_log_softmax_combine(const float* logits, int n, int V, const float* 
 /* local[k][j] += lm_weight * lm[k][cand_dev[k][j]], k < n, j < ncand (e2e_decoder.py:284-285 on re2e_ctc_prefix_score's outputs);
  * a candidate outside [0, V) gives NaN. */
 int re2e_lm_add_cands(float* local, const float* lm, const int* cand_dev, int n, int ncand, int V, float lm_weight, re2e_stream_t stream);
+/* The form re2e_lm_lstm_cell (kind RE2E_LM_PLAN_CELL), re2e_lm_lstm_cell_zo (RE2E_LM_PLAN_CELL_ZO) or re2e_lm_output (RE2E_LM_PLAN_OUTPUT)
+ * runs a call with, as one line of space-separated key=value pairs in `out`; nothing is launched and no pointer is dereferenced (the form
+ * follows from the row count and from the widest load every row of every operand is aligned for, so the query takes the call's own
+ * pointers and leading dimensions).  Cell kinds: x, ldx, I, w_ih, w_hh, h_prev, n, H as in the call (V is ignored) ->
+ *   family=lm_cell zo=0|1 rows=4|8|16 vi=.. vh=.. grid=Hx1x1 block=128 trips=..     (vi, vh) in (4,4), (4,2), (2,2), (1,1): floats per load of
+ * the W_ih x and W_hh h products; rows: activation rows per trip of a workgroup, trips = ceil(n / rows).  RE2E_LM_PLAN_OUTPUT: h_prev = the
+ * call's h, w_hh = its w, with n, H, V (x, ldx, I, w_ih are ignored) ->
+ *   family=lm_out rows=4|8|16 vec=4|2|1 grid=ceil(V/4)x1x1 block=128 trips=.. */
+#define RE2E_LM_PLAN_CELL 0
+#define RE2E_LM_PLAN_CELL_ZO 1
+#define RE2E_LM_PLAN_OUTPUT 2
+int re2e_lm_plan(int kind, const float* x, long ldx, int I, const float* w_ih, const float* w_hh, const float* h_prev, int n, int H, int V,
+                 char* out, size_t out_bytes);
 
 /* ---- Word-level LMs in the beam search (model/extlm.py; extlm.py:75-216 upstream; csrc/wordlm.hip) ----
  * The lexical tree is flat int32 arrays on the device: N nodes, node 0 the root; wid[N] the word id of a word end or -1; lo[N], hi[N] the

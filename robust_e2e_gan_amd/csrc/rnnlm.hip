@@ -195,6 +195,14 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lm_out_kernel(const float* __re
   }
 }
 
+// a + fl(w * x), the product and the sum rounded separately as the reference's two tensor operations are.  Contraction is switched off
+// for the statement: __fadd_rn(a, __fmul_rn(w, x)) are a plain * and + to this compiler, which fuses them into one FMA by default.
+__device__ __forceinline__ float add_scaled(float a, float w, float x) {
+#pragma clang fp contract(off)
+  const float p = w * x;
+  return a + p;
+}
+
 // lsm[r][:] = log_softmax(logits[r][:]); comb[r][:] = att[r][:] + lm_weight * lsm[r][:] when asked (product and sum rounded
 // separately, as the reference's two tensor operations are).  One workgroup per row; the first 8192 logits of a row stay in registers
 // between the three passes.
@@ -228,13 +236,13 @@ __global__ __launch_bounds__(LSM_THREADS) void lm_lsm_kernel(const float* __rest
     if (v < V) {
       const float lp = xv[i] - l;
       lsm[base + v] = lp;
-      if (comb) comb[base + v] = __fadd_rn(att[base + v], __fmul_rn(lm_weight, lp));
+      if (comb) comb[base + v] = add_scaled(att[base + v], lm_weight, lp);
     }
   }
   for (int v = threadIdx.x + LSM_KEEP * LSM_THREADS; v < V; v += LSM_THREADS) {
     const float lp = x[v] - l;
     lsm[base + v] = lp;
-    if (comb) comb[base + v] = __fadd_rn(att[base + v], __fmul_rn(lm_weight, lp));
+    if (comb) comb[base + v] = add_scaled(att[base + v], lm_weight, lp);
   }
 }
 
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(256) void lm_add_cands_kernel(float* __restrict__ l
   if (i >= total) return;
   const int c = cand[i];
   if (c < 0 || c >= V) { local[i] = __builtin_nanf(""); return; }
-  local[i] = __fadd_rn(local[i], __fmul_rn(lm_weight, lm[(long)(i / ncand) * V + c]));
+  local[i] = add_scaled(local[i], lm_weight, lm[(long)(i / ncand) * V + c]);
 }
 
 inline bool aligned(const void* p, int bytes) { return p == nullptr || ((uintptr_t)p % bytes) == 0; }
@@ -255,24 +263,44 @@ inline int vec_width(const void* p, long ld) {
   return 1;
 }
 
+// The form a call runs in, chosen on the host from the row count and from what every row of every operand is aligned for: the one
+// place lm_cell_entry, re2e_lm_output and re2e_lm_plan take it from.
+inline int rows_per_trip(int n) { return n <= 4 ? 4 : n <= 8 ? 8 : 16; }      // R: activation rows a workgroup carries per trip of its row0 loop
+struct CellForm { int R, vi, vh, grid; };                                       // lm_cell_kernel<R, vi, vh, .>, one workgroup per hidden unit
+struct OutForm { int R, vec, grid; };                                           // lm_out_kernel<R, vec>, one workgroup per four vocabulary rows
+// (vi, vh) is one of the four instantiated pairs (4,4), (4,2), (2,2), (1,1): the widest that both operands of each product allow
+inline CellForm cell_form(const float* x, long ldx, int I, const float* w_ih, const float* w_hh, const float* h_prev, int n, int H) {
+  const int vi = x ? min(vec_width(w_ih, I), vec_width(x, ldx)) : 1;
+  const int vh = min(vec_width(w_hh, H), vec_width(h_prev, H));
+  CellForm f = {rows_per_trip(n), 1, 1, H};
+  if (vi == 4 && vh == 4) { f.vi = 4; f.vh = 4; }
+  else if (vi == 4 && vh == 2) { f.vi = 4; f.vh = 2; }
+  else if (vi >= 2 && vh >= 2) { f.vi = 2; f.vh = 2; }
+  return f;
+}
+inline OutForm out_form(const float* h, const float* w, int n, int V, int H) {
+  return OutForm{rows_per_trip(n), min(vec_width(w, H), vec_width(h, H)), cdiv(V, 4)};
+}
+
 template <int R, bool ZO>
-void launch_cell(int vi, int vh, dim3 grid, hipStream_t st, const float* x, long ldx, const int* ids, int n_embed, int I, const float* w_ih,
+void launch_cell(const CellForm& f, hipStream_t st, const float* x, long ldx, const int* ids, int n_embed, int I, const float* w_ih,
                  const float* w_hh, const float* b_ih, const float* b_hh, const float* h_prev, const float* c_prev, int n, int H, float keep_h,
                  float keep_c, float* h_out, float* c_out) {
 #define RE2E_LM_CELL(VI, VH)                                                                                                             \
-  hipLaunchKernelGGL((lm_cell_kernel<R, VI, VH, ZO>), grid, dim3(64 * LM_WAVES), 0, st, x, ldx, ids, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, \
-                     n, H, keep_h, keep_c, h_out, c_out)
-  if (vi == 4 && vh == 4) RE2E_LM_CELL(4, 4);
-  else if (vi == 4 && vh == 2) RE2E_LM_CELL(4, 2);
-  else if (vi >= 2 && vh >= 2) RE2E_LM_CELL(2, 2);
+  hipLaunchKernelGGL((lm_cell_kernel<R, VI, VH, ZO>), dim3(f.grid), dim3(64 * LM_WAVES), 0, st, x, ldx, ids, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, \
+                     c_prev, n, H, keep_h, keep_c, h_out, c_out)
+  if (f.vi == 4 && f.vh == 4) RE2E_LM_CELL(4, 4);
+  else if (f.vi == 4 && f.vh == 2) RE2E_LM_CELL(4, 2);
+  else if (f.vi == 2 && f.vh == 2) RE2E_LM_CELL(2, 2);
   else RE2E_LM_CELL(1, 1);
 #undef RE2E_LM_CELL
 }
 
 template <int R>
-void launch_out(int vec, dim3 grid, hipStream_t st, const float* h, const float* w, const float* b, int n, int V, int H, float* logits) {
-  if (vec == 4) hipLaunchKernelGGL((lm_out_kernel<R, 4>), grid, dim3(64 * LM_WAVES), 0, st, h, w, b, n, V, H, logits);
-  else if (vec == 2) hipLaunchKernelGGL((lm_out_kernel<R, 2>), grid, dim3(64 * LM_WAVES), 0, st, h, w, b, n, V, H, logits);
+void launch_out(const OutForm& f, hipStream_t st, const float* h, const float* w, const float* b, int n, int V, int H, float* logits) {
+  const dim3 grid(f.grid);
+  if (f.vec == 4) hipLaunchKernelGGL((lm_out_kernel<R, 4>), grid, dim3(64 * LM_WAVES), 0, st, h, w, b, n, V, H, logits);
+  else if (f.vec == 2) hipLaunchKernelGGL((lm_out_kernel<R, 2>), grid, dim3(64 * LM_WAVES), 0, st, h, w, b, n, V, H, logits);
   else hipLaunchKernelGGL((lm_out_kernel<R, 1>), grid, dim3(64 * LM_WAVES), 0, st, h, w, b, n, V, H, logits);
 }
 
@@ -287,12 +315,10 @@ int lm_cell_entry(const float* x, long ldx, const int* ids_dev, int n_embed, int
   RE2E_CHECK_ARG(!ids_dev || n_embed > 0, "embedding gather needs the table's row count");
   RE2E_CHECK_ARG((long)(ids_dev ? n_embed : n) * ldx < (1L << 31) && (long)n * H < (1L << 31), "operand beyond 32-bit element offsets");
   RE2E_CHECK_ARG(h_out != h_prev && c_out != h_prev, "h_prev is read by every workgroup: the outputs must not alias it");
-  const int vi = x ? min(vec_width(w_ih, I), vec_width(x, ldx)) : 1;
-  const int vh = min(vec_width(w_hh, H), vec_width(h_prev, H));
-  const dim3 grid(H);
-#define RE2E_LM_ARGS vi, vh, grid, stream, x, ldx, ids_dev, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, n, H, keep_h, keep_c, h_out, c_out
-  if (n <= 4) launch_cell<4, ZO>(RE2E_LM_ARGS);
-  else if (n <= 8) launch_cell<8, ZO>(RE2E_LM_ARGS);
+  const CellForm f = cell_form(x, ldx, I, w_ih, w_hh, h_prev, n, H);
+#define RE2E_LM_ARGS f, stream, x, ldx, ids_dev, n_embed, I, w_ih, w_hh, b_ih, b_hh, h_prev, c_prev, n, H, keep_h, keep_c, h_out, c_out
+  if (f.R == 4) launch_cell<4, ZO>(RE2E_LM_ARGS);
+  else if (f.R == 8) launch_cell<8, ZO>(RE2E_LM_ARGS);
   else launch_cell<16, ZO>(RE2E_LM_ARGS);
 #undef RE2E_LM_ARGS
   RE2E_LAUNCH_CHECK();
@@ -316,12 +342,34 @@ extern "C" int re2e_lm_lstm_cell_zo(const float* x, long ldx, const int* ids_dev
 extern "C" int re2e_lm_output(const float* h, const float* w, const float* b, int n, int V, int H, float* logits, hipStream_t stream) {
   RE2E_CHECK_ARG(h && w && b && logits, "null operand");
   RE2E_CHECK_ARG(n > 0 && n <= 64 && V > 0 && H > 0, "bad shape (1 <= n <= 64)");
-  const int vec = min(vec_width(w, H), vec_width(h, H));
-  const dim3 grid(cdiv(V, 4));
-  if (n <= 4) launch_out<4>(vec, grid, stream, h, w, b, n, V, H, logits);
-  else if (n <= 8) launch_out<8>(vec, grid, stream, h, w, b, n, V, H, logits);
-  else launch_out<16>(vec, grid, stream, h, w, b, n, V, H, logits);
+  const OutForm f = out_form(h, w, n, V, H);
+  if (f.R == 4) launch_out<4>(f, stream, h, w, b, n, V, H, logits);
+  else if (f.R == 8) launch_out<8>(f, stream, h, w, b, n, V, H, logits);
+  else launch_out<16>(f, stream, h, w, b, n, V, H, logits);
   RE2E_LAUNCH_CHECK();
+  return RE2E_OK;
+}
+
+extern "C" int re2e_lm_plan(int kind, const float* x, long ldx, int I, const float* w_ih, const float* w_hh, const float* h_prev, int n, int H, int V,
+                            char* out, size_t out_bytes) {
+  RE2E_CHECK_ARG(out && out_bytes > 0, "no output buffer");
+  RE2E_CHECK_ARG(kind == RE2E_LM_PLAN_CELL || kind == RE2E_LM_PLAN_CELL_ZO || kind == RE2E_LM_PLAN_OUTPUT, "unknown kind");
+  RE2E_CHECK_ARG(n > 0 && n <= 64 && H > 0, "bad shape (1 <= n <= 64)");
+  int len;
+  if (kind == RE2E_LM_PLAN_OUTPUT) {
+    RE2E_CHECK_ARG(h_prev && w_hh && V > 0, "the output layer needs h, w and V > 0");
+    const OutForm f = out_form(h_prev, w_hh, n, V, H);
+    len = snprintf(out, out_bytes, "family=lm_out rows=%d vec=%d grid=%dx1x1 block=%d trips=%d", f.R, f.vec, f.grid, 64 * LM_WAVES, cdiv(n, f.R));
+  } else {
+    const bool zo = kind == RE2E_LM_PLAN_CELL_ZO;
+    RE2E_CHECK_ARG((x || zo) && (w_ih || !x) && w_hh, "null operand");
+    if (!x) { I = 1; ldx = 1; }
+    RE2E_CHECK_ARG(I > 0 && ldx >= I, "bad shape (ldx >= I > 0)");
+    const CellForm f = cell_form(x, ldx, I, w_ih, w_hh, h_prev, n, H);
+    len = snprintf(out, out_bytes, "family=lm_cell zo=%d rows=%d vi=%d vh=%d grid=%dx1x1 block=%d trips=%d", zo ? 1 : 0, f.R, f.vi, f.vh, f.grid,
+                   64 * LM_WAVES, cdiv(n, f.R));
+  }
+  RE2E_CHECK_ARG(len > 0 && (size_t)len < out_bytes, "output buffer too small");
   return RE2E_OK;
 }
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 331     # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 332     # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -158,6 +158,7 @@ SIGNATURES = {
     're2e_fsrnn_bwd': (I, [P, P, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P, I, I, I, I, P, Z, P]),
     're2e_fsrnn_plan': (I, [I, I, I, I, I, I, P, Z]),
     're2e_lm_add_cands': (I, [P, P, P, I, I, I, F, P]),
+    're2e_lm_plan': (I, [I, P, L, I, P, P, P, I, I, I, P, Z]),
     're2e_wlm_transition': (I, [P, P, I, I, I, I, P, P, P, P, I, I, P, P, P, P]),
     're2e_wlm_softmax_cumsum': (I, [P, I, I, P, I, P, P]),
     're2e_wlm_lookahead': (I, [P, I, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, P, P]),
@@ -307,6 +308,21 @@ def fsrnn_plan(T, B, H, L, backward=False, cus=0):
     rc = lib.re2e_fsrnn_plan(T, B, H, L, int(backward), cus, buf, len(buf))
     if rc != 0:
         raise Re2eError('re2e_fsrnn_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    return dict(kv.split('=') for kv in buf.value.decode().split())
+
+
+LM_PLAN_CELL, LM_PLAN_CELL_ZO, LM_PLAN_OUTPUT = 0, 1, 2          # include/re2e.h RE2E_LM_PLAN_*
+
+
+def lm_plan(kind, x=None, ldx=0, I=0, w_ih=None, w_hh=None, h_prev=None, n=1, H=1, V=0):
+    """re2e_lm_plan as a dict of strings: the few-row kernel, its rows per trip, load widths and grid re2e_lm_lstm_cell / _zo / re2e_lm_output
+    would run a call with.  The pointers are ADDRESSES (ints or None), those of the call itself: only their alignment is looked at, nothing is
+    launched or read.  LM_PLAN_OUTPUT: ``h_prev`` is the call's h and ``w_hh`` its w."""
+    buf = ctypes.create_string_buffer(160)
+    lib = load()
+    rc = lib.re2e_lm_plan(kind, x, ldx, I, w_ih, w_hh, h_prev, n, H, V, buf, len(buf))
+    if rc != 0:
+        raise Re2eError('re2e_lm_plan failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
     return dict(kv.split('=') for kv in buf.value.decode().split())
 
 

@@ -315,6 +315,34 @@ def test_conv_plan_table():
     assert points == 3 * 3 * 5 * 10 * 3 * 4 * 2
 
 
+def test_lm_plan_table():
+    """re2e_lm_plan (the host functions re2e_lm_lstm_cell / _zo and re2e_lm_output choose their kernel form with) reads the addresses it is
+    given and nothing behind them: on made-up addresses, without a device, the rows per trip, load widths and grid by row count, widths and
+    alignment; what the calls refuse is refused."""
+    from robust_e2e_gan_amd import lib
+    if not os.path.exists(lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    base = 1 << 20
+    p = lib.lm_plan(lib.LM_PLAN_CELL, x=base, ldx=256, I=256, w_ih=base, w_hh=base, h_prev=base, n=12, H=650)
+    assert p == dict(family='lm_cell', zo='0', rows='16', vi='4', vh='2', grid='650x1x1', block='128', trips='1'), p
+    p = lib.lm_plan(lib.LM_PLAN_CELL, x=base + 4, ldx=8, I=8, w_ih=base, w_hh=base, h_prev=None, n=64, H=8)
+    assert (p['rows'], p['vi'], p['vh'], p['trips']) == ('16', '1', '1', '4'), p
+    p = lib.lm_plan(lib.LM_PLAN_CELL_ZO, w_hh=base, h_prev=base, n=5, H=8)          # no input: the pair falls to (1, 1)
+    assert (p['zo'], p['rows'], p['vi'], p['vh']) == ('1', '8', '1', '1'), p
+    p = lib.lm_plan(lib.LM_PLAN_OUTPUT, w_hh=base, h_prev=base + 8, n=4, H=12, V=4233)
+    assert p == dict(family='lm_out', rows='4', vec='2', grid='1059x1x1', block='128', trips='1'), p
+    for bad in (dict(n=0), dict(n=65), dict(ldx=7)):
+        args = dict(x=base, ldx=8, I=8, w_ih=base, w_hh=base, h_prev=base, n=4, H=8)
+        args.update(bad)
+        with pytest.raises(lib.Re2eError):
+            lib.lm_plan(lib.LM_PLAN_CELL, **args)
+    with pytest.raises(lib.Re2eError):
+        lib.lm_plan(lib.LM_PLAN_CELL, x=None, w_hh=base, n=4, H=8)                    # only the zoneout entry takes a cell without input
+    with pytest.raises(lib.Re2eError):
+        lib.lm_plan(3, w_hh=base, h_prev=base, n=4, H=8, V=5)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from robust_e2e_gan_amd import lib
     monkeypatch.setattr(lib, '_lib', None)
