@@ -258,6 +258,26 @@ def _wants(ctx, i, p):
     return ctx.needs_input_grad[i] and (p is None or id(p) not in FROZEN_PARAMS)
 
 
+def _param_flags(Pm):
+    """{key: requires_grad} of a dict of parameters, read when the graph is built: the graph-time half of ``_wants`` for parameters that reach a
+    Function inside a dict and so have no entry in ``ctx.needs_input_grad`` (the decoder loop, its upper layers)."""
+    return {k: bool(p.requires_grad) for k, p in Pm.items() if isinstance(p, torch.Tensor)}
+
+
+def _dict_wants(flags, Pm):
+    """{key: the parameter gets a gradient from the backward now running}: it required one at forward time and is not frozen now."""
+    return {k: f and id(Pm[k]) not in FROZEN_PARAMS for k, f in flags.items()}
+
+
+def _spend(ctx, op):
+    """First line of a backward that overwrites its saved state (gates -> d(gates), in place): a second walk of a retained graph would return
+    plausible wrong numbers -- the saved tensors' version counters do not move under the raw pointers -- so it raises instead."""
+    if getattr(ctx, 'spent', False):
+        raise lib.Re2eError('%s: second backward through the same forward (retain_graph=True): its backward overwrites the saved gates with '
+                            'd(gates), one backward per forward -- run the forward again' % op)
+    ctx.spent = True
+
+
 class param_grads(object):
     """``with param_grads(t1, t2, ...):`` runs the enclosed weight/bias-gradient kernels on WGRAD_STREAM.
 
@@ -605,7 +625,7 @@ class MaskFcFn(torch.autograd.Function):
                 dp = empty((M, K), p2)
                 gemm(dlin, wt, dp, M, K, Np, transb=True)
                 dp = dp.view(ctx.oshape[:-1] + (K,))
-            if ctx.needs_input_grad[1]:
+            if _wants(ctx, 1, W):
                 with param_grads(dlin, p2):
                     tmp = empty((Np, K), p2)
                     gemm(dlin, p2, tmp, Np, K, M, transa=True)
@@ -622,7 +642,7 @@ class MaskFcFn(torch.autograd.Function):
             dp = empty((M, K), p2)
             gemm_input_grad(dlin, W, dp, M, K, N)
             dp = dp.view(ctx.oshape[:-1] + (K,))
-        if ctx.needs_input_grad[1]:
+        if _wants(ctx, 1, W):
             with param_grads(dlin, p2), accumulate(W) as (gw, beta):
                 gemm(dlin, p2, gw, N, K, M, transa=True, beta=beta)
         return dp, None, None, None, None
@@ -1263,10 +1283,21 @@ class BnLreluFn(torch.autograd.Function):
             call('re2e_bn_sync_bwd_apply', dy.data_ptr(), x.data_ptr(), Pn, C, gamma.data_ptr(), beta.data_ptr(), sm.data_ptr(), si.data_ptr(),
                  ctx.slope, tot.data_ptr(), dx.data_ptr())
             return dx, None, None, None, None, None, None, None, None
-        if _wants(ctx, 1, gamma):
+        want_g, want_b = _wants(ctx, 1, gamma), _wants(ctx, 2, beta)
+        if want_g and want_b and (gamma.grad is None) == (beta.grad is None):
             with accumulate(gamma) as (dg, gbeta), accumulate(beta) as (db, _):
                 call('re2e_bn_lrelu_bwd', dy.data_ptr(), x.data_ptr(), Pn, C, gamma.data_ptr(), beta.data_ptr(), sm.data_ptr(), si.data_ptr(),
                      ctx.slope, dx.data_ptr(), dg.data_ptr(), db.data_ptr(), gbeta, ws.data_ptr(), wsb)
+        elif want_g or want_b:
+            # one of the two alone (the other frozen or not trainable), or one fresh gradient beside one buffer: the kernel has ONE beta for
+            # both sums, so they go to a scratch pair and each wanted one is added under its own beta
+            sums = empty((2, C), x)
+            call('re2e_bn_lrelu_bwd', dy.data_ptr(), x.data_ptr(), Pn, C, gamma.data_ptr(), beta.data_ptr(), sm.data_ptr(), si.data_ptr(),
+                 ctx.slope, dx.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(), 0.0, ws.data_ptr(), wsb)
+            for p, s_, want in ((gamma, sums[0], want_g), (beta, sums[1], want_b)):
+                if want:
+                    with accumulate(p) as (gp, pbeta):
+                        call('re2e_axpby', 1.0, s_.data_ptr(), pbeta, gp.data_ptr(), C)
         else:
             call('re2e_bn_lrelu_bwd', dy.data_ptr(), x.data_ptr(), Pn, C, gamma.data_ptr(), beta.data_ptr(), sm.data_ptr(), si.data_ptr(),
                  ctx.slope, dx.data_ptr(), None, None, 0.0, ws.data_ptr(), wsb)
@@ -1383,13 +1414,15 @@ class BiLstmFn(torch.autograd.Function):
         w = ctx.w
         T, B, I, H = ctx.dims
         dy = _f32(dy)
-        # the saved gates are overwritten with d(pre-activation gates); a second backward is not supported
+        _spend(ctx, 'BiLstmFn')      # the saved gates are overwritten with d(pre-activation gates): one backward per forward
+        # graph-time choice AND not frozen now, per parameter (see LinearFn.backward)
+        needs = tuple(_wants(ctx, 2 + j, p) for j, p in enumerate(w))
         dc = empty((B, 2 * H), dy)
         wsb = query('re2e_lstm_workspace_bytes', B, H)
         ws = workspace(wsb, dy.device, 'lstm')
         # dbias (2, 4H): the column sums of d(gates) = the gradient of b_ih and of b_hh per direction, accumulated beside the recurrence
         # (csrc/lstm.hip lstm_bwd3: no pass of its own over the (T B, 4H) tensors, 105 MB per direction and layer at config 4)
-        dbias = empty((2, 4 * H), dy) if any(ctx.needs_input_grad[4 + 4 * d] or ctx.needs_input_grad[5 + 4 * d] for d in range(2)) else None
+        dbias = empty((2, 4 * H), dy) if any(needs[2 + 4 * d] or needs[3 + 4 * d] for d in range(2)) else None
         if dbias is not None and not FUSED_DBIAS:      # (experiments: the column sums as a pass of their own on the weight-gradient stream, rounds 1-5)
             dbias = None
         call('re2e_lstm_seq_bwd', g_f.data_ptr(), g_r.data_ptr(), w[1].data_ptr(), w[5].data_ptr(), dy.data_ptr(), ybuf.data_ptr(),
@@ -1415,13 +1448,12 @@ class BiLstmFn(torch.autograd.Function):
         # well was measured and changes nothing (71.63 against 71.55; again in round 6, with the filler streams the last to finish: 46.21 against 46.13).
         yflat = ybuf.view((T + 2) * B, 2 * H)
         last = INLINE_LAST_WGRAD and not ctx.needs_input_grad[0]
-        needs = ctx.needs_input_grad
 
         def weight_grads(inline):
             with param_grads(g_f, g_r, x2, ybuf, dbias, ctx.maps, inline=inline):
                 for d in range(2):
                     w_ih, w_hh, b_ih, b_hh = w[4 * d:4 * d + 4]
-                    n_ih, n_hh, n_bi, n_bh = needs[2 + 4 * d:6 + 4 * d]
+                    n_ih, n_hh, n_bi, n_bh = needs[4 * d:4 * d + 4]
                     mp = ctx.maps
                     if n_ih and x2.shape[1] != I:              # padded input copy (see forward): full-width product, then the real columns
                         tmp = empty((4 * H, x2.shape[1]), dy)
@@ -1842,10 +1874,15 @@ def _upper_seq_forward(lays, bufs, below, L1, B, D):
         below = zl[1:]
 
 
-def _upper_backward(lays, bufs, below0, dZ, L1, B, D):
+def _upper_flags(lays):
+    """Per layer {key: requires_grad}, read at forward time (``_param_flags``)."""
+    return [_param_flags({k: lay[k] for k in _UPPER_KEYS}) for lay in lays]
+
+
+def _upper_backward(lays, bufs, below0, dZ, L1, B, D, flags):
     """dZ (L1,B,D): gradient of the top layer's states -> gradient of ``below0`` (layer 0's states); the layers' parameter gradients go into
-    their ``.grad`` on the weight-gradient stream.  Top layer first; per layer one launch per token (cell backward + dgates W_hh), then the
-    products over the whole sequence."""
+    their ``.grad`` on the weight-gradient stream -- of the parameters ``flags`` (``_upper_flags``) names and nobody has frozen.  Top layer
+    first; per layer one launch per token (cell backward + dgates W_hh), then the products over the whole sequence."""
     M = L1 * B
     dev = dZ.device
     for l in range(len(lays) - 1, -1, -1):
@@ -1870,15 +1907,19 @@ def _upper_backward(lays, bufs, below0, dZ, L1, B, D):
         dG2 = dG.view(M, 4 * D)
         d_below = empty((L1, B, D), dZ)
         gemm(dG2, lay['w_ih'], d_below, M, D, 4 * D)                                      # d z_below = dgates W_ih
-        if lay['w_ih'].requires_grad:
+        want = _dict_wants(flags[l], lay)            # per parameter: required a gradient at forward time, not frozen now
+        if any(want.values()):
             with param_grads(dG, below, zl):
-                with accumulate(lay['w_ih']) as (gw, beta):
-                    gemm(dG2, below, gw, 4 * D, D, M, transa=True, beta=beta)
-                with accumulate(lay['w_hh']) as (gw, beta):
-                    gemm(dG2, zl, gw, 4 * D, D, M, transa=True, beta=beta)             # z[0:L1]: the states the recurrent product read
+                if want['w_ih']:
+                    with accumulate(lay['w_ih']) as (gw, beta):
+                        gemm(dG2, below, gw, 4 * D, D, M, transa=True, beta=beta)
+                if want['w_hh']:
+                    with accumulate(lay['w_hh']) as (gw, beta):
+                        gemm(dG2, zl, gw, 4 * D, D, M, transa=True, beta=beta)         # z[0:L1]: the states the recurrent product read
                 for k in ('b_ih', 'b_hh'):
-                    with accumulate(lay[k]) as (gb, beta):
-                        colsum_into(dG2, M, 4 * D, gb, beta)
+                    if want[k]:
+                        with accumulate(lay[k]) as (gb, beta):
+                            colsum_into(dG2, M, 4 * D, gb, beta)
         dZ = d_below
     return dZ
 
@@ -1898,6 +1939,7 @@ class DecoderUpperFn(torch.autograd.Function):
         bufs = _upper_alloc(lays, L1, B, D, z0)
         _upper_seq_forward(lays, bufs, z0, L1, B, D)
         ctx.lays, ctx.dims = lays, (L1, B, D)
+        ctx.uflags = _upper_flags(lays)
         ctx.save_for_backward(z0, *[t for b in bufs for t in b])
         return bufs[-1][1][1:]
 
@@ -1907,10 +1949,54 @@ class DecoderUpperFn(torch.autograd.Function):
         z0, flat = saved[0], saved[1:]
         bufs = [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))]
         L1, B, D = ctx.dims
-        return _upper_backward(ctx.lays, bufs, z0, _f32(dZ), L1, B, D), None
+        if not _upper_fused(D):
+            _spend(ctx, 'DecoderUpperFn')           # the general path turns the saved gates into d(gates) in place
+        return _upper_backward(ctx.lays, bufs, z0, _f32(dZ), L1, B, D, ctx.uflags), None
 
 
 decoder_upper = DecoderUpperFn.apply
+
+
+def _dec_weight_grads(ctx, want, G2, zp2, emb, cx, ddp, partials, npart, plist):
+    """The decoder loop's parameter gradients, from d(gates) G2 (M,4D), the states read zp2 (M,D), the embedded tokens, the contexts, d(decoder
+    projection) ddp and the per-utterance partial sums of the attention parameters ``plist`` = ((key, floats), ...): one gradient per
+    parameter ``want`` names (``_dict_wants``); what only an unwanted parameter would read is not computed."""
+    Pm = ctx.Pm
+    B, T, E, A, Dd, D, C, Fh, L1 = ctx.dims
+    M, ldw = L1 * B, Dd + E
+    w_ih = Pm['w_ih']
+    if want['w_ih']:
+        with accumulate(w_ih) as (gw, beta):
+            gemm(G2, emb.view(M, Dd), gw, 4 * D, Dd, M, transa=True, ldc=ldw, beta=beta)                       # dW_ih[:, :Dd]
+            gemm(G2, cx.view(M, E), gw.data_ptr() + 4 * Dd, 4 * D, E, M, transa=True, ldc=ldw, beta=beta)      # dW_ih[:, Dd:]
+    if want['w_hh']:
+        with accumulate(Pm['w_hh']) as (gw, beta):
+            gemm(G2, zp2, gw, 4 * D, D, M, transa=True, beta=beta)
+    for k in ('b_ih', 'b_hh'):
+        if want[k]:
+            with accumulate(Pm[k]) as (gb, beta):
+                colsum_into(G2, M, 4 * D, gb, beta)
+    if want['mlp_dec']:
+        with accumulate(Pm['mlp_dec']) as (gw, beta):
+            gemm(ddp.view(M, A), zp2, gw, A, D, M, transa=True, beta=beta)
+    if ctx.kind == 'dot' and want['mlp_dec_b']:
+        with accumulate(Pm['mlp_dec_b']) as (gb, beta):
+            colsum_into(ddp.view(M, A), M, A, gb, beta)
+    if want['embed']:
+        d_emb = empty((M, Dd), G2)
+        gemm(G2, w_ih, d_emb, M, Dd, 4 * D, ldb=ldw)                                                        # dgates W_ih[:, :Dd]
+        V = Pm['embed'].shape[0]
+        with accumulate(Pm['embed']) as (gw, beta):
+            call('re2e_embedding_bwd', d_emb.data_ptr(), Dd, ctx.ids.data_ptr(), M, Dd, V, gw.data_ptr(), beta)
+    if plist and any(want[k] for k, _ in plist):
+        tot = empty((npart,), G2)
+        colsum_into(partials, B, npart, tot, 0.0)
+        off = 0
+        for k, n in plist:
+            if want[k]:
+                with accumulate(Pm[k]) as (gt, beta):
+                    call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
+            off += n
 
 
 class DecoderLoopFn(torch.autograd.Function):
@@ -2019,6 +2105,7 @@ class DecoderLoopFn(torch.autograd.Function):
         ctx.persist = bool(lwsb)
         ctx.dims = (B, T, E, A, Dd, D, C, Fh, L1)
         ctx.lays = lays
+        ctx.pflags, ctx.uflags = _param_flags(Pm), _upper_flags(lays)
         ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, conv, dpj, *[t for b in ubufs for t in b])
         ctx.w_grad = bool(w_grad)
         if w_grad:
@@ -2029,6 +2116,7 @@ class DecoderLoopFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dZ, dW):
+        _spend(ctx, 'DecoderLoopFn')            # the reverse loop turns the saved gates into d(gates) in place
         if ctx.kind != 'location':
             return _att_loop_backward(ctx, dZ, dW)
         hmask, pre, emb, cx, z, c, w, gates, conv, dpj = ctx.saved_tensors[:10]
@@ -2038,7 +2126,7 @@ class DecoderLoopFn(torch.autograd.Function):
         dZ = _f32(dZ) if dZ is not None else zeros((L1, B, D), hmask)
         if ctx.lays:
             flat = ctx.saved_tensors[10:]
-            dZ = _upper_backward(ctx.lays, [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))], z[1:], dZ, L1, B, D)
+            dZ = _upper_backward(ctx.lays, [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))], z[1:], dZ, L1, B, D, ctx.uflags)
         dW = _f32(dW) if (getattr(ctx, 'w_grad', False) and dW is not None) else None      # upstream gradient on the attention weights
         w_ih = Pm['w_ih']
         ldw = Dd + E
@@ -2110,9 +2198,10 @@ class DecoderLoopFn(torch.autograd.Function):
         M = L1 * B
         G2, zp2 = gates.view(M, 4 * D), z[:L1].reshape(M, D)
         # nothing downstream waits for the decoder's weight gradients (~0.4 ms of small GEMMs and reductions): weight-gradient stream
-        if w_ih.requires_grad:
+        want = _dict_wants(ctx.pflags, Pm)          # per parameter: required a gradient at forward time, not frozen now
+        if any(want.values()):
             with param_grads(gates, z, emb, cx, ddp, partials, *((bws, de_all, conv, dpj, pre, w) if bwsb else ())):
-                if bwsb:
+                if bwsb and any(want[k] for k in ('gvec_w', 'gvec_b', 'mlp_att', 'loc_conv')):
                     # the persistent loop has written d_pre itself: the weight-gradient sums of the energy backward (d gvec, d W_att, recomputed
                     # from the saved rows) and d W_conv (from the d conv rows it left in its workspace) leave the critical stream
                     dpre_into(empty((B, T, A), hmask))
@@ -2121,28 +2210,8 @@ class DecoderLoopFn(torch.autograd.Function):
                     ev_read = torch.cuda.Event()
                     ev_read.record()                         # (on the stream the call above ran on)
                     _DECLOOP_BWS_READ[bws.data_ptr()] = ev_read
-                with accumulate(w_ih) as (gw, beta):
-                    gemm(G2, emb.view(M, Dd), gw, 4 * D, Dd, M, transa=True, ldc=ldw, beta=beta)                       # dW_ih[:, :Dd]
-                    gemm(G2, cx.view(M, E), gw.data_ptr() + 4 * Dd, 4 * D, E, M, transa=True, ldc=ldw, beta=beta)      # dW_ih[:, Dd:]
-                with accumulate(Pm['w_hh']) as (gw, beta):
-                    gemm(G2, zp2, gw, 4 * D, D, M, transa=True, beta=beta)
-                for k in ('b_ih', 'b_hh'):
-                    with accumulate(Pm[k]) as (gb, beta):
-                        colsum_into(G2, M, 4 * D, gb, beta)
-                with accumulate(Pm['mlp_dec']) as (gw, beta):
-                    gemm(ddp.view(M, A), zp2, gw, A, D, M, transa=True, beta=beta)
-                d_emb = empty((M, Dd), hmask)
-                gemm(G2, w_ih, d_emb, M, Dd, 4 * D, ldb=ldw)                                                        # dgates W_ih[:, :Dd]
-                V = Pm['embed'].shape[0]
-                with accumulate(Pm['embed']) as (gw, beta):
-                    call('re2e_embedding_bwd', d_emb.data_ptr(), Dd, ctx.ids.data_ptr(), M, Dd, V, gw.data_ptr(), beta)
-                tot = empty((npart,), hmask)
-                colsum_into(partials, B, npart, tot, 0.0)
-                off = 0
-                for k, n in (('gvec_w', A), ('gvec_b', 1), ('mlp_att', A * C), ('loc_conv', C * (2 * Fh + 1))):
-                    with accumulate(Pm[k]) as (gt, beta):
-                        call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
-                    off += n
+                _dec_weight_grads(ctx, want, G2, zp2, emb, cx, ddp, partials, npart,
+                                  (('gvec_w', A), ('gvec_b', 1), ('mlp_att', A * C), ('loc_conv', C * (2 * Fh + 1))))
         return d_enc, d_pre, None, None, None, None, None, None, None, None
 
 
@@ -2221,6 +2290,7 @@ def _att_loop_forward(ctx, hmask, pre, ids_tm, hlens_dev, L1, Pm, sample_steps, 
     ctx.persist = False
     ctx.dims = (B, T, E, A, Dd, D, C, Fh, L1)
     ctx.lays = lays
+    ctx.pflags, ctx.uflags = _param_flags(Pm), _upper_flags(lays)
     ctx.save_for_backward(hmask, pre, emb, cx, z, c, w, gates, dpj, *([cov] if has_cov else []), *([conv] if covloc else []),
                           *[t for b in ubufs for t in b])
     ctx.w_grad = bool(w_grad)
@@ -2247,7 +2317,7 @@ def _att_loop_backward(ctx, dZ, dW):
     dZ = _f32(dZ) if dZ is not None else zeros((L1, B, D), hmask)
     if ctx.lays:
         flat = saved[len(saved) - 3 * len(ctx.lays):]
-        dZ = _upper_backward(ctx.lays, [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))], z[1:], dZ, L1, B, D)
+        dZ = _upper_backward(ctx.lays, [tuple(flat[3 * l:3 * l + 3]) for l in range(len(ctx.lays))], z[1:], dZ, L1, B, D, ctx.uflags)
     dW = _f32(dW) if (ctx.w_grad and dW is not None) else None
     w_ih = Pm['w_ih']
     ldw = Dd + E
@@ -2319,34 +2389,10 @@ def _att_loop_backward(ctx, dZ, dW):
         plist = {'dot': (), 'add': (('gvec_w', A), ('gvec_b', 1)), 'coverage': (('gvec_w', A), ('gvec_b', 1), ('wvec_w', A), ('wvec_b', A))}[kind]
     M = L1 * B
     G2, zp2 = gates.view(M, 4 * D), z[:L1].reshape(M, D)
-    if w_ih.requires_grad:
+    want = _dict_wants(ctx.pflags, Pm)
+    if any(want.values()):
         with param_grads(gates, z, emb, cx, ddp, partials):
-            with accumulate(w_ih) as (gw, beta):
-                gemm(G2, emb.view(M, Dd), gw, 4 * D, Dd, M, transa=True, ldc=ldw, beta=beta)
-                gemm(G2, cx.view(M, E), gw.data_ptr() + 4 * Dd, 4 * D, E, M, transa=True, ldc=ldw, beta=beta)
-            with accumulate(Pm['w_hh']) as (gw, beta):
-                gemm(G2, zp2, gw, 4 * D, D, M, transa=True, beta=beta)
-            for k in ('b_ih', 'b_hh'):
-                with accumulate(Pm[k]) as (gb, beta):
-                    colsum_into(G2, M, 4 * D, gb, beta)
-            with accumulate(Pm['mlp_dec']) as (gw, beta):
-                gemm(ddp.view(M, A), zp2, gw, A, D, M, transa=True, beta=beta)
-            if kind == 'dot':
-                with accumulate(Pm['mlp_dec_b']) as (gb, beta):
-                    colsum_into(ddp.view(M, A), M, A, gb, beta)
-            d_emb = empty((M, Dd), hmask)
-            gemm(G2, w_ih, d_emb, M, Dd, 4 * D, ldb=ldw)
-            V = Pm['embed'].shape[0]
-            with accumulate(Pm['embed']) as (gw, beta):
-                call('re2e_embedding_bwd', d_emb.data_ptr(), Dd, ctx.ids.data_ptr(), M, Dd, V, gw.data_ptr(), beta)
-            if plist:
-                tot = empty((npart,), hmask)
-                colsum_into(partials, B, npart, tot, 0.0)
-                off = 0
-                for k, n in plist:
-                    with accumulate(Pm[k]) as (gt, beta):
-                        call('re2e_axpby', 1.0, tot.data_ptr() + 4 * off, beta, gt.data_ptr(), n)
-                    off += n
+            _dec_weight_grads(ctx, want, G2, zp2, emb, cx, ddp, partials, npart, plist)
     return d_enc, d_pre, None, None, None, None, None, None, None, None
 
 
@@ -2410,6 +2456,7 @@ class LmSeqFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_all, d_hT, d_cT):
         gates, hbuf, cbuf = ctx.saved_tensors
+        _spend(ctx, 'LmSeqFn')
         w_hh = ctx.w_hh
         T, B, H4 = gates.shape
         H = H4 // 4
@@ -2518,6 +2565,7 @@ class FsrnnSeqFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_all, d_fh, d_fc, d_sh, d_sc):
         gates, hbuf, cbuf, hd, mh, mc, dm = ctx.saved_tensors
+        _spend(ctx, 'FsrnnSeqFn')
         W = ctx.W
         keep_h, keep_c, L, composed = ctx.cfg
         T, B, H4 = gates.shape[1:]
