@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 332
+#define RE2E_ABI_VERSION 333
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -279,6 +279,29 @@ int re2e_pack_pad(const float* src_flat, const int* offsets_dev, const int* lens
  * (cmvn (2,F), optional); when dst_log is given dst is clamped at 1e-7 too, as the reference's in-place clamp does. */
 int re2e_kaldi_decode_pad(const unsigned char* blob, const long* rec_off_dev, const int* kind_dev, const int* lens_dev, int B,
                           int Tmax, int F, float* dst, float* dst_log, const float* cmvn, re2e_stream_t stream);
+
+/* ---- K0 waveform front end (csrc/stft.hip; data/prepare_feats.py: MakeMixture + librosa.stft(n_fft=512, hop 256, scipy.signal.hamming)).
+ * pcm: ONE device blob of 16-bit mono samples, used as they are (no scaling).  speech_off / speech_len / noise_off / noise_len / noise_start
+ * (and snr_db): HOST arrays of B entries, in samples; they are checked here and travel as kernel arguments, so nothing has to stay alive
+ * after the call.  Utterance b is s = pcm[speech_off[b] .. + L), 257 <= L = speech_len[b] < 2^31; its noise file n = pcm[noise_off[b] .. + N),
+ * 1 <= N < 2^31, 0 <= noise_start[b] = s0 < N.  The mixture is m[i] = s[i] + g n[(s0 + i) mod N] (the reference tiles the file and slices).
+ *
+ * re2e_wav_mix_scale: scale_out[b] = g = sqrt(sum s^2 / (P 10^(snr_db[b]/10))), P = sum_{i<L} n[(s0 + i) mod N]^2; the sums are taken in
+ * double in a fixed order (two runs agree bit for bit), the sums the reference meant (its own square int16 arrays and overflow).  P == 0:
+ * g = 0 and *zero_count (device int, optional) is incremented -- the reference draws another noise file instead.  No host synchronisation.
+ *
+ * re2e_wav_stft: frames T_b = 1 + L / 256, reflect padding (librosa center=True), symmetric Hamming window 0.54 - 0.46 cos(2 pi n / 511),
+ * X_t[k] = sum_n w[n] y[256 t - 256 + n] exp(-2 pi i k n / 512), k = 0 .. 256, of the clean signal (C) and of the mixture (M; scale[b] = g,
+ * device).  Every output is optional, (B,Tmax,257) fp32, rows t >= T_b zero:
+ *   clean = max(|C|, 1e-7), clean_log = (10 log10(clean) + cmvn[0]) * cmvn[1] (cmvn (2,257) optional), mix / mix_log likewise of M,
+ *   cos = cos(angle C - angle M) = Re(C conj M) / (|C| |M|), clean_ang / mix_ang = atan2f(Im, Re); a zero magnitude has angle 0.
+ * noise_off == NULL: the clean stream only (recognition); the four mixture outputs must be NULL.  Refused with a message, before anything
+ * is launched: L < 257, Tmax < T_b, noise without scale, an index outside its range. */
+int re2e_wav_mix_scale(const short* pcm, const long* speech_off, const long* speech_len, const long* noise_off, const long* noise_len,
+                       const long* noise_start, const float* snr_db, int B, float* scale_out, int* zero_count, re2e_stream_t stream);
+int re2e_wav_stft(const short* pcm, const long* speech_off, const long* speech_len, const long* noise_off, const long* noise_len,
+                  const long* noise_start, const float* scale, int B, int Tmax, float* clean, float* clean_log, float* mix,
+                  float* mix_log, float* cos_out, float* clean_ang, float* mix_ang, const float* cmvn, re2e_stream_t stream);
 
 /* ---- K2 fused fbank (model/feat_model.py:118-135): y = log(max((x^2) W, 1e-7)); optional
  * second output y_norm = (y + cmvn[0]) * cmvn[1]; optional third output pw_out = (x^2) W itself, which re2e_fbank_bwd takes

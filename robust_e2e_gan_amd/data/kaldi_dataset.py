@@ -1,6 +1,6 @@
 """Kaldi-table dataset of the joint / enhancement trainers (mirror of MixSequentialDataset,
-data/mix_data_loader.py:14-262, for ``feat_type`` 'kaldi_magspec' / 'kaldi_powspec' -- the wav front-ends need
-librosa / python_speech_features and are out of scope).
+data/mix_data_loader.py:14-262, for ``feat_type`` 'kaldi_magspec' / 'kaldi_powspec' -- waveform input is
+``wav_dataset.MixWavDataset``, which mixes and transforms on the device).
 
 Directory layout as upstream (:31-35, :127-133): ``clean_feats.scp``, ``clean_angles.scp``, ``mix_feats.scp``,
 ``mix_angles.scp``, ``utt2spk``, ``text_char`` | ``text_word`` and a dictionary file with one symbol per line;

@@ -4,7 +4,13 @@
 IntTensor sizes, flat LongTensor targets).  ``collate_device`` is the MI355X-first variant (K1):
 the ragged utterances are concatenated once on the host, shipped with ONE H2D copy per stream and
 zero-padded on the device by re2e_pack_pad -- 3 live tensors instead of 5 (cos_angles and
-clean_log_inputs are never read by joint_train.py)."""
+clean_log_inputs are never read by joint_train.py).
+
+``collate_wav_device`` / ``wav_features_device`` start from 16-bit PCM instead: the samples go over PCIe as ONE pinned int16 blob and
+re2e_wav_mix_scale / re2e_wav_stft (csrc/stft.hip) mix the noise in at the drawn SNR and produce the padded spectra on the device."""
+import ctypes
+import logging
+
 import numpy as np
 import torch
 
@@ -124,6 +130,114 @@ def ops_mask_rows(x, lens):
     from ..model.e2e_common import lens_dev
     with torch.no_grad():
         return ops.mask_rows(x, lens_dev(lens, x.device))
+
+
+WAV_OUTPUTS = ('clean', 'clean_log', 'mix', 'mix_log', 'cos', 'clean_ang', 'mix_ang')       # re2e_wav_stft's outputs, in its argument order
+WAV_BINS, WAV_HOP = 257, 256
+_zero_noise = {}          # device -> [counter (device int32), pinned copy, event behind the copy, count already logged]
+
+
+def wav_frames_of(n_samples):
+    """Frames of an utterance of ``n_samples`` samples: 1 + L // 256 (librosa center=True, hop 256)."""
+    return 1 + int(n_samples) // WAV_HOP
+
+
+def _zero_noise_counter(device):
+    """The device counter re2e_wav_mix_scale increments for a noise segment of zero power (the mixture is then the clean signal).  It is read
+    one batch LATE -- the copy enqueued behind the previous batch, if it has landed -- so that no collate waits for the device."""
+    key = str(device)
+    st = _zero_noise.get(key)
+    if st is None:
+        st = _zero_noise[key] = [torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32).pin_memory(), None, 0]
+    counter, host, ev, seen = st
+    if ev is not None and ev.query():
+        n = int(host[0])
+        if n > seen:
+            logging.getLogger(__name__).warning('%d noise segment(s) of zero power so far: those mixtures are the clean signal', n)
+            st[3] = n
+        st[2] = None
+    return st
+
+
+def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'mix', 'mix_log'), Tmax=None, pool=None):
+    """16-bit PCM -> spectra on ``device``, all work enqueued on the CURRENT stream.  ``speech``: int16 arrays, one per utterance, in the
+    order of the batch rows; ``noise``: None (clean stream only) or one ``(noise int16 array, s0, dB)`` per utterance -- the mixture is
+    ``s[i] + g * n[(s0 + i) % len(n)]`` with ``g = sqrt(sum s^2 / (P * 10^(dB/10)))``, P the power of that noise segment.  Arrays that are the
+    same object are uploaded once.  Returns ``{name: (B, Tmax, 257) fp32}`` for the names in ``want`` (WAV_OUTPUTS), plus 'scale' (B,) with
+    noise.  A noise segment of zero power gives g = 0 and is counted on the device (the reference draws another file instead)."""
+    bad = [w for w in want if w not in WAV_OUTPUTS]
+    if bad:
+        raise ValueError('unknown front-end output %r (one of %s)' % (bad[0], ', '.join(WAV_OUTPUTS)))
+    B = len(speech)
+    lens = [int(s.shape[0]) for s in speech]
+    T = max(wav_frames_of(n) for n in lens)
+    Tmax = T if Tmax is None else int(Tmax)
+    arrays, where, pos = [], {}, 0
+
+    def place(a):
+        nonlocal pos
+        if a.dtype != np.int16 or a.ndim != 1:
+            raise ValueError('the front end takes 1-D int16 sample arrays, got %s %s' % (a.dtype, a.shape))
+        if id(a) not in where:
+            where[id(a)] = pos
+            arrays.append(a)
+            pos += a.shape[0]
+        return where[id(a)]
+    soff = [place(s) for s in speech]
+    longs = lambda v: (ctypes.c_long * B)(*[int(x) for x in v])
+    on_gpu = torch.device(device).type == 'cuda'
+    if noise is not None:
+        noff = [place(n[0]) for n in noise]
+        nlen = [int(n[0].shape[0]) for n in noise]
+        s0 = [int(n[1]) % max(ln, 1) for n, ln in zip(noise, nlen)]
+        db = (ctypes.c_float * B)(*[float(n[2]) for n in noise])
+    host = pool.get('wav', 2 * pos).view(torch.int16) if pool is not None else torch.empty(pos, dtype=torch.int16)
+    if pool is None and on_gpu:
+        host = host.pin_memory()
+    np.concatenate(arrays, out=host.numpy())
+    blob = host.to(device, non_blocking=True)
+    out = {k: torch.empty(B, Tmax, WAV_BINS, dtype=torch.float32, device=device) for k in want}
+    cm = cmvn.to(device).float().contiguous() if cmvn is not None else None
+    p = lambda k: out[k].data_ptr() if k in out else None
+    if noise is None:
+        call('re2e_wav_stft', blob.data_ptr(), longs(soff), longs(lens), None, None, None, None, B, Tmax, *[p(k) for k in WAV_OUTPUTS],
+             cm.data_ptr() if cm is not None else None)
+    else:
+        st = _zero_noise_counter(device)
+        scale = torch.empty(B, dtype=torch.float32, device=device)
+        idx = (longs(soff), longs(lens), longs(noff), longs(nlen), longs(s0))
+        call('re2e_wav_mix_scale', blob.data_ptr(), *idx, db, B, scale.data_ptr(), st[0].data_ptr())
+        call('re2e_wav_stft', blob.data_ptr(), *idx, scale.data_ptr(), B, Tmax, *[p(k) for k in WAV_OUTPUTS],
+             cm.data_ptr() if cm is not None else None)
+        out['scale'] = scale
+        if st[2] is None and on_gpu:
+            st[1].copy_(st[0], non_blocking=True)
+            st[2] = torch.cuda.Event()
+            st[2].record(torch.cuda.current_stream())
+    if on_gpu:
+        blob.record_stream(torch.cuda.current_stream())
+    return out
+
+
+def collate_wav_device(batch, device, cmvn=None, want=('clean', 'mix', 'mix_log'), pool=None):
+    """Device-side collate for ``MixWavDataset``.  ``batch`` = list of ``(utt_id, spk_id, speech int16, noise int16, s0, dB, target list)``.
+    Returns the reference's 10-tuple (mix_data_loader.py:264-302), sorted by length (descending) and zero padded, with the streams named
+    in ``want`` on ``device`` ('clean_log' and 'cos' for the enhancement trainers) and None for the others.  One pinned int16 upload per
+    batch, the distinct noise files of the batch once; everything is enqueued on the current stream, so it plugs into ``DevicePrefetcher`` as
+    ``lambda b, d, p: collate_wav_device(b, d, cmvn, pool=p)``."""
+    batch = sorted(batch, key=lambda s: s[2].shape[0], reverse=True)
+    o = wav_frontend_device([s[2] for s in batch], device, [(s[3], s[4], s[5]) for s in batch], cmvn, want, pool=pool)
+    lens = [wav_frames_of(s[2].shape[0]) for s in batch]
+    targets = torch.LongTensor([t for s in batch for t in s[6]])
+    return ([s[0] for s in batch], [s[1] for s in batch], o.get('clean'), o.get('clean_log'), o.get('mix'), o.get('mix_log'), o.get('cos'), targets,
+            torch.IntTensor(lens), torch.IntTensor([len(s[6]) for s in batch]))
+
+
+def wav_features_device(pcms, device, cmvn=None):
+    """Recognition from waveforms: ``(inputs, log_inputs, input_sizes)`` as the reference's SequentialDataset hands them to ``enhance_model``,
+    ``feat_model`` and ``recognize`` -- the magnitude spectra (B,T,257), their normalised logs and the frame counts, in the order given."""
+    o = wav_frontend_device(list(pcms), device, None, cmvn, ('clean', 'clean_log'))
+    return o['clean'], o['clean_log'], torch.IntTensor([wav_frames_of(p.shape[0]) for p in pcms])
 
 
 class BucketingSampler(object):

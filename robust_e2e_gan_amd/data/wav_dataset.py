@@ -1,0 +1,135 @@
+"""Waveform dataset of the joint / enhancement trainers: the inputs of the reference's offline data/prepare_feats.py (``clean_wav.scp``,
+``noise.scp``) read directly, with the noise mixed in and the STFT taken on the device by ``mix_data_loader.collate_wav_device``
+(csrc/stft.hip) -- no librosa, no Kaldi binaries, no stored spectra.
+
+Directory layout: ``clean_wav.scp`` (``utt path``), ``noise.scp`` (one path per line; a leading id column is accepted), ``utt2spk``,
+``text_char`` | ``text_word`` and a dictionary file.  Items are ``<utt>__mix<k>``, k < ``noise_repeat_num``, as prepare_feats names its
+mixtures.  Where prepare_feats draws the noise file, the segment start and the SNR ~ U(0, 20) dB ONCE, offline, here they come from a
+generator seeded by (seed, epoch, index): ``set_epoch`` gives fresh mixtures every epoch, and the same triple gives the same mixture.
+The segment start follows the reference's rule (prepare_feats.py:45-50) on the noise file repeated until it covers the speech.  The
+reference draws again when the noise segment has zero power; here such a mixture is the clean signal and is counted on the device
+(re2e_wav_mix_scale), which the loader logs one batch late.
+
+``__getitem__`` returns ``(item id, speaker, speech int16, noise int16, s0, dB, target list)``."""
+import os
+from collections import defaultdict
+
+import numpy as np
+import torch
+
+from ..lib import call
+from . import wav_io
+from .kaldi_dataset import _read_table, read_dictionary, read_targets
+from .mix_data_loader import WAV_BINS, wav_frames_of, wav_frontend_device
+
+
+def segment_start_range(noise_len, speech_len):
+    """Exclusive upper end of the reference's draw of the segment start in the tiled noise: ``randint(0, elen - 1)`` when
+    ``elen = tiled - speech_len - 1 > 1``, else 0."""
+    tiled = noise_len * max(1, -(-speech_len // noise_len))
+    elen = tiled - speech_len - 1
+    return elen if elen > 1 else 1
+
+
+def draw_mixture(seed, epoch, index, noise_lens, speech_len):
+    """``(noise file index, segment start in the tiled noise, dB ~ U(0, 20))`` from a generator seeded by (seed, epoch, index)."""
+    rng = np.random.default_rng([int(seed), int(epoch), int(index)])
+    ni = int(rng.integers(len(noise_lens)))
+    start = int(rng.integers(segment_start_range(noise_lens[ni], speech_len)))
+    return ni, start, float(rng.uniform(0.0, 20.0))
+
+
+class MixWavDataset(torch.utils.data.Dataset):
+    def __init__(self, args, data_dir, dict_file):
+        self.args = args
+        self.clean = _read_table(os.path.join(data_dir, 'clean_wav.scp'))
+        self.clean = [(u, p.strip()) for u, p in self.clean]
+        with open(os.path.join(data_dir, 'noise.scp'), encoding='utf-8') as f:
+            self.noise_paths = [line.split()[-1] for line in f if line.strip()]
+        if not self.clean or not self.noise_paths:
+            raise ValueError('%s: clean_wav.scp and noise.scp must list at least one file each' % data_dir)
+        self.repeat = max(1, int(getattr(args, 'noise_repeat_num', 1)))
+        self.seed = int(getattr(args, 'seed', 0))
+        self.epoch = 0
+        self.samples = [wav_io.wav_frames(p) for _, p in self.clean]              # header only
+        short = [u for (u, _), n in zip(self.clean, self.samples) if n < WAV_BINS]
+        if short:
+            raise wav_io.WavError('%s: shorter than %d samples (the STFT pads by reflection)' % (short[0], WAV_BINS))
+        self.noise_len = [wav_io.wav_frames(p) for p in self.noise_paths]
+        self._noise = {}
+        self.feat_size = WAV_BINS
+        lengths = [wav_frames_of(self.samples[i % len(self.clean)]) for i in range(len(self))]
+        _, edges = np.histogram(lengths, bins='auto')                              # length buckets for BucketingSampler, as MixKaldiDataset
+        self.bins_to_samples = defaultdict(list)
+        for i, b in enumerate(np.digitize(lengths, bins=edges)):
+            self.bins_to_samples[int(b)].append(i)
+        self.utt2spk = dict(_read_table(os.path.join(data_dir, 'utt2spk')))
+        self.char_list = read_dictionary(dict_file)
+        self.num_classes = len(self.char_list)
+        unit = getattr(args, 'model_unit', 'char')
+        self.targets, self.labeldist = read_targets(os.path.join(data_dir, 'text_char' if unit == 'char' else 'text_word'), self.char_list, unit)
+        self.num_utt_cmvn = getattr(args, 'num_utt_cmvn', 20000)
+        self.cmvn = self._load_cmvn() if getattr(args, 'normalize_type', 1) == 1 else None
+
+    def __len__(self):
+        return len(self.clean) * self.repeat
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    # ---- items ----------------------------------------------------------------------------------------------
+    def item_id(self, index):
+        """``(<utt>__mix<k>, utt index)``: repeat k covers the whole list before k + 1 starts, as prepare_feats writes them."""
+        k, u = divmod(index, len(self.clean))
+        return '%s__mix%d' % (self.clean[u][0], k), u
+
+    def draw(self, index, epoch=None):
+        """``(noise file index, segment start in the tiled noise, dB)`` of item ``index`` in ``epoch`` (default: the current one)."""
+        return draw_mixture(self.seed, self.epoch if epoch is None else epoch, index, self.noise_len, self.samples[self.item_id(index)[1]])
+
+    def noise(self, ni):
+        """Noise file ``ni``, read once and kept: items that share it hand the SAME array to the collate, which uploads it once per batch."""
+        a = self._noise.get(ni)
+        if a is None:
+            a = self._noise[ni] = wav_io.read_wav(self.noise_paths[ni])
+        return a
+
+    def __getitem__(self, index):
+        item, u = self.item_id(index)
+        utt, path = self.clean[u]
+        ni, start, db = self.draw(index)
+        return (item, self.utt2spk[utt], wav_io.read_wav(path), self.noise(ni), start % self.noise_len[ni], db, list(self.targets.get(utt)))
+
+    # ---- CMVN -----------------------------------------------------------------------------------------------
+    def compute_cmvn(self, device='cuda', batch=16):
+        """[-mean; 1/sqrt(var)] of 10*log10(max(|M|, 1e-7)) over ``num_utt_cmvn`` random mixtures, (2, 257) as MixKaldiDataset's -- the
+        spectra and their per-bin sums are taken on the device (re2e_wav_stft, re2e_cmvn_stats), accumulated in float64 on the host."""
+        n = min(len(self), self.num_utt_cmvn)
+        order = np.random.permutation(len(self))[:n]
+        s, sq, frames = np.zeros(WAV_BINS), np.zeros(WAV_BINS), 0
+        for i in range(0, n, batch):
+            items = [self[int(j)] for j in order[i:i + batch]]
+            log = wav_frontend_device([it[2] for it in items], device, [(it[3], it[4], it[5]) for it in items], None, ('mix_log',))['mix_log']
+            lens = [wav_frames_of(it[2].shape[0]) for it in items]
+            ld = torch.tensor(lens, dtype=torch.int32, device=device)
+            bs, bq = torch.empty(WAV_BINS, device=device), torch.empty(WAV_BINS, device=device)
+            call('re2e_cmvn_stats', log.data_ptr(), ld.data_ptr(), len(items), log.shape[1], WAV_BINS, bs.data_ptr(), bq.data_ptr())
+            s += bs.double().cpu().numpy()
+            sq += bq.double().cpu().numpy()
+            frames += sum(lens)
+        mean = s / frames
+        var = sq / frames - np.square(mean)
+        return np.stack([-mean, 1 / np.sqrt(var)], 0).astype(np.float32)
+
+    def _load_cmvn(self):
+        exp = getattr(self.args, 'exp_path', None)
+        path = os.path.join(exp, 'cmvn.npy') if exp else None
+        if path and os.path.exists(path):
+            cm = np.load(path)
+            if cm.shape[1] == self.feat_size:
+                return cm
+        cm = self.compute_cmvn()
+        if path:
+            os.makedirs(exp, exist_ok=True)
+            np.save(path, cm)
+        return cm
