@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 333
+#define RE2E_ABI_VERSION 334
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -302,6 +302,26 @@ int re2e_wav_mix_scale(const short* pcm, const long* speech_off, const long* spe
 int re2e_wav_stft(const short* pcm, const long* speech_off, const long* speech_len, const long* noise_off, const long* noise_len,
                   const long* noise_start, const float* scale, int B, int Tmax, float* clean, float* clean_log, float* mix,
                   float* mix_log, float* cos_out, float* clean_ang, float* mix_ang, const float* cmvn, re2e_stream_t stream);
+
+/* The way back (csrc/stft.hip), librosa.istft(hop_length=256, window=scipy.signal.hamming, center=True, length=L): no reference counterpart
+ * on the device (the reference's enhance_out.py stops at the enhanced features).  mag, ang: (B,Tmax,257) fp32; out_off / out_len: HOST
+ * arrays of B entries, in samples, checked here and passed as kernel arguments.  For utterance b, L = out_len[b], T = 1 + L / 256:
+ *   X_t[k] = mag (cos ang + i sin ang), the imaginary parts of bins 0 and 256 ignored; x_t = irfft(X_t, 512) (with the 1/512);
+ *   y[i] = (w[m + 256] x_{t-1}[m + 256] + w[m] x_t[m]) / (w[m + 256]^2 + w[m]^2), t = 1 + i / 256, m = i mod 256, for i < 256 (T - 1);
+ *   y[i] = 0 for 256 (T - 1) <= i < L.  Rows t >= T of mag / ang are never read.
+ * Every kept sample lies under exactly two frames, so the overlap-add is a gather: no atomics, two runs agree bit for bit.
+ * The samples go to wav_f32[out_off[b] .. + L) (fp32) and / or pcm_out[out_off[b] .. + L) (int16: rintf, saturated to -32768 .. 32767;
+ * *clip_count, device int, optional, is incremented by the number of saturated samples); both blobs hold out_samples samples, nothing
+ * outside the B ranges is written.  Refused with a message, before anything is launched: L < 257, Tmax < T, mag or ang NULL, both outputs
+ * NULL, a range outside 0 .. out_samples.
+ *
+ * re2e_wav_sdr_sums: sums[b] = {sum s^2, sum y^2, sum s y} over i < len[b] ((B,3) double, device), s = ref_pcm[ref_off[b] + i] (int16),
+ * y = est[est_off[b] + i] (fp32); taken in double in a fixed order (two runs agree bit for bit).  The host derives
+ * SNR = 10 log10(sum s^2 / sum (s - y)^2) and SI-SDR = 10 log10(|a s|^2 / |a s - y|^2), a = sum s y / sum s^2, from them. */
+int re2e_wav_istft(const float* mag, const float* ang, const long* out_off, const long* out_len, int B, int Tmax, long out_samples,
+                   float* wav_f32, short* pcm_out, int* clip_count, re2e_stream_t stream);
+int re2e_wav_sdr_sums(const short* ref_pcm, const long* ref_off, const float* est, const long* est_off, const long* len, int B,
+                      double* sums, re2e_stream_t stream);
 
 /* ---- K2 fused fbank (model/feat_model.py:118-135): y = log(max((x^2) W, 1e-7)); optional
  * second output y_norm = (y + cmvn[0]) * cmvn[1]; optional third output pw_out = (x^2) W itself, which re2e_fbank_bwd takes

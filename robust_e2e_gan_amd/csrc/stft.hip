@@ -14,6 +14,8 @@
 // recorded at any level, while g n is at most the speech's power (SNR >= 0 dB) -- so the leak stays at rounding level of C, and silent speech
 // under a loud file (g = 0) still gives C = 0 exactly.  The output rows are written 64 consecutive bins per wavefront store.
 //
+// re2e_wav_istft / re2e_wav_sdr_sums: the way back (enhanced magnitudes and a phase to samples) and the sums of SNR / SI-SDR, further down.
+//
 // LDS banking of the exchanges (8-byte elements; ds_read_b64 conflicts per 32-lane half over 64 dword banks):
 //   pass 1 -> 2: element (k0, n1, n0) at 72 k0 + 8 n1 + n0.  Written lane-consecutive (lane = 8 n1 + n0); read by lane (k0, n0) for each n1:
 //                a half wave covers k0 = 0..3, n0 = 0..7 -> 72 k0 + n0 is 0..7, 8..15, 16..23, 24..31 mod 32: conflict free.
@@ -280,6 +282,159 @@ void fill_chunk(WavUtt& u, const long* soff, const long* slen, const long* noff,
   }
 }
 
+// ---- the way back: re2e_wav_istft ---------------------------------------------------------------------------------------------------------
+// With hop = NFFT / 2 every kept sample lies under exactly two frames: hop block h (samples 256 h .. 256 h + 255) is the second half of
+// frame h plus the first half of frame h + 1, over w^2 of the two halves -- a gather, no atomics.  A workgroup owns IBLOCKS = 15 consecutive
+// hop blocks and transforms the IFRAMES = 16 frames under them (the first frame of the next group is transformed again there: 1/15 more
+// work, no wait on another workgroup).  Two real frames share one complex transform, the mirror image of the forward's packing:
+// Z = Xa + i Xb over the Hermitian-extended spectra gives xa + i xb.  The inverse runs on the forward's butterflies and twiddles as
+// conj(FFT(conj Z)) / 512.  The imaginary parts of bins 0 and 256 are dropped BEFORE packing (kept, Im Xa[0] would land in xb).
+// The spectrum of a pair is staged in the wavefront's exchange buffer in natural order (bin k and its mirror 512 - k written by the lane
+// that read bin k: lane-consecutive, conflict free), the windowed frames go to fr[frame][n] (lane-consecutive), and sample m of every block
+// belongs to thread m, which keeps 1 / (512 (w[m]^2 + w[m + 256]^2)) in a register.  Rows t >= T_b are never read.
+constexpr int IFRAMES = 16, IBLOCKS = IFRAMES - 1;
+
+struct IstftUtt {                                // read-only kernel argument, as WavUtt
+  long off[CHUNK], len[CHUNK];
+};
+
+__global__ __launch_bounds__(256) void wav_istft_kernel(const float* __restrict__ mag, const float* __restrict__ ang, const IstftUtt u, int b0,
+                                                        int Tmax, float* __restrict__ wav, short* __restrict__ pcm, int* __restrict__ clip_count) {
+  __shared__ float win[NFFT];
+  __shared__ float2 tw[NFFT];
+  __shared__ float2 xbuf[4][576];
+  __shared__ float fr[IFRAMES][NFFT];
+  const int bi = blockIdx.y, b = b0 + bi, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long L = u.len[bi];
+  const int T = 1 + (int)(L >> 8);
+  const int h0 = blockIdx.x * IBLOCKS;           // first hop block = first frame of this workgroup
+  if (h0 >= T) return;                           // blocks 0 .. T - 2 carry samples, block T - 1 is the zero tail
+  for (int i = tid; i < NFFT; i += 256) { win[i] = g_wav_window[i]; tw[i] = g_wav_twiddle[i]; }
+  __syncthreads();
+  const long row0 = (long)b * Tmax;
+  float2* zb = xbuf[wave];
+  const int n0 = lane & 7, k0 = lane >> 3;
+#pragma unroll 1
+  for (int q = wave; q < IFRAMES / 2; q += 4) {    // every wavefront makes the same two trips: the barriers below are uniform
+    const int ta = h0 + 2 * q, tb = ta + 1;
+    const bool live_a = ta < T, live_b = tb < T;   // an odd T leaves a lone frame; frames >= T are zero and their rows are not read
+    const long rowa = (row0 + ta) * NBIN, rowb = (row0 + tb) * NBIN;
+#pragma unroll 1
+    for (int k = lane; k < NBIN; k += 64) {
+      float ar = 0.f, ai = 0.f, br = 0.f, bim = 0.f;
+      if (live_a) { float s, c; const float m = mag[rowa + k]; sincosf(ang[rowa + k], &s, &c); ar = m * c; ai = m * s; }
+      if (live_b) { float s, c; const float m = mag[rowb + k]; sincosf(ang[rowb + k], &s, &c); br = m * c; bim = m * s; }
+      if ((k & (HOP - 1)) == 0) { ai = 0.f; bim = 0.f; }                    // k = 0 and 256: the spectrum of a real frame is real there
+      zb[k] = make_float2(ar - bim, -(ai + br));                           // conj Z[k], Z[k] = Xa[k] + i Xb[k]
+      if (k > 0 && k < HOP) zb[NFFT - k] = make_float2(ar + bim, ai - br); // conj Z[512 - k], Z[512 - k] = conj Xa[k] + i conj Xb[k]
+    }
+    __syncthreads();
+    float re[8], im[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float2 v = zb[lane + 64 * j]; re[j] = v.x; im[j] = v.y; }
+    __syncthreads();
+    fft8(re, im);
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+      const float2 c = tw[k * lane];
+      const float r = re[k] * c.x - im[k] * c.y, i = re[k] * c.y + im[k] * c.x;
+      re[k] = r; im[k] = i;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) zb[72 * k + lane] = make_float2(re[k], im[k]);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float2 v = zb[72 * k0 + 8 * j + n0]; re[j] = v.x; im[j] = v.y; }
+    __syncthreads();
+    fft8(re, im);
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+      const float2 c = tw[8 * n0 * k];
+      const float r = re[k] * c.x - im[k] * c.y, i = re[k] * c.y + im[k] * c.x;
+      re[k] = r; im[k] = i;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) zb[68 * n0 + 8 * k + k0] = make_float2(re[k], im[k]);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float2 v = zb[68 * j + lane]; re[j] = v.x; im[j] = v.y; }
+    fft8(re, im);                                  // 512 (xa - i xb)[lane + 64 k]
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float w = win[lane + 64 * k];
+      fr[2 * q][lane + 64 * k] = w * re[k];
+      fr[2 * q + 1][lane + 64 * k] = -(w * im[k]);
+    }
+    __syncthreads();                               // zb is written again on the next trip; after the last one fr is complete
+  }
+  const float w0 = win[tid], w1 = win[tid + HOP];
+  const float inv = 1.f / ((float)NFFT * (w0 * w0 + w1 * w1));
+  const long base = u.off[bi];
+  int clipped = 0;
+#pragma unroll 1
+  for (int g = 0; g < IBLOCKS; ++g) {
+    const int h = h0 + g;
+    if (h >= T) break;
+    const long i = (long)HOP * h + tid;
+    float v = 0.f;
+    if (h < T - 1) v = (fr[g][HOP + tid] + fr[g + 1][tid]) * inv;
+    else if (i >= L) break;                        // the tail 256 (T - 1) .. L is zero (librosa's length padding); nothing beyond L
+    if (wav) wav[base + i] = v;
+    if (pcm) {
+      const float r = rintf(v);
+      if (r > 32767.f || r < -32768.f) ++clipped;
+      pcm[base + i] = (short)fminf(32767.f, fmaxf(-32768.f, r));
+    }
+  }
+  if (pcm && clip_count) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) clipped += __shfl_xor(clipped, o, 64);
+    if (lane == 0 && clipped > 0) atomicAdd(clip_count, clipped);
+  }
+}
+
+// re2e_wav_sdr_sums: one workgroup per utterance, each thread a fixed run of indices into three double sums, then a fixed tree (as
+// wav_mix_scale_kernel): the same bits on every run.  1024 threads and SDR_UNROLL loads of each stream in flight per thread: the sums are
+// bound by the latency of the loads, not by the arithmetic.
+constexpr int SDR_THREADS = 1024, SDR_UNROLL = 4;          // a workgroup's stride is SDR_THREADS * SDR_UNROLL samples
+
+struct SdrUtt {
+  long roff[CHUNK], eoff[CHUNK], len[CHUNK];
+};
+
+__global__ __launch_bounds__(SDR_THREADS) void wav_sdr_sums_kernel(const short* __restrict__ ref, const float* __restrict__ est, const SdrUtt u,
+                                                                   int b0, double* __restrict__ sums) {
+  __shared__ double red[3][SDR_THREADS];
+  const int bi = blockIdx.x, tid = threadIdx.x;
+  const long n = u.len[bi];
+  const short* sp = ref + u.roff[bi];
+  const float* yp = est + u.eoff[bi];
+  double ss = 0.0, yy = 0.0, sy = 0.0;
+  for (long i0 = tid; i0 < n; i0 += SDR_THREADS * SDR_UNROLL) {
+    short sv[SDR_UNROLL];
+    float yv[SDR_UNROLL];
+#pragma unroll
+    for (int j = 0; j < SDR_UNROLL; ++j) {         // the loads of a trip first, then its sums in index order
+      const long i = i0 + SDR_THREADS * j;
+      const bool in = i < n;
+      sv[j] = in ? sp[i] : (short)0;
+      yv[j] = in ? yp[i] : 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < SDR_UNROLL; ++j) {         // an index beyond n adds exact zeros
+      const double s = (double)sv[j], y = (double)yv[j];
+      ss += s * s; yy += y * y; sy += s * y;
+    }
+  }
+  red[0][tid] = ss; red[1][tid] = yy; red[2][tid] = sy;
+  __syncthreads();
+  for (int h = SDR_THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) { red[0][tid] += red[0][tid + h]; red[1][tid] += red[1][tid + h]; red[2][tid] += red[2][tid + h]; }
+    __syncthreads();
+  }
+  if (tid < 3) sums[3 * (long)(b0 + bi) + tid] = red[tid][0];
+}
+
 }  // namespace
 
 extern "C" int re2e_wav_mix_scale(const short* pcm, const long* speech_off, const long* speech_len, const long* noise_off,
@@ -332,6 +487,59 @@ extern "C" int re2e_wav_stft(const short* pcm, const long* speech_off, const lon
     const dim3 grid(cdiv(Tmax, FRAMES), nb);
     if (noise_off) hipLaunchKernelGGL(wav_stft_kernel<true>, grid, dim3(256), 0, stream, pcm, u, scale, b0, Tmax, o, cmvn);
     else hipLaunchKernelGGL(wav_stft_kernel<false>, grid, dim3(256), 0, stream, pcm, u, scale, b0, Tmax, o, cmvn);
+    RE2E_LAUNCH_CHECK();
+  }
+  return RE2E_OK;
+}
+
+extern "C" int re2e_wav_istft(const float* mag, const float* ang, const long* out_off, const long* out_len, int B, int Tmax, long out_samples,
+                              float* wav_f32, short* pcm_out, int* clip_count, hipStream_t stream) {
+  RE2E_CHECK_ARG(mag && ang, "null operand (mag and ang are both needed)");
+  RE2E_CHECK_ARG(out_off && out_len, "null operand");
+  RE2E_CHECK_ARG(wav_f32 || pcm_out, "no output: wav_f32 and pcm_out are both NULL");
+  RE2E_CHECK_ARG(B > 0 && Tmax > 0 && out_samples > 0, "bad shape");
+  for (int b = 0; b < B; ++b) {
+    RE2E_CHECK_ARG(out_len[b] >= NBIN, "an utterance is shorter than 257 samples (the forward's reflect padding needs 257)");
+    RE2E_CHECK_ARG(out_len[b] <= LMAX, "an utterance has 2^31 samples or more");
+    RE2E_CHECK_ARG(1 + out_len[b] / HOP <= Tmax, "Tmax is below an utterance's frame count 1 + L / 256");
+    RE2E_CHECK_ARG(out_off[b] >= 0 && out_off[b] <= out_samples - out_len[b], "an output offset outside its range 0 .. out_samples - L");
+  }
+  if (ensure_tables() != 0) {
+    re2e_set_error("%s: could not upload the window and twiddle tables", __func__);
+    return RE2E_EHIP;
+  }
+  for (int b0 = 0; b0 < B; b0 += CHUNK) {
+    const int nb = B - b0 < CHUNK ? B - b0 : CHUNK;
+    IstftUtt u;
+    int Tlong = 0;                               // the longest utterance of the chunk sizes the grid
+    for (int i = 0; i < CHUNK; ++i) {
+      const int b = b0 + (i < nb ? i : 0);
+      u.off[i] = out_off[b]; u.len[i] = out_len[b];
+      const int T = 1 + (int)(out_len[b] / HOP);
+      if (T > Tlong) Tlong = T;
+    }
+    hipLaunchKernelGGL(wav_istft_kernel, dim3(cdiv(Tlong, IBLOCKS), nb), dim3(256), 0, stream, mag, ang, u, b0, Tmax, wav_f32, pcm_out, clip_count);
+    RE2E_LAUNCH_CHECK();
+  }
+  return RE2E_OK;
+}
+
+extern "C" int re2e_wav_sdr_sums(const short* ref_pcm, const long* ref_off, const float* est, const long* est_off, const long* len, int B,
+                                 double* sums, hipStream_t stream) {
+  RE2E_CHECK_ARG(ref_pcm && ref_off && est && est_off && len && sums, "null operand");
+  RE2E_CHECK_ARG(B > 0, "bad shape");
+  for (int b = 0; b < B; ++b) {
+    RE2E_CHECK_ARG(ref_off[b] >= 0 && est_off[b] >= 0, "negative offset");
+    RE2E_CHECK_ARG(len[b] >= 1 && len[b] <= LMAX, "length outside 1 .. 2^31 - 1");
+  }
+  for (int b0 = 0; b0 < B; b0 += CHUNK) {
+    const int nb = B - b0 < CHUNK ? B - b0 : CHUNK;
+    SdrUtt u;
+    for (int i = 0; i < CHUNK; ++i) {
+      const int b = b0 + (i < nb ? i : 0);
+      u.roff[i] = ref_off[b]; u.eoff[i] = est_off[b]; u.len[i] = len[b];
+    }
+    hipLaunchKernelGGL(wav_sdr_sums_kernel, dim3(nb), dim3(SDR_THREADS), 0, stream, ref_pcm, est, u, b0, sums);
     RE2E_LAUNCH_CHECK();
   }
   return RE2E_OK;

@@ -11,6 +11,7 @@ Two ways to get a matrix:
     shipped as ONE byte blob and decoded + padded (+ 10*log10 + CMVN) on the GPU by
     ``mix_data_loader.collate_kaldi_device`` (re2e_kaldi_decode_pad): 1 byte per element over PCIe instead of 4."""
 import gzip
+import os
 import re
 import struct
 
@@ -269,3 +270,21 @@ def write_mat_compressed(file_or_fd, m, key=''):
     finally:
         if fd is not file_or_fd:
             fd.close()
+
+
+class ArkScpWriter(object):
+    """One ark file and the scp lines that point into it (``key path:offset``, the offset just behind the key): what
+    ``copy-feats ark:- ark,scp:...`` writes, without the Kaldi binary."""
+
+    def __init__(self, ark, compress):
+        self.ark, self.fd, self.lines = os.path.abspath(ark), open(ark, 'wb'), []
+        self.write = write_mat_compressed if compress else write_mat
+
+    def add(self, key, m):
+        self.lines.append('%s %s:%d\n' % (key, self.ark, self.fd.tell() + len(key) + 1))
+        self.write(self.fd, np.ascontiguousarray(m, dtype=np.float32), key=key)
+
+    def close(self, scp):
+        self.fd.close()
+        with open(scp, 'w') as f:
+            f.writelines(self.lines)

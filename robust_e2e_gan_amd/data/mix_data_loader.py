@@ -7,7 +7,9 @@ zero-padded on the device by re2e_pack_pad -- 3 live tensors instead of 5 (cos_a
 clean_log_inputs are never read by joint_train.py).
 
 ``collate_wav_device`` / ``wav_features_device`` start from 16-bit PCM instead: the samples go over PCIe as ONE pinned int16 blob and
-re2e_wav_mix_scale / re2e_wav_stft (csrc/stft.hip) mix the noise in at the drawn SNR and produce the padded spectra on the device."""
+re2e_wav_mix_scale / re2e_wav_stft (csrc/stft.hip) mix the noise in at the drawn SNR and produce the padded spectra on the device.
+``wav_istft_device`` goes the other way (re2e_wav_istft: enhanced magnitudes and a phase back to samples) and ``wav_sdr_device`` scores the
+result against the clean samples (re2e_wav_sdr_sums: SNR and SI-SDR)."""
 import ctypes
 import logging
 
@@ -238,6 +240,68 @@ def wav_features_device(pcms, device, cmvn=None):
     ``feat_model`` and ``recognize`` -- the magnitude spectra (B,T,257), their normalised logs and the frame counts, in the order given."""
     o = wav_frontend_device(list(pcms), device, None, cmvn, ('clean', 'clean_log'))
     return o['clean'], o['clean_log'], torch.IntTensor([wav_frames_of(p.shape[0]) for p in pcms])
+
+
+def wav_istft_device(mag, ang, lengths, device, int16=True, blob=False, clip_count=None):
+    """Spectra back to samples on ``device`` (re2e_wav_istft, csrc/stft.hip): ``mag`` and ``ang`` (B,Tmax,257) fp32, ``lengths`` the sample
+    count L_b of every utterance (its frames are the rows t < 1 + L_b // 256; ``wav_frontend_device`` of L_b samples gives exactly those).
+    Samples 256 * (L_b // 256) .. L_b are zero (librosa's ``length`` padding).  ``int16``: rounded and saturated 16-bit samples, else fp32.
+    Returns one numpy array of L_b samples per utterance, or with ``blob`` the device blob and the offsets of the utterances in it
+    (nothing is read back).  ``clip_count``: a device int32 tensor incremented by the number of saturated samples."""
+    lens = [int(n) for n in lengths]
+    B = len(lens)
+    if mag.shape != ang.shape or mag.dim() != 3 or mag.shape[0] != B or mag.shape[2] != WAV_BINS:
+        raise ValueError('wav_istft_device takes mag and ang of shape (%d, Tmax, %d), got %s and %s' % (B, WAV_BINS, tuple(mag.shape), tuple(ang.shape)))
+    mag = mag.to(device).float().contiguous()
+    ang = ang.to(device).float().contiguous()
+    offs = [0] * B
+    for b in range(1, B):
+        offs[b] = offs[b - 1] + lens[b - 1]
+    total = offs[-1] + lens[-1]
+    out = torch.empty(max(total, 1), dtype=torch.int16 if int16 else torch.float32, device=device)
+    longs = lambda v: (ctypes.c_long * B)(*v)
+    call('re2e_wav_istft', mag.data_ptr(), ang.data_ptr(), longs(offs), longs(lens), B, int(mag.shape[1]), total,
+         None if int16 else out.data_ptr(), out.data_ptr() if int16 else None, clip_count.data_ptr() if clip_count is not None else None)
+    if blob:
+        return out, offs
+    host = out.cpu().numpy()
+    return [host[o:o + n] for o, n in zip(offs, lens)]
+
+
+def sdr_from_sums(ss, yy, sy):
+    """``{'snr', 'si_sdr'}`` in dB from sum s^2, sum y^2 and sum s y (re2e_wav_sdr_sums), in float64:
+    SNR = 10 log10(sum s^2 / sum (s - y)^2), SI-SDR = 10 log10(|a s|^2 / |a s - y|^2) with a = sum s y / sum s^2, i.e.
+    |a s|^2 = (sum s y)^2 / sum s^2 and |a s - y|^2 = sum y^2 - |a s|^2.  A zero denominator gives inf, a silent reference nan."""
+    ss, yy, sy = float(ss), float(yy), float(sy)
+    if ss <= 0.0:
+        return {'snr': float('nan'), 'si_sdr': float('nan')}
+    db = lambda num, den: float('inf') if den <= 0.0 else (float('-inf') if num <= 0.0 else 10.0 * float(np.log10(num / den)))
+    target = sy * sy / ss
+    return {'snr': db(ss, ss - 2.0 * sy + yy), 'si_sdr': db(target, yy - target)}
+
+
+def wav_sdr_device(ref_pcms, est_blob, offsets, lengths):
+    """SNR and SI-SDR of estimates on the device against int16 references: ``ref_pcms`` int16 arrays (uploaded as one blob), ``est_blob``
+    the fp32 device blob of ``wav_istft_device(..., int16=False, blob=True)`` with its ``offsets``; utterance b is compared over its
+    first ``lengths[b]`` samples.  The three sums per utterance are taken in double on the device (re2e_wav_sdr_sums); returns one
+    ``{'snr', 'si_sdr'}`` dict per utterance."""
+    B = len(ref_pcms)
+    lens = [int(n) for n in lengths]
+    device = est_blob.device
+    if est_blob.dtype != torch.float32:
+        raise ValueError('wav_sdr_device takes the fp32 estimate blob, got %s' % est_blob.dtype)
+    roff, pos = [], 0
+    for r, n, o in zip(ref_pcms, lens, offsets):
+        if r.dtype != np.int16 or r.ndim != 1 or r.shape[0] < n or int(o) + n > est_blob.numel():
+            raise ValueError('wav_sdr_device: a reference is not 1-D int16, or a length reaches beyond its reference or the estimate blob')
+        roff.append(pos)
+        pos += r.shape[0]
+    host = torch.from_numpy(np.concatenate(ref_pcms))
+    ref = (host.pin_memory() if device.type == 'cuda' else host).to(device, non_blocking=True)
+    sums = torch.empty(B, 3, dtype=torch.float64, device=device)
+    longs = lambda v: (ctypes.c_long * B)(*[int(x) for x in v])
+    call('re2e_wav_sdr_sums', ref.data_ptr(), longs(roff), est_blob.data_ptr(), longs(offsets), longs(lens), B, sums.data_ptr())
+    return [sdr_from_sums(*row) for row in sums.cpu().tolist()]
 
 
 class BucketingSampler(object):

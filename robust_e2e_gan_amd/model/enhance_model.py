@@ -187,6 +187,20 @@ class EnhanceModel(ModelBase):
             loss = ops.mean_loss(enhance_out, tgt, 0.0, lib.LOSS_L2) * (enhance_out.numel() / n)
         return loss, enhance_out
 
+    def enhance_wav(self, pcms, cmvn=None):
+        """Waveforms in, enhanced waveforms out (no reference counterpart: upstream stops at the enhanced features): ``pcms`` int16 arrays,
+        one per utterance; returns int16 arrays of the same lengths.  re2e_wav_stft (magnitudes, normalised logs with the data set's
+        ``cmvn`` (2,257), phase) -> the masked inference forward -> re2e_wav_istft with the INPUT's phase.  Samples 256 * (L // 256) .. L of
+        an utterance come back zero (no frame pair covers them).  The U-Net types keep their rule that T is a multiple of 32."""
+        from ..data.mix_data_loader import wav_frames_of, wav_frontend_device, wav_istft_device
+        pcms = list(pcms)
+        with torch.no_grad():
+            dev = next(self.parameters()).device
+            o = wav_frontend_device(pcms, dev, None, cmvn, ('clean', 'clean_log', 'clean_ang'))
+            sizes = torch.IntTensor([wav_frames_of(p.shape[0]) for p in pcms])
+            out = self.forward(o['clean'], o['clean_log'], sizes)
+            return wav_istft_device(out, o['clean_ang'], [p.shape[0] for p in pcms], dev, int16=True)
+
     def calculate_all_specgram(self, mix_inputs, mix_log_inputs, input_sizes):
         """enhance_model.py:188-217: same as forward but WITHOUT the length mask."""
         with torch.no_grad():

@@ -16,28 +16,12 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
-
 from robust_e2e_gan_amd.data import kaldi_io, wav_io
 from robust_e2e_gan_amd.data.mix_data_loader import wav_frames_of, wav_frontend_device
 from robust_e2e_gan_amd.data.wav_dataset import draw_mixture
 
 
-class _Table(object):
-    """One ark file and the scp lines that point into it (``key path:offset``, the offset just behind the key)."""
-
-    def __init__(self, ark, compress):
-        self.ark, self.fd, self.lines = os.path.abspath(ark), open(ark, 'wb'), []
-        self.write = kaldi_io.write_mat_compressed if compress else kaldi_io.write_mat
-
-    def add(self, key, m):
-        self.lines.append('%s %s:%d\n' % (key, self.ark, self.fd.tell() + len(key) + 1))
-        self.write(self.fd, np.ascontiguousarray(m, dtype=np.float32), key=key)
-
-    def close(self, scp):
-        self.fd.close()
-        with open(scp, 'w') as f:
-            f.writelines(self.lines)
+_Table = kaldi_io.ArkScpWriter          # one ark file and the scp lines that point into it
 
 
 def prepare(data_dir, feat_dir, noise_repeat_num=1, compress=True, seed=0, device='cuda', batch=16):
