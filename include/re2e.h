@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 334
+#define RE2E_ABI_VERSION 335
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -745,6 +745,28 @@ int re2e_wlm_multilevel_fix(const float* lsm, const float* wlm_logprobs, int n, 
 int re2e_beam_prune(const int* seg_off_dev, int U, int max_seg_rows, const float* hyp_score, const float* local, const int* cand_dev, int nh,
                     int ncand, int beam, int* parent_out, int* col_out, int* label_out, float* score_out, int* count_out, void* workspace,
                     size_t workspace_bytes, re2e_stream_t stream);
+
+/* ---- K12 scoring (csrc/align.hip): weighted edit-distance alignment of n_pairs pairs of integer label sequences in one launch -- in practice
+ * every n-best hypothesis of every utterance of a test set (utils/score.py).  ref_labels / hyp_labels: flat int32 arrays on the device, of
+ * n_ref_labels / n_hyp_labels entries; ref_off_host (n_ref + 1) and hyp_off_host (n_pairs + 1): offsets into them; pair_ref_host (n_pairs): the
+ * reference of pair n, so that an utterance's n-best shares one reference.  The three tables are HOST arrays: the call checks them (offsets
+ * non-decreasing and inside the arrays, pair_ref in range, lengths within the limit), copies them to the head of the workspace and waits for
+ * that copy on `stream`; a table that fails a check launches nothing and leaves the outputs untouched.
+ *   D[0][0] = 0, D[i][0] = i deletions, D[0][j] = j insertions; cell (i, j) takes the best of, in this order, the diagonal (ref[i-1] == hyp[j-1]:
+ *   a correct label at cost 0, else a substitution at c_sub), a deletion from (i-1, j) at c_del, an insertion from (i, j-1) at c_ins.  Best: the
+ *   smallest (cost, number of errors S+D+I) pair, compared lexicographically; on a full tie the earlier candidate.  Exact integers throughout.
+ * counts (n_pairs, 6) int32 = cost, errors, C, S, D, I of the path those choices define.  path (optional, with path_off_host (n_pairs + 1), host,
+ * non-decreasing, pair n owning at least |ref| + |hyp| bytes, the last offset <= path_bytes): the path from its start, one byte per step
+ * ('C' / 'S' / 'D' / 'I'); the rest of the pair's bytes is set to 0, nothing else is touched.  Every output is a function of its pair alone:
+ * two calls give the same bytes.  Costs 1 .. 255 (RE2E_EINVAL beyond); at most 1024 labels per sequence (RE2E_EUNSUPPORTED beyond); empty
+ * sequences are legal.  workspace: re2e_align_counts_workspace_bytes of the same tables (with_path: 2 bits per cell on top of the tables; 0 when
+ * the tables fail the checks, with the message set), 16-byte aligned. */
+size_t re2e_align_counts_workspace_bytes(const int* ref_off_host, int n_ref, const int* hyp_off_host, const int* pair_ref_host, int n_pairs,
+                                         int with_path);
+int re2e_align_counts(const int* ref_labels, const int* ref_off_host, int n_ref, long n_ref_labels, const int* hyp_labels,
+                      const int* hyp_off_host, const int* pair_ref_host, int n_pairs, long n_hyp_labels, int c_sub, int c_ins, int c_del,
+                      int* counts, unsigned char* path, const long* path_off_host, long path_bytes, void* workspace, size_t workspace_bytes,
+                      re2e_stream_t stream);
 
 /* ---- K11 optimizer (joint_train.py:131-140,188-193; Appendix A.16) ------------------------ */
 /* stats[0]=||g||_2, stats[1]=clip coefficient (<=1), stats[2]=1 if finite else 0; from sumsq[0];

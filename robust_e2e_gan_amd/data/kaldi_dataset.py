@@ -148,3 +148,88 @@ class MixKaldiDataset(torch.utils.data.Dataset):
         cos = np.cos(kaldi_io.read_mat(self.clean_angles[clean_id]) - kaldi_io.read_mat(self.mix_angles[mix_id]))
         F = torch.FloatTensor
         return (mix_id, self.utt2spk[clean_id], F(clean_spect), F(clean_log), F(mix_spect), F(mix_log), F(cos), torch.LongTensor(target))
+
+
+class SequentialKaldiDataset(torch.utils.data.Dataset):
+    """Single-stream data set of the recognisers (mirror of SequentialDataset, data/data_loader.py:15-233, for ``feat_type``
+    'kaldi_magspec' / 'kaldi_fbank'): ``feats.scp``, ``utt2spk``, ``text_char`` | ``text_word`` and the dictionary file;
+    ``kaldi_feat_len.scp`` (frame counts) is created on first use (:42-43).  An utterance ``<id>__<noise...>`` that has no speaker or
+    transcript of its own takes those of ``<id>`` (:182-204).
+
+    ``__getitem__`` returns the reference's 5-tuple of host tensors (``raw=False``: decoded, clamped at 1e-7, log + CMVN on the host as
+    upstream) or ``(utt, spk, RawMat, target list)`` (``raw=True``) for ``mix_data_loader.decode_pad_device``, which does the same on the
+    GPU for a whole batch."""
+
+    def __init__(self, args, data_dir, dict_file, raw=False):
+        self.args, self.raw = args, raw
+        self.feat_type = getattr(args, 'feat_type', 'kaldi_magspec')
+        if self.feat_type not in ('kaldi_magspec', 'kaldi_fbank'):
+            raise ValueError('SequentialKaldiDataset reads Kaldi tables only (feat_type kaldi_magspec / kaldi_fbank), not %r' % (self.feat_type,))
+        self.data_dir = data_dir
+        self.spe_ids = _read_table(os.path.join(data_dir, 'feats.scp'))
+        if not self.spe_ids:
+            raise ValueError('%s lists no utterance' % os.path.join(data_dir, 'feats.scp'))
+        len_scp = os.path.join(data_dir, 'kaldi_feat_len.scp')
+        if not os.path.exists(len_scp):
+            with open(len_scp, 'w') as f:
+                for utt, path in self.spe_ids:
+                    f.write('%s %d\n' % (utt, kaldi_io.read_mat_raw(path).rows))
+        known = {k: int(v) for k, v in _read_table(len_scp)}
+        self.lengths = [known[utt] if utt in known else kaldi_io.read_mat_raw(path).rows for utt, path in self.spe_ids]      # :214-224
+        self.feat_size = kaldi_io.read_mat_raw(self.spe_ids[0][1]).cols
+        self.utt2spk = dict(_read_table(os.path.join(data_dir, 'utt2spk')))
+        self.char_list = read_dictionary(dict_file)
+        self.num_classes = len(self.char_list)
+        unit = getattr(args, 'model_unit', 'char')
+        self.targets, self.labeldist = read_targets(os.path.join(data_dir, 'text_char' if unit == 'char' else 'text_word'), self.char_list, unit)
+        self.num_utt_cmvn = getattr(args, 'num_utt_cmvn', 20000)
+        self.cmvn = self._load_cmvn() if getattr(args, 'normalize_type', 1) == 1 else None
+
+    def compute_cmvn(self):
+        """[-mean; 1/sqrt(var)] of 10*log10(max(x,1e-7)) over ``num_utt_cmvn`` random utterances (:140-177)."""
+        n = min(len(self.spe_ids), self.num_utt_cmvn)
+        s, sq, frames = np.zeros((1, self.feat_size), np.float32), np.zeros((1, self.feat_size), np.float32), 0
+        for i in np.random.permutation(len(self.spe_ids))[:n]:
+            x = kaldi_io.read_mat(self.spe_ids[i][1])
+            x[x <= 1e-7] = 1e-7
+            f = 10 * np.log10(x)
+            s, sq, frames = s + f.sum(0), sq + np.square(f).sum(0), frames + f.shape[0]
+        mean = s / frames
+        return np.concatenate([-mean, 1 / np.sqrt(sq / frames - np.square(mean))], 0).astype(np.float32)
+
+    def _load_cmvn(self):
+        exp = getattr(self.args, 'exp_path', None)
+        path = os.path.join(exp, 'cmvn.npy') if exp else None
+        if path and os.path.exists(path):
+            cm = np.load(path)
+            if cm.shape[1] == self.feat_size:
+                return cm
+        cm = self.compute_cmvn()
+        if path:
+            os.makedirs(exp, exist_ok=True)
+            np.save(path, cm)
+        return cm
+
+    def __len__(self):
+        return len(self.spe_ids)
+
+    def _lookup(self, table, utt, what):
+        if utt in table:
+            return table[utt]
+        clean = utt.split('__')[0]
+        if clean in table:
+            return table[clean]
+        raise KeyError('utterance %s of %s has no %s (neither has %s)' % (utt, os.path.join(self.data_dir, 'feats.scp'), what, clean))
+
+    def __getitem__(self, index):
+        utt, path = self.spe_ids[index]
+        spk = self._lookup(self.utt2spk, utt, 'speaker in utt2spk')
+        target = self._lookup(self.targets, utt, 'transcript')
+        if self.raw:
+            return utt, spk, kaldi_io.read_mat_raw(path), list(target)
+        x = kaldi_io.read_mat(path)
+        x[x <= 1e-7] = 1e-7
+        log = 10 * np.log10(x)
+        if self.cmvn is not None:
+            log = (log + self.cmvn[0, :]) * self.cmvn[1, :]
+        return utt, spk, torch.FloatTensor(x), torch.FloatTensor(log.astype(np.float32)), torch.LongTensor(target)
