@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 335
+#define RE2E_ABI_VERSION 336
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -322,6 +322,38 @@ int re2e_wav_istft(const float* mag, const float* ang, const long* out_off, cons
                    float* wav_f32, short* pcm_out, int* clip_count, re2e_stream_t stream);
 int re2e_wav_sdr_sums(const short* ref_pcm, const long* ref_off, const float* est, const long* est_off, const long* len, int B,
                       double* sums, re2e_stream_t stream);
+
+/* Reverberation (csrc/reverb.hip; data/audioparse.py:254-303 Make_Reverberation = np.convolve(rir, x)[:len(x)], Make_Noisy_Wave): a batch of
+ * n_jobs independent truncated FIR filters on the exact-fp32 matrix instruction.  pcm: the device blob of 16-bit samples (pcm_samples of
+ * them), used as they are; rir: a device blob of rir_floats fp32 taps.  src_off / src_len / first / count / rir_off / rir_len / dst_off:
+ * HOST arrays of n_jobs entries, checked here and passed as kernel arguments (jobs go 32 to a launch, as the utterances of
+ * re2e_wav_stft), so nothing has to stay alive after the call.  Job q has the source x[j] = pcm[src_off[q] + j], 0 <= j < src_len[q] (zero
+ * for j < 0), the filter h[k] = rir[rir_off[q] + k], 0 <= k < K = rir_len[q], and writes, for 0 <= i < count[q],
+ *   y[i] = sum_{k < K} h[k] x[first[q] + i - k]
+ * to wav_f32[dst_off[q] + i] (fp32) and / or pcm_out[dst_off[q] + i] (int16: rintf of the value wav_f32 holds, saturated to
+ * -32768 .. 32767; *clip_count, device int, optional, is incremented by the number of saturated samples).  Both outputs hold out_samples
+ * samples; nothing outside the n_jobs destination ranges is written.  The summation order of every output is fixed (ascending taps in
+ * fp32, no atomics): two runs agree bit for bit.  pcm_out may be pcm itself (the reverberant signals land behind the uploaded samples of
+ * one allocation).  Refused with a message, before anything is launched: first + count > src_len, K < 1 or K > RE2E_WAV_RIR_MAX, first < 0,
+ * count < 1, a source range outside 0 .. pcm_samples, a filter range outside 0 .. rir_floats, a destination range outside 0 .. out_samples,
+ * both outputs NULL, n_jobs < 1, and with pcm_out == pcm a destination range that overlaps any source range [src_off, src_off + src_len)
+ * of the same call.
+ * re2e_wav_reverb_geometry(which): 0 the K-tile (taps staged at a time), 1 the outputs per workgroup, 2 the jobs per launch,
+ * 3 RE2E_WAV_RIR_MAX, 4 the contraction steps a K-tile is rounded up to; -1 otherwise.  The kernel takes other paths at their multiples (tests place their edges there).
+ *
+ * re2e_wav_stft_rev: re2e_wav_stft with a mixture that has its own speech stream, mix_off (HOST, B entries): the clean stream is still
+ * s = pcm[speech_off[b] ..), the dry signal, and the mixture is m[i] = pcm[mix_off[b] + i] + g n[(s0 + i) mod N] (Make_Noisy_Wave changes the
+ * noisy signal only; the L samples at mix_off[b] are the reverberant speech, the noise file is the reverberated noise).  M is the spectrum
+ * of m itself; every output keeps its definition.  mix_off requires the noise arrays and scale; mix_off == NULL is re2e_wav_stft, the
+ * same launches bit for bit.  re2e_wav_mix_scale called with mix_off as its speech_off gives the reference's g (SNR after reverberation). */
+#define RE2E_WAV_RIR_MAX 32768        /* taps: 2.048 s at 16 kHz */
+int re2e_wav_reverb(const short* pcm, long pcm_samples, const float* rir, long rir_floats, const long* src_off, const long* src_len,
+                    const long* first, const long* count, const long* rir_off, const long* rir_len, const long* dst_off, int n_jobs,
+                    long out_samples, float* wav_f32, short* pcm_out, int* clip_count, re2e_stream_t stream);
+int re2e_wav_reverb_geometry(int which);
+int re2e_wav_stft_rev(const short* pcm, const long* speech_off, const long* mix_off, const long* speech_len, const long* noise_off,
+                      const long* noise_len, const long* noise_start, const float* scale, int B, int Tmax, float* clean, float* clean_log,
+                      float* mix, float* mix_log, float* cos_out, float* clean_ang, float* mix_ang, const float* cmvn, re2e_stream_t stream);
 
 /* ---- K2 fused fbank (model/feat_model.py:118-135): y = log(max((x^2) W, 1e-7)); optional
  * second output y_norm = (y + cmvn[0]) * cmvn[1]; optional third output pw_out = (x^2) W itself, which re2e_fbank_bwd takes

@@ -36,6 +36,11 @@ constexpr float FLOOR = 1e-7f;
 struct WavUtt {                                  // read-only kernel argument (uniform index: scalar loads, nothing is copied)
   long soff[CHUNK], slen[CHUNK], noff[CHUNK], nlen[CHUNK], s0[CHUNK];
 };
+struct WavUttRev : WavUtt {                      // re2e_wav_stft_rev: the mixture's own speech stream
+  long moff[CHUNK];
+};
+template <bool REV> struct UttOf { typedef WavUtt type; };
+template <> struct UttOf<true> { typedef WavUttRev type; };
 struct WavRatio {
   double r[CHUNK];                               // 10^(dB/10), taken in double on the host
 };
@@ -77,8 +82,10 @@ __device__ __forceinline__ void zero_rows(float* p, long first, int n, int tid) 
   for (int i = tid; i < n; i += 256) p[first + i] = 0.f;
 }
 
-template <bool NOISE>
-__global__ __launch_bounds__(256) void wav_stft_kernel(const short* __restrict__ pcm, const WavUtt u, const float* __restrict__ scale,
+// REV (re2e_wav_stft_rev; needs NOISE): the imaginary half of z is w (rs + g n), rs = pcm[moff ..) the mixture's own (reverberant) speech,
+// and M is that half's spectrum itself; C stays the spectrum of the dry s.
+template <bool NOISE, bool REV = false>
+__global__ __launch_bounds__(256) void wav_stft_kernel(const short* __restrict__ pcm, const typename UttOf<REV>::type u, const float* __restrict__ scale,
                                                        int b0, int Tmax, const WavOut o, const float* __restrict__ cmvn) {
   __shared__ float win[NFFT];
   __shared__ float2 tw[NFFT];
@@ -103,6 +110,8 @@ __global__ __launch_bounds__(256) void wav_stft_kernel(const short* __restrict__
   {
     const short* sp = pcm + u.soff[bi];
     const short* np = NOISE ? pcm + u.noff[bi] : nullptr;
+    const short* mp = nullptr;
+    if constexpr (REV) mp = pcm + u.moff[bi];
     const unsigned N = NOISE ? (unsigned)u.nlen[bi] : 1u, s0 = NOISE ? (unsigned)u.s0[bi] : 0u;
     const long first = (long)HOP * (t0 - 1);
     for (int j = tid; j < RUN; j += 256) {
@@ -110,7 +119,8 @@ __global__ __launch_bounds__(256) void wav_stft_kernel(const short* __restrict__
       const long r = i < 0 ? -i : (i >= L ? 2 * (L - 1) - i : i);          // reflect (librosa center=True)
       const bool in = r >= 0 && r < L;                                     // false only under frames >= T, which are not transformed
       xs[j] = in ? (float)sp[r] : 0.f;
-      if (NOISE) xn[j] = in ? g * (float)np[(s0 + (unsigned)r) % N] : 0.f; // s0 + r < 2^32
+      if (NOISE && !REV) xn[j] = in ? g * (float)np[(s0 + (unsigned)r) % N] : 0.f; // s0 + r < 2^32
+      if (REV) xn[j] = in ? (float)mp[r] + g * (float)np[(s0 + (unsigned)r) % N] : 0.f;
     }
   }
   __syncthreads();
@@ -174,13 +184,13 @@ __global__ __launch_bounds__(256) void wav_stft_kernel(const short* __restrict__
             cr = zk.x; ci = zk.y;
           }
           if (real_bin) { ci = 0.f; ni = 0.f; }
-          if (g == 0.f) { nr = 0.f; ni = 0.f; }                               // no noise (zero-power segment): M is C bit for bit
+          if (!REV && g == 0.f) { nr = 0.f; ni = 0.f; }                       // no noise (zero-power segment): M is C bit for bit
           const float cm = sqrtf(cr * cr + ci * ci);
           v_clean = cm < FLOOR ? FLOOR : cm;
           v_clog = (10.f * log10f(v_clean) + m0) * m1;
           v_cang = atan2f(ci, cr);
           if (NOISE) {
-            const float mr = cr + nr, mi = ci + ni;
+            const float mr = REV ? nr : cr + nr, mi = REV ? ni : ci + ni;
             const float mm = sqrtf(mr * mr + mi * mi);
             v_mix = mm < FLOOR ? FLOOR : mm;
             v_mlog = (10.f * log10f(v_mix) + m0) * m1;
@@ -487,6 +497,39 @@ extern "C" int re2e_wav_stft(const short* pcm, const long* speech_off, const lon
     const dim3 grid(cdiv(Tmax, FRAMES), nb);
     if (noise_off) hipLaunchKernelGGL(wav_stft_kernel<true>, grid, dim3(256), 0, stream, pcm, u, scale, b0, Tmax, o, cmvn);
     else hipLaunchKernelGGL(wav_stft_kernel<false>, grid, dim3(256), 0, stream, pcm, u, scale, b0, Tmax, o, cmvn);
+    RE2E_LAUNCH_CHECK();
+  }
+  return RE2E_OK;
+}
+
+extern "C" int re2e_wav_stft_rev(const short* pcm, const long* speech_off, const long* mix_off, const long* speech_len, const long* noise_off,
+                                 const long* noise_len, const long* noise_start, const float* scale, int B, int Tmax, float* clean,
+                                 float* clean_log, float* mix, float* mix_log, float* cos_out, float* clean_ang, float* mix_ang, const float* cmvn,
+                                 hipStream_t stream) {
+  if (!mix_off)
+    return re2e_wav_stft(pcm, speech_off, speech_len, noise_off, noise_len, noise_start, scale, B, Tmax, clean, clean_log, mix, mix_log, cos_out,
+                         clean_ang, mix_ang, cmvn, stream);
+  RE2E_CHECK_ARG(pcm && speech_off && speech_len, "null operand");
+  RE2E_CHECK_ARG(B > 0 && Tmax > 0, "bad shape");
+  RE2E_CHECK_ARG(noise_off && noise_len && noise_start, "mix_off without noise (noise_off / noise_len / noise_start)");
+  RE2E_CHECK_ARG(scale, "noise without a scale (re2e_wav_mix_scale writes it)");
+  for (int b = 0; b < B; ++b) {
+    const char* why = check_utt(speech_off, speech_len, noise_off, noise_len, noise_start, b);
+    RE2E_CHECK_ARG(!why, why);
+    RE2E_CHECK_ARG(mix_off[b] >= 0, "negative mixture offset");
+    RE2E_CHECK_ARG(1 + speech_len[b] / HOP <= Tmax, "Tmax is below an utterance's frame count 1 + L / 256");
+  }
+  if (ensure_tables() != 0) {
+    re2e_set_error("%s: could not upload the window and twiddle tables", __func__);
+    return RE2E_EHIP;
+  }
+  const WavOut o = {clean, clean_log, mix, mix_log, cos_out, clean_ang, mix_ang};
+  for (int b0 = 0; b0 < B; b0 += CHUNK) {
+    const int nb = B - b0 < CHUNK ? B - b0 : CHUNK;
+    WavUttRev u;
+    fill_chunk(u, speech_off, speech_len, noise_off, noise_len, noise_start, b0, nb);
+    for (int i = 0; i < CHUNK; ++i) u.moff[i] = mix_off[b0 + (i < nb ? i : 0)];
+    hipLaunchKernelGGL((wav_stft_kernel<true, true>), dim3(cdiv(Tmax, FRAMES), nb), dim3(256), 0, stream, pcm, u, scale, b0, Tmax, o, cmvn);
     RE2E_LAUNCH_CHECK();
   }
   return RE2E_OK;

@@ -161,12 +161,70 @@ def _zero_noise_counter(device):
     return st
 
 
-def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'mix', 'mix_log'), Tmax=None, pool=None):
+_reverb_clip = {}         # device -> the same four for the samples re2e_wav_reverb saturated
+
+
+def _reverb_clip_counter(device):
+    """The device counter re2e_wav_reverb increments for every reverberant sample it saturated to int16; read one batch late, as the
+    zero-power counter."""
+    key = str(device)
+    st = _reverb_clip.get(key)
+    if st is None:
+        st = _reverb_clip[key] = [torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32).pin_memory(), None, 0]
+    counter, host, ev, seen = st
+    if ev is not None and ev.query():
+        n = int(host[0])
+        if n > seen:
+            logging.getLogger(__name__).warning('%d reverberant sample(s) clipped at the 16-bit range so far', n)
+            st[3] = n
+        st[2] = None
+    return st
+
+
+def reverb_jobs(speech, noise, rirs, pos):
+    """The convolutions of one reverberant batch, as re2e_wav_reverb takes them (pure host arithmetic, no device).  ``speech``: one
+    ``(offset, L)`` per utterance, ``noise``: one ``(offset, N, s0)``, ``rirs``: one ``((offset, taps) | None, (offset, taps) | None)`` for
+    speech and noise, ``pos``: the first free sample behind the uploaded ones.  Returns ``(jobs, mix_off, noise, end)``: ``jobs`` rows of
+    ``(src_off, src_len, first, count, rir_off, rir_len, dst_off)``, the offset of every utterance's mixture speech (its own offset without
+    a speech RIR), the ``(offset, N, s0)`` the mixture reads its noise with, and the first free sample behind the destinations.
+    The noise follows the reference's order -- the whole file is reverberated, cut to the file's length, tiled and sliced -- without
+    filtering samples nobody reads: a segment inside the file is one job (the new file is the segment, start 0), one that wraps once is
+    two jobs to consecutive destinations, and a segment longer than the file takes the whole file and keeps its start."""
+    jobs, mix_off, noise_out = [], [], []
+    for (soff, L), (noff, N, s0), (hs, hn) in zip(speech, noise, rirs):
+        if hs is None:
+            mix_off.append(soff)
+        else:
+            jobs.append((soff, L, 0, L, hs[0], hs[1], pos))
+            mix_off.append(pos)
+            pos += L
+        if hn is None:
+            noise_out.append((noff, N, s0))
+        elif L > N:
+            jobs.append((noff, N, 0, N, hn[0], hn[1], pos))
+            noise_out.append((pos, N, s0))
+            pos += N
+        else:
+            head = min(L, N - s0)
+            jobs.append((noff, N, s0, head, hn[0], hn[1], pos))
+            if head < L:
+                jobs.append((noff, N, 0, L - head, hn[0], hn[1], pos + head))
+            noise_out.append((pos, L, 0))
+            pos += L
+    return jobs, mix_off, noise_out, pos
+
+
+def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'mix', 'mix_log'), Tmax=None, pool=None, reverb=None):
     """16-bit PCM -> spectra on ``device``, all work enqueued on the CURRENT stream.  ``speech``: int16 arrays, one per utterance, in the
     order of the batch rows; ``noise``: None (clean stream only) or one ``(noise int16 array, s0, dB)`` per utterance -- the mixture is
     ``s[i] + g * n[(s0 + i) % len(n)]`` with ``g = sqrt(sum s^2 / (P * 10^(dB/10)))``, P the power of that noise segment.  Arrays that are the
     same object are uploaded once.  Returns ``{name: (B, Tmax, 257) fp32}`` for the names in ``want`` (WAV_OUTPUTS), plus 'scale' (B,) with
-    noise.  A noise segment of zero power gives g = 0 and is counted on the device (the reference draws another file instead)."""
+    noise.  A noise segment of zero power gives g = 0 and is counted on the device (the reference draws another file instead).
+    ``reverb`` (with ``noise``): None or one ``(h_speech | None, h_noise | None)`` of fp32 taps per utterance (Make_Noisy_Wave): the mixture
+    is then ``conv(h_s, s)[:L][i] + g * r[(s0 + i) % len(n)]``, ``r = conv(h_n, n)[:len(n)]``, g from the powers AFTER reverberation, while
+    'clean' stays the dry ``s``.  The distinct RIR arrays go up once in a pinned fp32 blob; the reverberant signals are rounded to int16
+    behind the uploaded samples of the same allocation (re2e_wav_reverb), the spectra come from re2e_wav_stft_rev.  Reverberant samples
+    that saturate are counted on the device and logged one batch late."""
     bad = [w for w in want if w not in WAV_OUTPUTS]
     if bad:
         raise ValueError('unknown front-end output %r (one of %s)' % (bad[0], ', '.join(WAV_OUTPUTS)))
@@ -193,11 +251,41 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
         nlen = [int(n[0].shape[0]) for n in noise]
         s0 = [int(n[1]) % max(ln, 1) for n, ln in zip(noise, nlen)]
         db = (ctypes.c_float * B)(*[float(n[2]) for n in noise])
+    if reverb is not None and not any(h is not None for pair in reverb for h in pair):
+        reverb = None                                # a batch without a reverberant item launches what it launches without RIRs
+    if reverb is not None:
+        if noise is None:
+            raise ValueError('reverb needs noise: the reverberant signal is the mixture\'s speech stream')
+        taps, hwhere, hpos = [], {}, 0
+
+        def place_rir(h):
+            nonlocal hpos
+            if h is None:
+                return None
+            if h.dtype != np.float32 or h.ndim != 1 or h.shape[0] < 1:
+                raise ValueError('an impulse response is a 1-D float32 array, got %s %s' % (h.dtype, h.shape))
+            if id(h) not in hwhere:
+                hwhere[id(h)] = hpos
+                taps.append(h)
+                hpos += h.shape[0]
+            return hwhere[id(h)], int(h.shape[0])
+        rirs = [(place_rir(hs), place_rir(hn)) for hs, hn in reverb]
+        jobs, moff, nz, total = reverb_jobs(list(zip(soff, lens)), list(zip(noff, nlen, s0)), rirs, pos)
+        noff, nlen, s0 = [z[0] for z in nz], [z[1] for z in nz], [z[2] for z in nz]
+        hhost = pool.get('rir', 4 * hpos).view(torch.float32) if pool is not None else torch.empty(hpos, dtype=torch.float32)
+        if pool is None and on_gpu:
+            hhost = hhost.pin_memory()
+        np.concatenate(taps, out=hhost.numpy())
+        hblob = hhost.to(device, non_blocking=True)
     host = pool.get('wav', 2 * pos).view(torch.int16) if pool is not None else torch.empty(pos, dtype=torch.int16)
     if pool is None and on_gpu:
         host = host.pin_memory()
     np.concatenate(arrays, out=host.numpy())
-    blob = host.to(device, non_blocking=True)
+    if reverb is None:
+        blob = host.to(device, non_blocking=True)
+    else:                                            # room behind the uploaded samples for the reverberant signals
+        blob = torch.empty(total, dtype=torch.int16, device=device)
+        blob[:pos].copy_(host, non_blocking=True)
     out = {k: torch.empty(B, Tmax, WAV_BINS, dtype=torch.float32, device=device) for k in want}
     cm = cmvn.to(device).float().contiguous() if cmvn is not None else None
     p = lambda k: out[k].data_ptr() if k in out else None
@@ -208,9 +296,24 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
         st = _zero_noise_counter(device)
         scale = torch.empty(B, dtype=torch.float32, device=device)
         idx = (longs(soff), longs(lens), longs(noff), longs(nlen), longs(s0))
-        call('re2e_wav_mix_scale', blob.data_ptr(), *idx, db, B, scale.data_ptr(), st[0].data_ptr())
-        call('re2e_wav_stft', blob.data_ptr(), *idx, scale.data_ptr(), B, Tmax, *[p(k) for k in WAV_OUTPUTS],
-             cm.data_ptr() if cm is not None else None)
+        if reverb is None:
+            call('re2e_wav_mix_scale', blob.data_ptr(), *idx, db, B, scale.data_ptr(), st[0].data_ptr())
+            call('re2e_wav_stft', blob.data_ptr(), *idx, scale.data_ptr(), B, Tmax, *[p(k) for k in WAV_OUTPUTS],
+                 cm.data_ptr() if cm is not None else None)
+        else:
+            clip = _reverb_clip_counter(device)
+            cols = [(ctypes.c_long * len(jobs))(*[int(j[c]) for j in jobs]) for c in range(7)]
+            call('re2e_wav_reverb', blob.data_ptr(), total, hblob.data_ptr(), hpos, *cols, len(jobs), total, None, blob.data_ptr(),
+                 clip[0].data_ptr())
+            call('re2e_wav_mix_scale', blob.data_ptr(), longs(moff), *idx[1:], db, B, scale.data_ptr(), st[0].data_ptr())
+            call('re2e_wav_stft_rev', blob.data_ptr(), idx[0], longs(moff), *idx[1:], scale.data_ptr(), B, Tmax, *[p(k) for k in WAV_OUTPUTS],
+                 cm.data_ptr() if cm is not None else None)
+            if on_gpu:
+                hblob.record_stream(torch.cuda.current_stream())
+                if clip[2] is None:
+                    clip[1].copy_(clip[0], non_blocking=True)
+                    clip[2] = torch.cuda.Event()
+                    clip[2].record(torch.cuda.current_stream())
         out['scale'] = scale
         if st[2] is None and on_gpu:
             st[1].copy_(st[0], non_blocking=True)
@@ -222,13 +325,15 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
 
 
 def collate_wav_device(batch, device, cmvn=None, want=('clean', 'mix', 'mix_log'), pool=None):
-    """Device-side collate for ``MixWavDataset``.  ``batch`` = list of ``(utt_id, spk_id, speech int16, noise int16, s0, dB, target list)``.
+    """Device-side collate for ``MixWavDataset``.  ``batch`` = list of ``(utt_id, spk_id, speech int16, noise int16, s0, dB, target list)``,
+    with an eighth element ``(h_speech | None, h_noise | None)`` when the data set has impulse responses (reverberant mixtures).
     Returns the reference's 10-tuple (mix_data_loader.py:264-302), sorted by length (descending) and zero padded, with the streams named
     in ``want`` on ``device`` ('clean_log' and 'cos' for the enhancement trainers) and None for the others.  One pinned int16 upload per
     batch, the distinct noise files of the batch once; everything is enqueued on the current stream, so it plugs into ``DevicePrefetcher`` as
     ``lambda b, d, p: collate_wav_device(b, d, cmvn, pool=p)``."""
     batch = sorted(batch, key=lambda s: s[2].shape[0], reverse=True)
-    o = wav_frontend_device([s[2] for s in batch], device, [(s[3], s[4], s[5]) for s in batch], cmvn, want, pool=pool)
+    o = wav_frontend_device([s[2] for s in batch], device, [(s[3], s[4], s[5]) for s in batch], cmvn, want, pool=pool,
+                            reverb=[s[7] for s in batch] if len(batch[0]) > 7 else None)
     lens = [wav_frames_of(s[2].shape[0]) for s in batch]
     targets = torch.LongTensor([t for s in batch for t in s[6]])
     return ([s[0] for s in batch], [s[1] for s in batch], o.get('clean'), o.get('clean_log'), o.get('mix'), o.get('mix_log'), o.get('cos'), targets,

@@ -10,7 +10,13 @@ The segment start follows the reference's rule (prepare_feats.py:45-50) on the n
 reference draws again when the noise segment has zero power; here such a mixture is the clean signal and is counted on the device
 (re2e_wav_mix_scale), which the loader logs one batch late.
 
-``__getitem__`` returns ``(item id, speaker, speech int16, noise int16, s0, dB, target list)``."""
+``__getitem__`` returns ``(item id, speaker, speech int16, noise int16, s0, dB, target list)``.
+
+Reverberant mixtures (the reference's Make_Noisy_Wave, data/audioparse.py:254-303): with ``args.rir_scp`` (one impulse response per line; a
+leading id column is accepted), an item is reverberant with probability ``args.reverb_prob`` (default 1.0), and the speech and the noise
+then get one impulse response each, drawn independently from a generator of their own seeded by (seed, epoch, index, 1) -- the mixture
+draws above are the numbers they are without it.  ``__getitem__`` then appends an eighth element ``(h_speech | None, h_noise | None)``
+(fp32 taps, ``wav_io.read_rir``); the device convolves (csrc/reverb.hip), the clean stream stays the dry signal."""
 import os
 from collections import defaultdict
 
@@ -39,6 +45,15 @@ def draw_mixture(seed, epoch, index, noise_lens, speech_len):
     return ni, start, float(rng.uniform(0.0, 20.0))
 
 
+def draw_reverb(seed, epoch, index, n_rirs, prob):
+    """``(speech RIR index | None, noise RIR index | None)`` from a generator seeded by (seed, epoch, index, 1), a stream apart from
+    ``draw_mixture``'s: with probability ``prob`` the item is reverberant, and both indices are then drawn independently."""
+    rng = np.random.default_rng([int(seed), int(epoch), int(index), 1])
+    if n_rirs < 1 or not rng.random() < prob:
+        return None, None
+    return int(rng.integers(n_rirs)), int(rng.integers(n_rirs))
+
+
 class MixWavDataset(torch.utils.data.Dataset):
     def __init__(self, args, data_dir, dict_file):
         self.args = args
@@ -57,6 +72,16 @@ class MixWavDataset(torch.utils.data.Dataset):
             raise wav_io.WavError('%s: shorter than %d samples (the STFT pads by reflection)' % (short[0], WAV_BINS))
         self.noise_len = [wav_io.wav_frames(p) for p in self.noise_paths]
         self._noise = {}
+        self.rir_paths = []
+        rir_scp = getattr(args, 'rir_scp', None)
+        if rir_scp:
+            with open(rir_scp, encoding='utf-8') as f:
+                self.rir_paths = [line.split()[-1] for line in f if line.strip()]
+            if not self.rir_paths:
+                raise ValueError('%s lists no impulse response' % rir_scp)
+        prob = getattr(args, 'reverb_prob', None)
+        self.reverb_prob = 1.0 if prob is None else float(prob)
+        self.rir_max_taps = int(getattr(args, 'rir_max_taps', None) or 16000)
         self.feat_size = WAV_BINS
         lengths = [wav_frames_of(self.samples[i % len(self.clean)]) for i in range(len(self))]
         _, edges = np.histogram(lengths, bins='auto')                              # length buckets for BucketingSampler, as MixKaldiDataset
@@ -94,11 +119,22 @@ class MixWavDataset(torch.utils.data.Dataset):
             a = self._noise[ni] = wav_io.read_wav(self.noise_paths[ni])
         return a
 
+    def draw_rirs(self, index, epoch=None):
+        """``(speech RIR index | None, noise RIR index | None)`` of item ``index`` in ``epoch`` (default: the current one)."""
+        return draw_reverb(self.seed, self.epoch if epoch is None else epoch, index, len(self.rir_paths), self.reverb_prob)
+
+    def rir(self, ri):
+        return None if ri is None else wav_io.read_rir(self.rir_paths[ri], self.rir_max_taps)
+
     def __getitem__(self, index):
         item, u = self.item_id(index)
         utt, path = self.clean[u]
         ni, start, db = self.draw(index)
-        return (item, self.utt2spk[utt], wav_io.read_wav(path), self.noise(ni), start % self.noise_len[ni], db, list(self.targets.get(utt)))
+        out = (item, self.utt2spk[utt], wav_io.read_wav(path), self.noise(ni), start % self.noise_len[ni], db, list(self.targets.get(utt)))
+        if not self.rir_paths:
+            return out
+        rs, rn = self.draw_rirs(index)
+        return out + ((self.rir(rs), self.rir(rn)),)
 
     # ---- CMVN -----------------------------------------------------------------------------------------------
     def compute_cmvn(self, device='cuda', batch=16):
@@ -109,7 +145,8 @@ class MixWavDataset(torch.utils.data.Dataset):
         s, sq, frames = np.zeros(WAV_BINS), np.zeros(WAV_BINS), 0
         for i in range(0, n, batch):
             items = [self[int(j)] for j in order[i:i + batch]]
-            log = wav_frontend_device([it[2] for it in items], device, [(it[3], it[4], it[5]) for it in items], None, ('mix_log',))['mix_log']
+            log = wav_frontend_device([it[2] for it in items], device, [(it[3], it[4], it[5]) for it in items], None, ('mix_log',),
+                                      reverb=[it[7] for it in items] if self.rir_paths else None)['mix_log']
             lens = [wav_frames_of(it[2].shape[0]) for it in items]
             ld = torch.tensor(lens, dtype=torch.int32, device=device)
             bs, bq = torch.empty(WAV_BINS, device=device), torch.empty(WAV_BINS, device=device)

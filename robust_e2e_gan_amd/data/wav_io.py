@@ -41,6 +41,41 @@ def wav_frames(path):
         w.close()
 
 
+_rirs = {}          # (path, max_taps) -> the one array object of that file
+
+
+def read_rir(path, max_taps=16000):
+    """A room impulse response as fp32 taps: a 16-bit mono 16 kHz wav (divided by 32768) or a 1-D ``.npy``.  The filter starts at its
+    largest-magnitude tap (the direct path lands on tap 0, so a reverberant signal stays aligned with its dry source), is divided by that
+    tap (unit direct path) and cut to ``max_taps``.  One array object per file, kept: items that share a file hand the SAME array to the
+    collate, which uploads it once per batch."""
+    key = (str(path), int(max_taps))
+    h = _rirs.get(key)
+    if h is not None:
+        return h
+    if int(max_taps) < 1:
+        raise WavError('%s: max_taps must be at least 1' % path)
+    if str(path).endswith('.npy'):
+        try:
+            a = np.load(path, allow_pickle=False)
+        except (OSError, ValueError) as e:
+            raise WavError('%s: not a .npy file (%s)' % (path, e))
+        if a.ndim != 1 or a.dtype.kind not in 'fiu':
+            raise WavError('%s: shape %s of %s; an impulse response is a 1-D real array' % (path, a.shape, a.dtype))
+        a = a.astype(np.float64)
+    else:
+        a = read_wav(path).astype(np.float64) / 32768.0
+    if a.size == 0 or not np.isfinite(a).all():
+        raise WavError('%s: an impulse response needs at least one tap, all finite' % path)
+    peak = int(np.argmax(np.abs(a)))
+    if a[peak] == 0.0:
+        raise WavError('%s: an impulse response of zeros' % path)
+    h = np.ascontiguousarray((a[peak:peak + int(max_taps)] / a[peak]).astype(np.float32))
+    h.setflags(write=False)
+    _rirs[key] = h
+    return h
+
+
 def write_wav(path, samples):
     """int16 samples -> a 16-bit mono 16 kHz file (tools and tests)."""
     samples = np.asarray(samples)

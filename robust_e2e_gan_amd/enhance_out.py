@@ -17,7 +17,9 @@ keyed by the mixture's id with rows cut at the utterance's frame count, as the r
     metrics.json                     per item and mean: SI-SDR and SNR of the mixture, of the enhanced signal, and the SI-SDR improvement
 
 The mixture's waveform is ``istft(mix, mix_ang)`` and the enhanced one ``istft(enhance(mix), mix_ang)``: both come out of the same kernel and are
-scored by re2e_wav_sdr_sums against the clean samples over the 256 * (L // 256) samples an inverse STFT restores (the rest is zero padding)."""
+scored by re2e_wav_sdr_sums against the clean samples over the 256 * (L // 256) samples an inverse STFT restores (the rest is zero padding).
+With ``--rir_scp`` the mixtures are reverberant (csrc/reverb.hip, the draws of (seed, epoch 0, item, 1)); the reference of the scores stays the
+dry signal."""
 import argparse
 import json
 import os
@@ -44,6 +46,9 @@ def parse_args(argv=None):
     ap.add_argument('--compress', action='store_true', help='8-bit compressed records, as copy-feats --compress=true')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--noise_repeat_num', type=int, default=1)
+    ap.add_argument('--rir_scp', default=None, help='with --wav: room impulse responses (one wav or .npy per line): reverberant mixtures')
+    ap.add_argument('--reverb_prob', type=float, default=None, help='share of reverberant items (default 1.0 with --rir_scp)')
+    ap.add_argument('--rir_max_taps', type=int, default=16000)
     ap.add_argument('--normalize_type', type=int, default=1)
     ap.add_argument('--num_utt_cmvn', type=int, default=20000)
     ap.add_argument('--feat_type', default='kaldi_magspec')
@@ -124,7 +129,7 @@ def run(a, model=None):
             if a.wav:
                 speech = [it[2] for it in items]
                 o = wav_frontend_device(speech, device, [(it[3], it[4], it[5]) for it in items], cmvn,
-                                        ('clean', 'clean_log', 'mix', 'mix_log', 'mix_ang'))
+                                        ('clean', 'clean_log', 'mix', 'mix_log', 'mix_ang'), reverb=[it[7] for it in items] if ds.rir_paths else None)
                 utts, spks, targets = [it[0] for it in items], [it[1] for it in items], [it[6] for it in items]
                 sizes = [wav_frames_of(s.shape[0]) for s in speech]
                 clean, clean_log, mix, mix_log = o['clean'], o['clean_log'], o['mix'], o['mix_log']

@@ -10,7 +10,8 @@ seeded by (seed, 0, index) -- the draws ``MixWavDataset`` makes in epoch 0 with 
 Records are 8-bit compressed as the reference's ``copy-feats --compress=true`` writes them; ``--no-compress`` writes float32 records.
 No librosa, no Kaldi binaries.
 
-    python tools/prepare_feats.py <data_dir> <feat_dir> <noise_repeat_num> [--no-compress] [--seed 0] [--batch 16]"""
+    python tools/prepare_feats.py <data_dir> <feat_dir> <noise_repeat_num> [--no-compress] [--seed 0] [--batch 16]
+                                  [--rir_scp FILE] [--reverb_prob P] [--rir_max_taps N]"""
 import argparse
 import os
 import sys
@@ -18,14 +19,22 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from robust_e2e_gan_amd.data import kaldi_io, wav_io
 from robust_e2e_gan_amd.data.mix_data_loader import wav_frames_of, wav_frontend_device
-from robust_e2e_gan_amd.data.wav_dataset import draw_mixture
+from robust_e2e_gan_amd.data.wav_dataset import draw_mixture, draw_reverb
 
 
 _Table = kaldi_io.ArkScpWriter          # one ark file and the scp lines that point into it
 
 
-def prepare(data_dir, feat_dir, noise_repeat_num=1, compress=True, seed=0, device='cuda', batch=16):
-    """Returns the draws ``[(item id, noise file index, segment start, dB)]`` the mixtures were made with."""
+def prepare(data_dir, feat_dir, noise_repeat_num=1, compress=True, seed=0, device='cuda', batch=16, rir_scp=None, reverb_prob=None,
+            rir_max_taps=16000):
+    """Returns the draws ``[(item id, noise file index, segment start, dB)]`` the mixtures were made with.  ``rir_scp``: reverberant
+    mixtures, with the impulse responses ``MixWavDataset`` draws in epoch 0 (seed, 0, index, 1); the clean tables stay the dry signal."""
+    rir_paths = []
+    if rir_scp:
+        with open(rir_scp, encoding='utf-8') as f:
+            rir_paths = [line.split()[-1] for line in f if line.strip()]
+    prob = 1.0 if reverb_prob is None else float(reverb_prob)
+    rir_of = lambda ri: None if ri is None else wav_io.read_rir(rir_paths[ri], rir_max_taps)
     with open(os.path.join(data_dir, 'clean_wav.scp'), encoding='utf-8') as f:
         clean = [line.split() for line in f if line.strip()]
     with open(os.path.join(data_dir, 'noise.scp'), encoding='utf-8') as f:
@@ -42,7 +51,11 @@ def prepare(data_dir, feat_dir, noise_repeat_num=1, compress=True, seed=0, devic
             speech = [wav_io.read_wav(p) for _, p in part]
             mine = [draw_mixture(seed, 0, k * len(clean) + i + j, noise_lens, s.shape[0]) for j, s in enumerate(speech)]
             want = ('mix', 'mix_ang') + (('clean', 'clean_ang') if k == 0 else ())
-            out = wav_frontend_device(speech, device, [(noises[ni], start % noise_lens[ni], db) for ni, start, db in mine], None, want)
+            reverb = None
+            if rir_paths:
+                reverb = [tuple(rir_of(ri) for ri in draw_reverb(seed, 0, k * len(clean) + i + j, len(rir_paths), prob)) for j in range(len(part))]
+            out = wav_frontend_device(speech, device, [(noises[ni], start % noise_lens[ni], db) for ni, start, db in mine], None, want,
+                                      reverb=reverb)
             out = {name: t.cpu().numpy() for name, t in out.items()}
             for j, ((utt, _), s, (ni, start, db)) in enumerate(zip(part, speech, mine)):
                 T = wav_frames_of(s.shape[0])
@@ -68,8 +81,12 @@ def main():
     ap.add_argument('--no-compress', action='store_true')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--rir_scp', default=None, help='room impulse responses (one wav or .npy per line): reverberant mixtures')
+    ap.add_argument('--reverb_prob', type=float, default=None, help='share of reverberant items (default 1.0 with --rir_scp)')
+    ap.add_argument('--rir_max_taps', type=int, default=16000)
     a = ap.parse_args()
-    draws = prepare(a.data_dir, a.feat_dir, a.noise_repeat_num, not a.no_compress, a.seed, batch=a.batch)
+    draws = prepare(a.data_dir, a.feat_dir, a.noise_repeat_num, not a.no_compress, a.seed, batch=a.batch, rir_scp=a.rir_scp,
+                    reverb_prob=a.reverb_prob, rir_max_taps=a.rir_max_taps)
     print('%d mixtures written under %s' % (len(draws), a.feat_dir))
 
 
