@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 336
+#define RE2E_ABI_VERSION 337
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -354,6 +354,38 @@ int re2e_wav_reverb_geometry(int which);
 int re2e_wav_stft_rev(const short* pcm, const long* speech_off, const long* mix_off, const long* speech_len, const long* noise_off,
                       const long* noise_len, const long* noise_start, const float* scale, int B, int Tmax, float* clean, float* clean_log,
                       float* mix, float* mix_log, float* cos_out, float* clean_ang, float* mix_ang, const float* cmvn, re2e_stream_t stream);
+
+/* Speed perturbation (csrc/resample.hip; no reference counterpart on the device: the reference's AudioParser promises "random tempo and gain
+ * perturbations" and never implements them; this is Kaldi's 3-way `sox speed 0.9 / 1.0 / 1.1` as a rational resampler): a batch of n_jobs
+ * independent polyphase resamplings, scipy.signal.resample_poly(x, up, down) with its defaults.  A speed factor s, given as a decimal string,
+ * is the fraction p/q in lowest terms; up = q, down = p (0.9: 10/9, 1.1: 10/11).  For an L-sample source x the resampled signal has
+ * L' = ceil(L up / down) samples:
+ *   half = 10 max(up, down),  fc = 1 / max(up, down)
+ *   g[i] = fc sinc(fc (i - half)) kaiser_{2 half + 1, beta = 5}(i),  0 <= i <= 2 half   (sinc(t) = sin(pi t) / (pi t), symmetric Kaiser window)
+ *   h[i] = up g[i] / sum g
+ *   y[m] = sum_j x[j] h[half + m down - j up],  over 0 <= j < L with 0 <= half + m down - j up <= 2 half   (x is zero outside 0 .. L - 1)
+ * h is built inside the library on the host, in double (I0 by its power series), rounded ONCE to fp32 and kept per (up, down);
+ * re2e_wav_resample_taps writes that fp32 table (2 half + 1 floats) to h_host and half to *half (either may be NULL, not both; no device).
+ * pcm: the device blob of 16-bit samples (pcm_samples of them).  src_off / src_len / up / down / first / count / dst_off: HOST arrays of
+ * n_jobs entries, checked here and passed as kernel arguments (jobs go 32 to a launch; jobs of different ratios may share one), so nothing
+ * has to stay alive after the call.  Job q has the source x[j] = pcm[src_off[q] + j], 0 <= j < L = src_len[q], and writes y[first[q] + i],
+ * 0 <= i < count[q], to wav_f32[dst_off[q] + i] (fp32) and / or pcm_out[dst_off[q] + i] (int16: rintf of the value wav_f32 holds, saturated
+ * to -32768 .. 32767; *clip_count, device int, optional, is incremented by the number of saturated samples).  Both outputs hold out_samples
+ * samples; nothing outside the n_jobs destination ranges is written.  Every output is accumulated in fp32 in ascending tap order (the
+ * clip counter is the only atomic): two runs agree bit for bit.  pcm_out may be pcm itself (the perturbed speech lands behind the uploaded
+ * samples of one allocation).  A speed of exactly 1 is not a job: the samples pass through untouched, and up == down is refused.
+ * Refused with a message, before anything is launched: up < 1 or down < 1, up == down, gcd(up, down) != 1,
+ * max(up, down) > RE2E_WAV_RESAMPLE_MAX_RATE, first < 0, count < 1, first + count > L', a source range outside 0 .. pcm_samples, a
+ * destination range outside 0 .. out_samples, both outputs NULL, n_jobs < 1, and with pcm_out == pcm a destination range that overlaps any
+ * source range [src_off, src_off + src_len) of the same call.  The first job of a ratio in a process allocates its table on the device
+ * and copies it there with a blocking copy (some 5 KB at most, kept for the life of the process).
+ * re2e_wav_resample_geometry(which): 0 the outputs per workgroup, 1 the jobs per launch, 2 RE2E_WAV_RESAMPLE_MAX_RATE; -1 otherwise. */
+#define RE2E_WAV_RESAMPLE_MAX_RATE 64        /* every speed on a 1/64 grid, 0.95 and 1.05 among them; its table is 1281 floats */
+int re2e_wav_resample(const short* pcm, long pcm_samples, const long* src_off, const long* src_len, const int* up, const int* down,
+                      const long* first, const long* count, const long* dst_off, int n_jobs, long out_samples, float* wav_f32,
+                      short* pcm_out, int* clip_count, re2e_stream_t stream);
+int re2e_wav_resample_geometry(int which);
+int re2e_wav_resample_taps(int up, int down, float* h_host, int* half);
 
 /* ---- K2 fused fbank (model/feat_model.py:118-135): y = log(max((x^2) W, 1e-7)); optional
  * second output y_norm = (y + cmvn[0]) * cmvn[1]; optional third output pw_out = (x^2) W itself, which re2e_fbank_bwd takes

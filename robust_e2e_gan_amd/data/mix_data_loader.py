@@ -9,9 +9,12 @@ clean_log_inputs are never read by joint_train.py).
 ``collate_wav_device`` / ``wav_features_device`` start from 16-bit PCM instead: the samples go over PCIe as ONE pinned int16 blob and
 re2e_wav_mix_scale / re2e_wav_stft (csrc/stft.hip) mix the noise in at the drawn SNR and produce the padded spectra on the device.
 ``wav_istft_device`` goes the other way (re2e_wav_istft: enhanced magnitudes and a phase back to samples) and ``wav_sdr_device`` scores the
-result against the clean samples (re2e_wav_sdr_sums: SNR and SI-SDR)."""
+result against the clean samples (re2e_wav_sdr_sums: SNR and SI-SDR).  With speeds (``resample_jobs``, ``wav_frontend_device(speed=...)``) the
+speech is resampled on the device first (re2e_wav_resample, csrc/resample.hip): speed perturbation."""
 import ctypes
 import logging
+import re
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -181,6 +184,69 @@ def _reverb_clip_counter(device):
     return st
 
 
+_resample_clip = {}       # device -> the same four for the samples re2e_wav_resample saturated
+
+
+def _resample_clip_counter(device):
+    """The device counter re2e_wav_resample increments for every resampled sample it saturated to int16; read one batch late, as the
+    zero-power counter."""
+    key = str(device)
+    st = _resample_clip.get(key)
+    if st is None:
+        st = _resample_clip[key] = [torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32).pin_memory(), None, 0]
+    counter, host, ev, seen = st
+    if ev is not None and ev.query():
+        n = int(host[0])
+        if n > seen:
+            logging.getLogger(__name__).warning('%d speed-perturbed sample(s) clipped at the 16-bit range so far', n)
+            st[3] = n
+        st[2] = None
+    return st
+
+
+WAV_RESAMPLE_MAX_RATE = 64        # include/re2e.h RE2E_WAV_RESAMPLE_MAX_RATE
+
+
+def speed_ratio(speed):
+    """A speed factor given as a decimal string ('0.9') -> ``(up, down)`` of re2e_wav_resample, or None for a speed of exactly 1: the
+    factor is p/q in lowest terms, up = q, down = p (0.9: 10/9, 1.1: 10/11).  Refuses what is not a positive decimal and a ratio beyond
+    RE2E_WAV_RESAMPLE_MAX_RATE."""
+    text = str(speed).strip()
+    if not re.fullmatch(r'\d+(\.\d*)?|\.\d+', text) or Fraction(text) <= 0:
+        raise ValueError('a speed is a positive decimal such as 0.9, got %r' % (speed,))
+    f = Fraction(text)
+    up, down = f.denominator, f.numerator
+    if max(up, down) > WAV_RESAMPLE_MAX_RATE:
+        raise ValueError('speed %s is the ratio %d/%d: beyond RE2E_WAV_RESAMPLE_MAX_RATE = %d' % (text, up, down, WAV_RESAMPLE_MAX_RATE))
+    return None if up == down else (up, down)
+
+
+def resampled_len(n_samples, ratio):
+    """L' = ceil(L up / down) of an L-sample signal at ``ratio`` = None | (up, down)."""
+    n = int(n_samples)
+    if ratio is None or ratio[0] == ratio[1]:
+        return n
+    return -(-n * int(ratio[0]) // int(ratio[1]))
+
+
+def resample_jobs(speech, speeds, pos):
+    """The resamplings of one speed-perturbed batch, as re2e_wav_resample takes them (pure host arithmetic, no device).  ``speech``: one
+    ``(offset, L)`` per utterance, ``speeds``: one ``None | (up, down)``, ``pos``: the first free sample behind the uploaded ones.  Returns
+    ``(jobs, speech, end)``: ``jobs`` rows of ``(src_off, src_len, up, down, first, count, dst_off)``, the new ``(offset, L')`` of every
+    utterance's speech (its own without a speed, and at a speed of exactly 1, which is not a job) and the first free sample behind the
+    destinations."""
+    jobs, out = [], []
+    for (soff, L), ratio in zip(speech, speeds):
+        if ratio is None or ratio[0] == ratio[1]:
+            out.append((soff, L))
+            continue
+        n = resampled_len(L, ratio)
+        jobs.append((soff, L, int(ratio[0]), int(ratio[1]), 0, n, pos))
+        out.append((pos, n))
+        pos += n
+    return jobs, out, pos
+
+
 def reverb_jobs(speech, noise, rirs, pos):
     """The convolutions of one reverberant batch, as re2e_wav_reverb takes them (pure host arithmetic, no device).  ``speech``: one
     ``(offset, L)`` per utterance, ``noise``: one ``(offset, N, s0)``, ``rirs``: one ``((offset, taps) | None, (offset, taps) | None)`` for
@@ -214,7 +280,7 @@ def reverb_jobs(speech, noise, rirs, pos):
     return jobs, mix_off, noise_out, pos
 
 
-def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'mix', 'mix_log'), Tmax=None, pool=None, reverb=None):
+def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'mix', 'mix_log'), Tmax=None, pool=None, reverb=None, speed=None):
     """16-bit PCM -> spectra on ``device``, all work enqueued on the CURRENT stream.  ``speech``: int16 arrays, one per utterance, in the
     order of the batch rows; ``noise``: None (clean stream only) or one ``(noise int16 array, s0, dB)`` per utterance -- the mixture is
     ``s[i] + g * n[(s0 + i) % len(n)]`` with ``g = sqrt(sum s^2 / (P * 10^(dB/10)))``, P the power of that noise segment.  Arrays that are the
@@ -224,14 +290,17 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
     is then ``conv(h_s, s)[:L][i] + g * r[(s0 + i) % len(n)]``, ``r = conv(h_n, n)[:len(n)]``, g from the powers AFTER reverberation, while
     'clean' stays the dry ``s``.  The distinct RIR arrays go up once in a pinned fp32 blob; the reverberant signals are rounded to int16
     behind the uploaded samples of the same allocation (re2e_wav_reverb), the spectra come from re2e_wav_stft_rev.  Reverberant samples
-    that saturate are counted on the device and logged one batch late."""
+    that saturate are counted on the device and logged one batch late.
+    ``speed``: None or one ``None | (up, down)`` per utterance (``speed_ratio``): those utterances are resampled first (re2e_wav_resample,
+    int16, behind the uploaded samples), and from then on the resampled signal IS the speech -- the clean stream, the frame counts and Tmax
+    (from L' = ceil(L up / down)), the source of the speech RIR, the L the noise segment and the SNR run over.  The order is resample,
+    reverberate, mix, as Kaldi's recipes have it; the noise is never perturbed.  Saturated samples are counted on the device and logged one
+    batch late.  A batch in which no utterance has a speed launches what it launches without the argument."""
     bad = [w for w in want if w not in WAV_OUTPUTS]
     if bad:
         raise ValueError('unknown front-end output %r (one of %s)' % (bad[0], ', '.join(WAV_OUTPUTS)))
     B = len(speech)
     lens = [int(s.shape[0]) for s in speech]
-    T = max(wav_frames_of(n) for n in lens)
-    Tmax = T if Tmax is None else int(Tmax)
     arrays, where, pos = [], {}, 0
 
     def place(a):
@@ -251,6 +320,15 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
         nlen = [int(n[0].shape[0]) for n in noise]
         s0 = [int(n[1]) % max(ln, 1) for n, ln in zip(noise, nlen)]
         db = (ctypes.c_float * B)(*[float(n[2]) for n in noise])
+    uploaded = total = pos
+    rs_jobs = []
+    if speed is not None:
+        if len(speed) != B:
+            raise ValueError('speed: one None | (up, down) per utterance, got %d for %d utterances' % (len(speed), B))
+        rs_jobs, moved, total = resample_jobs(list(zip(soff, lens)), speed, pos)
+        soff, lens = [m[0] for m in moved], [m[1] for m in moved]
+    T = max(wav_frames_of(n) for n in lens)
+    Tmax = T if Tmax is None else int(Tmax)
     if reverb is not None and not any(h is not None for pair in reverb for h in pair):
         reverb = None                                # a batch without a reverberant item launches what it launches without RIRs
     if reverb is not None:
@@ -270,22 +348,31 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
                 hpos += h.shape[0]
             return hwhere[id(h)], int(h.shape[0])
         rirs = [(place_rir(hs), place_rir(hn)) for hs, hn in reverb]
-        jobs, moff, nz, total = reverb_jobs(list(zip(soff, lens)), list(zip(noff, nlen, s0)), rirs, pos)
+        jobs, moff, nz, total = reverb_jobs(list(zip(soff, lens)), list(zip(noff, nlen, s0)), rirs, total)
         noff, nlen, s0 = [z[0] for z in nz], [z[1] for z in nz], [z[2] for z in nz]
         hhost = pool.get('rir', 4 * hpos).view(torch.float32) if pool is not None else torch.empty(hpos, dtype=torch.float32)
         if pool is None and on_gpu:
             hhost = hhost.pin_memory()
         np.concatenate(taps, out=hhost.numpy())
         hblob = hhost.to(device, non_blocking=True)
-    host = pool.get('wav', 2 * pos).view(torch.int16) if pool is not None else torch.empty(pos, dtype=torch.int16)
+    host = pool.get('wav', 2 * uploaded).view(torch.int16) if pool is not None else torch.empty(uploaded, dtype=torch.int16)
     if pool is None and on_gpu:
         host = host.pin_memory()
     np.concatenate(arrays, out=host.numpy())
-    if reverb is None:
+    if total == uploaded:
         blob = host.to(device, non_blocking=True)
-    else:                                            # room behind the uploaded samples for the reverberant signals
+    else:                                            # room behind the uploaded samples for the resampled and the reverberant signals
         blob = torch.empty(total, dtype=torch.int16, device=device)
-        blob[:pos].copy_(host, non_blocking=True)
+        blob[:uploaded].copy_(host, non_blocking=True)
+    if rs_jobs:
+        rclip = _resample_clip_counter(device)
+        rcols = [(ctypes.c_int if c in (2, 3) else ctypes.c_long) * len(rs_jobs) for c in range(7)]
+        rcols = [t(*[int(j[c]) for j in rs_jobs]) for c, t in enumerate(rcols)]
+        call('re2e_wav_resample', blob.data_ptr(), total, *rcols, len(rs_jobs), total, None, blob.data_ptr(), rclip[0].data_ptr())
+        if on_gpu and rclip[2] is None:
+            rclip[1].copy_(rclip[0], non_blocking=True)
+            rclip[2] = torch.cuda.Event()
+            rclip[2].record(torch.cuda.current_stream())
     out = {k: torch.empty(B, Tmax, WAV_BINS, dtype=torch.float32, device=device) for k in want}
     cm = cmvn.to(device).float().contiguous() if cmvn is not None else None
     p = lambda k: out[k].data_ptr() if k in out else None
@@ -326,15 +413,19 @@ def wav_frontend_device(speech, device, noise=None, cmvn=None, want=('clean', 'm
 
 def collate_wav_device(batch, device, cmvn=None, want=('clean', 'mix', 'mix_log'), pool=None):
     """Device-side collate for ``MixWavDataset``.  ``batch`` = list of ``(utt_id, spk_id, speech int16, noise int16, s0, dB, target list)``,
-    with an eighth element ``(h_speech | None, h_noise | None)`` when the data set has impulse responses (reverberant mixtures).
+    with an eighth element ``(h_speech | None, h_noise | None)`` when the data set has impulse responses (reverberant mixtures) and a
+    ninth ``None | (up, down)`` when it perturbs the speed (the eighth is then always there): the batch is sorted by the PERTURBED length
+    L' and the frame counts are those of L'.
     Returns the reference's 10-tuple (mix_data_loader.py:264-302), sorted by length (descending) and zero padded, with the streams named
     in ``want`` on ``device`` ('clean_log' and 'cos' for the enhancement trainers) and None for the others.  One pinned int16 upload per
     batch, the distinct noise files of the batch once; everything is enqueued on the current stream, so it plugs into ``DevicePrefetcher`` as
     ``lambda b, d, p: collate_wav_device(b, d, cmvn, pool=p)``."""
-    batch = sorted(batch, key=lambda s: s[2].shape[0], reverse=True)
+    length = lambda s: resampled_len(s[2].shape[0], s[8] if len(s) > 8 else None)
+    batch = sorted(batch, key=length, reverse=True)
     o = wav_frontend_device([s[2] for s in batch], device, [(s[3], s[4], s[5]) for s in batch], cmvn, want, pool=pool,
-                            reverb=[s[7] for s in batch] if len(batch[0]) > 7 else None)
-    lens = [wav_frames_of(s[2].shape[0]) for s in batch]
+                            reverb=[s[7] for s in batch] if len(batch[0]) > 7 else None,
+                            speed=[s[8] for s in batch] if len(batch[0]) > 8 else None)
+    lens = [wav_frames_of(length(s)) for s in batch]
     targets = torch.LongTensor([t for s in batch for t in s[6]])
     return ([s[0] for s in batch], [s[1] for s in batch], o.get('clean'), o.get('clean_log'), o.get('mix'), o.get('mix_log'), o.get('cos'), targets,
             torch.IntTensor(lens), torch.IntTensor([len(s[6]) for s in batch]))

@@ -16,7 +16,16 @@ Reverberant mixtures (the reference's Make_Noisy_Wave, data/audioparse.py:254-30
 leading id column is accepted), an item is reverberant with probability ``args.reverb_prob`` (default 1.0), and the speech and the noise
 then get one impulse response each, drawn independently from a generator of their own seeded by (seed, epoch, index, 1) -- the mixture
 draws above are the numbers they are without it.  ``__getitem__`` then appends an eighth element ``(h_speech | None, h_noise | None)``
-(fp32 taps, ``wav_io.read_rir``); the device convolves (csrc/reverb.hip), the clean stream stays the dry signal."""
+(fp32 taps, ``wav_io.read_rir``); the device convolves (csrc/reverb.hip), the clean stream stays the dry signal.
+
+Speed perturbation (Kaldi's 3-way ``sox speed 0.9 / 1.0 / 1.1``; no reference counterpart): with ``args.speed_perturb``, a comma list of
+decimal strings such as ``'0.9,1.0,1.1'``, every item draws one of them uniformly from a generator of its own seeded by
+(seed, epoch, index, 2) -- the mixture and RIR draws keep their streams -- and the device resamples the speech by the rational ratio
+(csrc/resample.hip, ``mix_data_loader.speed_ratio``) BEFORE it is reverberated and mixed; the perturbed dry signal is the enhancer's target,
+the noise is never perturbed.  The mixture is drawn for the perturbed length L' = ceil(L up / down): the reference's segment-start rule
+applies to the speech that is actually mixed.  ``__getitem__`` then appends a ninth element ``None | (up, down)`` behind the RIR pair, which
+is ``(None, None)`` when the data set has no impulse responses; the speech array itself stays the file's samples.  The length buckets of
+``BucketingSampler`` stay on the NOMINAL lengths: a speed changes a length by a tenth, a bucket spans more, and the draw changes every epoch."""
 import os
 from collections import defaultdict
 
@@ -26,7 +35,7 @@ import torch
 from ..lib import call
 from . import wav_io
 from .kaldi_dataset import _read_table, read_dictionary, read_targets
-from .mix_data_loader import WAV_BINS, wav_frames_of, wav_frontend_device
+from .mix_data_loader import WAV_BINS, resampled_len, speed_ratio, wav_frames_of, wav_frontend_device
 
 
 def segment_start_range(noise_len, speech_len):
@@ -52,6 +61,13 @@ def draw_reverb(seed, epoch, index, n_rirs, prob):
     if n_rirs < 1 or not rng.random() < prob:
         return None, None
     return int(rng.integers(n_rirs)), int(rng.integers(n_rirs))
+
+
+def draw_speed(seed, epoch, index, n):
+    """Index of one of ``n`` speeds, uniform, from a generator seeded by (seed, epoch, index, 2), a stream apart from ``draw_mixture``'s and
+    ``draw_reverb``'s."""
+    rng = np.random.default_rng([int(seed), int(epoch), int(index), 2])
+    return int(rng.integers(n))
 
 
 class MixWavDataset(torch.utils.data.Dataset):
@@ -82,6 +98,15 @@ class MixWavDataset(torch.utils.data.Dataset):
         prob = getattr(args, 'reverb_prob', None)
         self.reverb_prob = 1.0 if prob is None else float(prob)
         self.rir_max_taps = int(getattr(args, 'rir_max_taps', None) or 16000)
+        self.speeds = []                                                           # None | (up, down) per configured speed
+        speed_perturb = getattr(args, 'speed_perturb', None)
+        if speed_perturb:
+            self.speeds = [speed_ratio(t) for t in str(speed_perturb).split(',') if t.strip()]
+            if not self.speeds:
+                raise ValueError('speed_perturb %r lists no speed' % (speed_perturb,))
+            short = [u for (u, _), n in zip(self.clean, self.samples) if min(resampled_len(n, r) for r in self.speeds) < WAV_BINS]
+            if short:
+                raise wav_io.WavError('%s: shorter than %d samples at its fastest speed (the STFT pads by reflection)' % (short[0], WAV_BINS))
         self.feat_size = WAV_BINS
         lengths = [wav_frames_of(self.samples[i % len(self.clean)]) for i in range(len(self))]
         _, edges = np.histogram(lengths, bins='auto')                              # length buckets for BucketingSampler, as MixKaldiDataset
@@ -110,7 +135,14 @@ class MixWavDataset(torch.utils.data.Dataset):
 
     def draw(self, index, epoch=None):
         """``(noise file index, segment start in the tiled noise, dB)`` of item ``index`` in ``epoch`` (default: the current one)."""
-        return draw_mixture(self.seed, self.epoch if epoch is None else epoch, index, self.noise_len, self.samples[self.item_id(index)[1]])
+        return draw_mixture(self.seed, self.epoch if epoch is None else epoch, index, self.noise_len,
+                            resampled_len(self.samples[self.item_id(index)[1]], self.draw_speed(index, epoch)))
+
+    def draw_speed(self, index, epoch=None):
+        """``None | (up, down)`` of item ``index`` in ``epoch`` (default: the current one); None without ``speed_perturb`` and at speed 1."""
+        if not self.speeds:
+            return None
+        return self.speeds[draw_speed(self.seed, self.epoch if epoch is None else epoch, index, len(self.speeds))]
 
     def noise(self, ni):
         """Noise file ``ni``, read once and kept: items that share it hand the SAME array to the collate, which uploads it once per batch."""
@@ -131,10 +163,12 @@ class MixWavDataset(torch.utils.data.Dataset):
         utt, path = self.clean[u]
         ni, start, db = self.draw(index)
         out = (item, self.utt2spk[utt], wav_io.read_wav(path), self.noise(ni), start % self.noise_len[ni], db, list(self.targets.get(utt)))
-        if not self.rir_paths:
+        if self.rir_paths:
+            rs, rn = self.draw_rirs(index)
+            out += ((self.rir(rs), self.rir(rn)),)
+        if not self.speeds:
             return out
-        rs, rn = self.draw_rirs(index)
-        return out + ((self.rir(rs), self.rir(rn)),)
+        return (out if self.rir_paths else out + ((None, None),)) + (self.draw_speed(index),)
 
     # ---- CMVN -----------------------------------------------------------------------------------------------
     def compute_cmvn(self, device='cuda', batch=16):
@@ -146,8 +180,9 @@ class MixWavDataset(torch.utils.data.Dataset):
         for i in range(0, n, batch):
             items = [self[int(j)] for j in order[i:i + batch]]
             log = wav_frontend_device([it[2] for it in items], device, [(it[3], it[4], it[5]) for it in items], None, ('mix_log',),
-                                      reverb=[it[7] for it in items] if self.rir_paths else None)['mix_log']
-            lens = [wav_frames_of(it[2].shape[0]) for it in items]
+                                      reverb=[it[7] for it in items] if self.rir_paths else None,
+                                      speed=[it[8] for it in items] if self.speeds else None)['mix_log']
+            lens = [wav_frames_of(resampled_len(it[2].shape[0], it[8] if self.speeds else None)) for it in items]
             ld = torch.tensor(lens, dtype=torch.int32, device=device)
             bs, bq = torch.empty(WAV_BINS, device=device), torch.empty(WAV_BINS, device=device)
             call('re2e_cmvn_stats', log.data_ptr(), ld.data_ptr(), len(items), log.shape[1], WAV_BINS, bs.data_ptr(), bq.data_ptr())

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 336    # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 337    # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -81,6 +81,9 @@ SIGNATURES = {
     're2e_wav_sdr_sums': (I, [P, P, P, P, P, I, P, P]),
     're2e_wav_reverb': (I, [P, L, P, L, P, P, P, P, P, P, P, I, L, P, P, P, P]),
     're2e_wav_reverb_geometry': (I, [I]),
+    're2e_wav_resample': (I, [P, L, P, P, P, P, P, P, P, I, L, P, P, P, P]),
+    're2e_wav_resample_geometry': (I, [I]),
+    're2e_wav_resample_taps': (I, [I, I, P, P]),
     're2e_wav_stft_rev': (I, [P, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P]),
     're2e_fbank_fwd': (I, [P, L, I, I, P, P, P, I, P, P, P, P, P]),
     're2e_fbank_bwd': (I, [P, L, I, I, P, P, P, I, P, P, P, P, P, P]),
@@ -285,6 +288,21 @@ def set_stream_role(torch_stream, filler=True):
 
 def query(name, *args):
     return getattr(load(), name)(*args)
+
+
+def resample_taps(up, down):
+    """``(h, half)``: the fp32 table re2e_wav_resample uses for the ratio up/down (numpy, 2 half + 1 floats), re2e_wav_resample_taps."""
+    import numpy as np
+    lib = load()
+    half = c_int(0)
+    rc = lib.re2e_wav_resample_taps(int(up), int(down), None, ctypes.addressof(half))
+    if rc != 0:
+        raise Re2eError('re2e_wav_resample_taps failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    h = np.empty(2 * half.value + 1, np.float32)
+    rc = lib.re2e_wav_resample_taps(int(up), int(down), h.ctypes.data, None)
+    if rc != 0:
+        raise Re2eError('re2e_wav_resample_taps failed (%d): %s' % (rc, lib.re2e_last_error().decode()))
+    return h, half.value
 
 
 def lstm_plan(T, B, H, backward=False, cus=0):
