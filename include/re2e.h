@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 337
+#define RE2E_ABI_VERSION 338
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -386,6 +386,37 @@ int re2e_wav_resample(const short* pcm, long pcm_samples, const long* src_off, c
                       short* pcm_out, int* clip_count, re2e_stream_t stream);
 int re2e_wav_resample_geometry(int which);
 int re2e_wav_resample_taps(int up, int down, float* h_host, int* half);
+
+/* SpecAugment on the normalised filterbank features (csrc/specaug.hip; Park et al. 2019 in ESPnet's form: `time_warp`, `freq_mask`,
+ * `time_mask`; no reference counterpart): y = masks(warp(x)), and dx = J^T dy for the same plan.
+ * x, y: (R, Tp, F) fp32, rows zero-padded behind their valid frames.  plan: DEVICE int32, R rows of P = 3 + 2 nF + 2 nT entries
+ *   [T_r, c, w, f0_1, f_1, .., f0_nF, f_nF, t0_1, t_1, .., t0_nT, t_nT]
+ * Time warp, per row over its own T_r valid frames: c == 0 is no warp.  Otherwise, for a warp window W, W <= c < T_r - W and
+ * c - W + 1 <= w <= c + W: the frames [0, c) are resized along time to w frames and the frames [c, T_r) to T_r - w frames, each segment as
+ * torch.nn.functional.interpolate(mode='bicubic', align_corners=False) resizes it (the feature axis keeps its size).  For a segment of
+ * n_in -> n_out frames and its output frame t:
+ *   N = (2 t + 1) n_in - n_out,  D = 2 n_out,  i0 = floor(N / D),  tau = (N - i0 D) / D      (integers; ONE fp32 division)
+ *   y[t] = sum_{k = 0..3} wk(tau) x[clamp(i0 - 1 + k, 0, n_in - 1)]
+ *   w0 = ((A (tau + 1) - 5 A)(tau + 1) + 8 A)(tau + 1) - 4 A,  w1 = ((A + 2) tau - (A + 3)) tau^2 + 1,  w2 = w1(1 - tau),  w3 = w0(1 - tau),
+ *   A = -0.75 (the cubic convolution).  A segment with n_in == n_out, and a row with c == 0, is copied bit for bit.
+ * Masks, after the warp: the cells with f0_k <= f < f0_k + f_k and t < T_r, and the cells with t0_k <= t < t0_k + t_k, become 0.0 (the
+ * feature mean after CMVN).  Widths of zero and overlapping masks are legal.  Frames t >= T_r pass through unchanged, forward and backward.
+ * Backward: a gather -- source frame s sums wk dy[t] over the contiguous run of output frames t whose clamped taps hit it, found by inverting
+ * i0(t) in integers, in ascending (t, k); the first and last frame of a segment collect the clamped taps; masked cells contribute nothing.
+ * No atomics: two runs agree bit for bit.
+ * The plan arrives from the host without a round trip, so the kernels clamp every value where they read it: T_r into 0 .. Tp; c <= 0 or
+ * T_r < 2 is no warp, otherwise c into 1 .. T_r - 1 and w into 1 .. T_r - 1; f0 into 0 .. F and f into 0 .. F - f0; t0 into 0 .. T_r and t
+ * into 0 .. T_r - t0.  No plan reads or writes outside row r.  (A plan outside the contract can make one source frame of the backward sum
+ * many output frames: correct, and slower.)
+ * One launch each, whatever R, nF and nT.  Rows go as float4 where F % 4 == 0 and both tensors are 16-byte aligned, scalar otherwise.
+ * Refused with a message, before anything is launched and with nothing written: x == y (dy == dx), a null operand, R < 1, Tp < 1, F < 1,
+ * nF or nT outside 0 .. RE2E_SPECAUG_MAX_MASKS.
+ * re2e_spec_augment_geometry(which): 0 the output frames per forward workgroup, 1 the source frames per backward workgroup,
+ * 2 RE2E_SPECAUG_MAX_MASKS, 3 the output frames a backward workgroup stages; -1 otherwise. */
+#define RE2E_SPECAUG_MAX_MASKS 8
+int re2e_spec_augment_fwd(const float* x, const int* plan, int R, int Tp, int F, int nF, int nT, float* y, re2e_stream_t stream);
+int re2e_spec_augment_bwd(const float* dy, const int* plan, int R, int Tp, int F, int nF, int nT, float* dx, re2e_stream_t stream);
+int re2e_spec_augment_geometry(int which);
 
 /* ---- K2 fused fbank (model/feat_model.py:118-135): y = log(max((x^2) W, 1e-7)); optional
  * second output y_norm = (y + cmvn[0]) * cmvn[1]; optional third output pw_out = (x^2) W itself, which re2e_fbank_bwd takes

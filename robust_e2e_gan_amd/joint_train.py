@@ -17,8 +17,9 @@ import torch
 
 from . import lib, ops
 from . import dist as rdist
+from .data import spec_augment
 from .dist import GradSync
-from .model.e2e_common import set_requires_grad
+from .model.e2e_common import lens_list, set_requires_grad
 from .model.gan_model import CORAL, GANLoss, replay_running_stats
 from .optim import FlatOptimizer
 
@@ -103,6 +104,11 @@ class JointTrainer(object):
         # are multiplied by (two of them, alternating: step k reads one while its gate writes the other for step k + 1), the step's delta
         self._gate = None
         self._step_no = 0
+        # SpecAugment (opt.spec_augment = 'W,F,nF,T,nT', data/spec_augment.py; ops.spec_augment): the features both ASR branches enter the
+        # encoder with are augmented by ONE plan per training step, drawn from (opt.seed, this counter, rank).  The counter is part of
+        # ``state()`` and ``_uncount_step`` takes a step back, so a step that is run again sees the plan it saw.  Validation never augments.
+        self.spec_augment = spec_augment.parse(getattr(opt, 'spec_augment', None))
+        self.aug_step = 0
         # Dropout masks (ops.dropout: counter-based Philox, nothing stored): one stream per process, keyed by (opt.seed, rank) so that
         # data-parallel replicas draw DIFFERENT masks, as upstream's per-process RNG would; the (seed, next mask index) pair is part
         # of ``state()`` and ``restore_dropout`` puts it back, so a resumed run continues the mask sequence instead of replaying
@@ -173,12 +179,13 @@ class JointTrainer(object):
         self._mark('start')
         clean_inputs, mix_inputs, mix_log_inputs, targets, input_sizes, target_sizes = data[2], data[4], data[5], data[7], data[8], data[9]
         hold = self._hold_factor()
-        fwd = self._enhancer_forward(clean_inputs, mix_inputs, mix_log_inputs, input_sizes, enhance_cmvn, hold)
+        aug = self._draw_aug(input_sizes)
+        fwd = self._enhancer_forward(clean_inputs, mix_inputs, mix_log_inputs, input_sizes, enhance_cmvn, hold, aug)
         enhance_loss = opt.enhance_loss_lambda * ops.mean_loss(fwd.enhance_feat, fwd.clean_feat, 0.0, _LOSS_KIND[opt.enhance_loss_type])
         d_fwd = self._gstep_d_forward(fwd.enhance_feat, enhance_cmvn) if self.isGAN else None
         self._mark('fbank + G-step D fwd enqueued (side)')
         loss, out, asr_meters = self._asr_forward_and_loss(fwd, d_fwd, enhance_loss, targets, input_sizes, target_sizes, sche_samp_rate,
-                                                           enhance_cmvn, hold)
+                                                           enhance_cmvn, hold, aug)
         self.enhance_optimizer.zero_grad()
         self.asr_optimizer.zero_grad()
         sync = GradSync()
@@ -201,7 +208,16 @@ class JointTrainer(object):
         self._mark('optimizers')
         return out
 
-    def _enhancer_forward(self, clean_inputs, mix_inputs, mix_log_inputs, input_sizes, enhance_cmvn, hold):
+    def _draw_aug(self, input_sizes):
+        """The SpecAugment plan of the step about to run (None without ``opt.spec_augment``), and count the step."""
+        if self.spec_augment is None:
+            return None
+        aug = spec_augment.Plan.draw(int(getattr(self.opt, 'seed', 1234)), self.aug_step, rdist.rank(), lens_list(input_sizes),
+                                     int(self.opt.fbank_dim), self.spec_augment)
+        self.aug_step += 1
+        return aug
+
+    def _enhancer_forward(self, clean_inputs, mix_inputs, mix_log_inputs, input_sizes, enhance_cmvn, hold, aug=None):
         """Enhancer -> fbank on the current (main) stream.  With overlap and a VGG encoder the clean branch and, GAN, the early real half of the
         D-step go on the side stream, under the enhancer's recurrent chain."""
         if not (self.overlap_dstep and getattr(self.asr_model, 'etype', '').startswith('vgg')):
@@ -219,7 +235,8 @@ class JointTrainer(object):
                 clean_feat = self.feat_model(clean_inputs)
             ev_cf = torch.cuda.Event()
             ev_cf.record()
-            clean_branch = self.asr_model.encode_clean(clean_feat, enhance_cmvn, input_sizes)
+            clean_branch = (self.asr_model.encode_clean(clean_feat, enhance_cmvn, input_sizes) if aug is None else
+                            self.asr_model.encode_clean(clean_feat, enhance_cmvn, input_sizes, aug=aug))
         self._mark('clean branch enqueued (side)')
         enhance_out = self.enhance_model(mix_inputs, mix_log_inputs, input_sizes)
         self._mark('enhancer fwd')
@@ -262,12 +279,13 @@ class JointTrainer(object):
             d_fake, gan_loss = forward()
         return _DFake(d_fake, gan_loss, stats, list(self.gan_model._bn_layers_last))
 
-    def _asr_forward_and_loss(self, fwd, d_fwd, enhance_loss, targets, input_sizes, target_sizes, sche_samp_rate, enhance_cmvn, hold):
+    def _asr_forward_and_loss(self, fwd, d_fwd, enhance_loss, targets, input_sizes, target_sizes, sche_samp_rate, enhance_cmvn, hold, aug=None):
         """ASR forward, then the step's loss.  Returns the loss to differentiate, the meters known so far and the ASR meters that close the dict."""
         opt = self.opt
         loss_ctc, loss_att, acc, _, _ = self.asr_model(
             fwd.clean_feat, fwd.enhance_feat, targets, input_sizes, target_sizes, sche_samp_rate, enhance_cmvn, clean_branch=fwd.clean_branch,
-            context_loss=lambda cc, mc: opt.coral_loss_lambda * CORAL(cc, mc))      # on the filler stream, beside the decoder
+            context_loss=lambda cc, mc: opt.coral_loss_lambda * CORAL(cc, mc),      # on the filler stream, beside the decoder
+            **({} if aug is None else {'aug': aug}))
         self._mark('ASR fwd')
         coral_loss = self.asr_model.last_context_loss
         asr_loss = opt.mtlalpha * loss_ctc.view(()) + (1 - opt.mtlalpha) * loss_att
@@ -615,13 +633,13 @@ class JointTrainer(object):
             if train_sampler is not None and epoch > opt.shuffle_epoch:
                 train_sampler.shuffle(epoch)
             for data in loader():
-                entry = (data, sche_samp_rate, enhance_cmvn, self._bn_snapshot(), self._rng_snapshot())
+                entry = (data, sche_samp_rate, enhance_cmvn, self._bn_snapshot(), self._rng_snapshot(), self.aug_step)
                 errors = self.step(data, sche_samp_rate, enhance_cmvn)
                 if flush():                               # previous step's meters, now that this step is queued
                     # the previous step was repeated: THIS one ran behind the give-up and was held (it applied nothing; what it did to D's
                     # running statistics was put back with the previous step's snapshot): run it again, on the repaired state
                     self._uncount_step()
-                    entry = (data, sche_samp_rate, enhance_cmvn, self._bn_snapshot(), self._rng_snapshot())
+                    entry = (data, sche_samp_rate, enhance_cmvn, self._bn_snapshot(), self._rng_snapshot(), self.aug_step)
                     errors = self.step(data, sche_samp_rate, enhance_cmvn)
                 pending = {k: v for k, v in errors.items() if k.startswith('train/') or k in ('grad_norm', 'aborts')}
                 pending['_read'] = self.start_read(pending)        # the copy is enqueued NOW, behind this step; read after the next one is enqueued
@@ -737,6 +755,8 @@ class JointTrainer(object):
         for o in (self.enhance_optimizer, self.asr_optimizer, self.gan_optimizer):
             if o is not None:
                 o.step_count -= 1
+        if self.spec_augment is not None:      # ... and must see the SpecAugment plan it saw
+            self.aug_step -= 1
 
     def recover_aborted_step(self, entry, mine):
         """Called for a step whose update the device-side gate refused.  ``mine``: give-ups counted on this device in it.  If there were any
@@ -756,10 +776,14 @@ class JointTrainer(object):
         if self.isGAN:
             for b, s in zip(self.gan_model.buffers(), bn):
                 b.copy_(s)
+        counted = self.aug_step                # every step enqueued so far, a held one behind this one included
         self._uncount_step()
+        if len(entry) > 5:
+            self.aug_step = entry[5]           # the SpecAugment plan the aborted attempt drew, whatever was enqueued behind it
         self._acknowledge_aborts()
         with stepwise_kernels():
             vals = self.to_floats({k: v for k, v in self.step(data, rate, cmvn).items() if k.startswith('train/') or k in ('grad_norm', 'aborts')})
+        self.aug_step = counted                # the repeat counts once; ``fit`` takes the held step back before it runs it again
         gn, again = vals.pop('grad_norm', 0.0), int(vals.pop('aborts', 0.0))
         if rdist.any_rank(1 if (again or not math.isfinite(gn)) else 0):
             raise lib.Re2eError('a step that a persistent kernel had aborted is not finite with the launch-per-step kernels either (grad norm %r)' % gn)
@@ -813,6 +837,8 @@ class JointTrainer(object):
         # the dropout mask stream: the BASE seed (opt.seed) and the index of the next mask -- not the writing rank's own stream seed, which
         # every replica would otherwise inherit on resume (the index is the same on all ranks: they make the same calls); not an upstream key
         st['dropout_state'] = {'base_seed': int(getattr(self.opt, 'seed', 1234)), 'call': int(ops.dropout_state()[1])}
+        if self.spec_augment is not None:      # the SpecAugment plans continue where they stopped; not an upstream key, written only with the option
+            st['spec_augment_step'] = int(self.aug_step)
         return st
 
     @staticmethod
@@ -856,6 +882,7 @@ class JointTrainer(object):
             if o.kind == 'adam' and 'lr' in package:
                 g['lr'] = float(package['lr'])
         self.restore_dropout(package)
+        self.aug_step = int(package.get('spec_augment_step', 0))
         return (int(package.get('epoch', 0)), int(package.get('iters', 0)) - 1, float(package.get('best_loss', float('inf'))),
                 float(package.get('best_acc', 0.0)))
 

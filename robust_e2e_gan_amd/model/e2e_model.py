@@ -123,10 +123,20 @@ class E2E(ModelBase):
             if prev:
                 self.train()
 
-    def forward(self, inputs, targets, input_sizes, target_sizes, scheduled_sampling_rate=0.0):
-        """-> (loss_ctc, loss_att, acc)   (e2e_model.py:169-202)"""
+    @staticmethod
+    def _augment(x, aug, ilens, branches=1):
+        """SpecAugment (ops.spec_augment) on the features entering the encoder; ``aug``: a ``data.spec_augment.Plan`` with one row per
+        utterance, whose lengths are the batch's.  ``branches`` = 2: the same rows for both halves of a 2B batch."""
+        if [int(v) for v in aug.rows[:, 0]] != [int(v) for v in ilens]:
+            raise Re2eError('the SpecAugment plan was drawn for other lengths than the batch has')
+        return ops.spec_augment(x, aug.twice() if branches == 2 else aug)
+
+    def forward(self, inputs, targets, input_sizes, target_sizes, scheduled_sampling_rate=0.0, aug=None):
+        """-> (loss_ctc, loss_att, acc)   (e2e_model.py:169-202).  ``aug``: None, or the SpecAugment plan of this batch (training only)."""
         xpad = to_cuda(self, inputs)
         ilens = lens_list(input_sizes)
+        if aug is not None:
+            xpad = self._augment(xpad, aug, ilens)
         ys = self._split_targets(targets, target_sizes)
         h_tm, hlens = self.enc.forward_tm(xpad, ilens)
         # CTC and the attention decoder only share the encoder output: with a filler stream available (trainers.StepStreams, JointTrainer) the
@@ -163,20 +173,23 @@ class ShareE2E(E2E):
     one 2B batch, losses come from the enhanced branch exactly as E2E.forward, contexts are the
     encoder states of the valid frames of each branch."""
 
-    def encode_clean(self, clean_feat, cmvn, input_sizes=None):
+    def encode_clean(self, clean_feat, cmvn, input_sizes=None, aug=None):
         """Clean-branch CMVN + VGG conv stack, to be enqueued on a SIDE stream while the enhancer's recurrent chain
         occupies the main stream (the clean branch does not depend on the enhancer).  Returns a handle for
-        ``forward(..., clean_branch=handle)``."""
+        ``forward(..., clean_branch=handle)``.  ``aug``: the SpecAugment plan ``forward`` is given as well -- both branches take the SAME
+        rows, after CMVN, so that the clean and enhanced contexts stay frame-aligned for the CORAL term."""
         cln = to_cuda(self, clean_feat)
         if cmvn is not None:
             cln = ops.cmvn_pair(cln, None, to_cuda(self, cmvn).float().contiguous())
+        if aug is not None:
+            cln = self._augment(cln, aug, lens_list(input_sizes))
         h = self.enc.enc1.conv_stack(cln, input_sizes)
         ev = torch.cuda.Event()
         ev.record()
         return h, ev
 
     def forward(self, clean_feat, enhance_feat, targets, input_sizes, target_sizes, scheduled_sampling_rate=0.0, cmvn=None,
-                clean_branch=None, context_loss=None):
+                clean_branch=None, context_loss=None, aug=None):
         enh = to_cuda(self, enhance_feat)
         cln = to_cuda(self, clean_feat)
         ilens = lens_list(input_sizes)
@@ -187,7 +200,10 @@ class ShareE2E(E2E):
             # the two branches share only the recurrent stack: conv stacks separately (possibly on different streams),
             # then ONE (T', 2B, .) tensor for the BLSTMP so that the sequential chain is paid once
             h_cln, ev = clean_branch
-            h_enh = self.enc.enc1.conv_stack(ops.cmvn_pair(enh, None, cm) if cm is not None else enh, ilens)
+            x_enh = ops.cmvn_pair(enh, None, cm) if cm is not None else enh
+            if aug is not None:                # (the clean branch took the same plan in ``encode_clean``)
+                x_enh = self._augment(x_enh, aug, ilens)
+            h_enh = self.enc.enc1.conv_stack(x_enh, ilens)
             torch.cuda.current_stream().wait_event(ev)
             h_cln.record_stream(torch.cuda.current_stream())
             if torch.is_grad_enabled() and h_cln.requires_grad:
@@ -205,6 +221,8 @@ class ShareE2E(E2E):
             ops.mark('  shared BLSTMP fwd done')
         else:
             x2 = ops.cmvn_pair(enh, cln, cm) if cm is not None else torch.cat([enh, cln], 0)
+            if aug is not None:
+                x2 = self._augment(x2, aug, ilens, branches=2)
             h_tm2, hl2 = self.enc.forward_tm(x2, ilens + ilens)           # (T', 2B, E)
         hlens = hl2[:B]
         hpad2 = ops.transpose01(h_tm2)                                     # (2B, T', E)

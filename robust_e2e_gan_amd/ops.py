@@ -2730,3 +2730,7 @@ class Linear2BiasFn(torch.autograd.Function):
 
 def linear_2bias(x, W, b1, b2):
     return Linear2BiasFn.apply(x, W, b1, b2)
+
+
+# SpecAugment on the features entering the encoder (csrc/specaug.hip): ops.SpecAugmentFn / ops.spec_augment, kept in a module of their own
+from .specaug_op import SpecAugmentFn, spec_augment  # noqa: E402,F401

@@ -10,5 +10,6 @@ class TrainOptions(BaseOptions):
                                    ('--start_epoch', int, 0), ('--iters', int, 0), ('--epochs', int, 30), ('--shuffle_epoch', int, -1),
                                    ('--grad-clip', float, 5), ('--num-save-attention', int, 3), ('--num-saved-specgram', int, 3),
                                    ('--validate_freq', int, 8000), ('--print_freq', int, 500), ('--best_acc', float, 0),
-                                   ('--best_loss', float, float('inf'))]:
+                                   ('--best_loss', float, float('inf')),
+                                   ('--spec_augment', str, None)]:      # 'W,F,nF,T,nT' (data/spec_augment.py); not an upstream flag
             self.parser.add_argument(flag, type=typ, default=default)

@@ -16,9 +16,11 @@ import os
 import torch
 
 from . import lib, ops
+from . import dist as rdist
+from .data import spec_augment
 from .dist import GradSync
 from .joint_train import _LOSS_KIND
-from .model.e2e_common import set_requires_grad
+from .model.e2e_common import lens_list, set_requires_grad
 from .model.gan_model import GANLoss
 from .optim import FlatOptimizer
 
@@ -200,18 +202,50 @@ class EnhanceGanTrainer(object):
 
 
 class AsrTrainer(object):
-    """asr_train.py:118-131: E2E (CTC + attention) on pre-computed fbank features."""
+    """asr_train.py:118-131: E2E (CTC + attention) on pre-computed fbank features.  With ``opt.spec_augment`` ('W,F,nF,T,nT',
+    data/spec_augment.py) every training step augments its features on the device (ops.spec_augment) by a plan drawn from
+    (opt.seed, the trainer's own step counter, rank)."""
 
     def __init__(self, opt, asr_model):
         self.opt, self.asr_model = opt, asr_model
         self.optimizer = make_optimizer(opt, asr_model)
         self.asr_model.dec.return_acc_tensor = True
         self.streams = StepStreams()
+        self.spec_augment = spec_augment.parse(getattr(opt, 'spec_augment', None))
+        self.aug_step = 0          # steps whose plan has been drawn: part of ``state()``; ``_uncount_step`` takes one back
+
+    def _draw_aug(self, input_sizes, fdim):
+        """The SpecAugment plan of the step about to run (None without ``opt.spec_augment``), and count the step."""
+        if self.spec_augment is None:
+            return None
+        aug = spec_augment.Plan.draw(int(getattr(self.opt, 'seed', 1234)), self.aug_step, rdist.rank(), lens_list(input_sizes), fdim, self.spec_augment)
+        self.aug_step += 1
+        return aug
+
+    def _uncount_step(self):
+        """A step that is run again must see the plan it saw: take its count back."""
+        if self.spec_augment is not None:
+            self.aug_step -= 1
+
+    def state(self):
+        """What a checkpoint needs of this trainer besides ``opt``: the model and the augmentation's step counter."""
+        st = {'asr_state_dict': self.asr_model.state_dict()}
+        if self.spec_augment is not None:
+            st['spec_augment_step'] = int(self.aug_step)
+        return st
+
+    def load_state(self, package):
+        self.asr_model.load_state_dict(package['asr_state_dict'])
+        self.aug_step = int(package.get('spec_augment_step', 0))
 
     def step(self, data, sche_samp_rate=0.0):
         fbank_features, targets, input_sizes, target_sizes = data[2], data[3], data[4], data[5]
+        aug = self._draw_aug(input_sizes, fbank_features.shape[-1])
         with self.streams.step() as st:
-            loss_ctc, loss_att, acc = self.asr_model(fbank_features, targets, input_sizes, target_sizes, sche_samp_rate)[:3]
+            if aug is None:
+                loss_ctc, loss_att, acc = self.asr_model(fbank_features, targets, input_sizes, target_sizes, sche_samp_rate)[:3]
+            else:
+                loss_ctc, loss_att, acc = self.asr_model(fbank_features, targets, input_sizes, target_sizes, sche_samp_rate, aug=aug)[:3]
             loss = self.opt.mtlalpha * loss_ctc.view(()) + (1 - self.opt.mtlalpha) * loss_att
             self.optimizer.zero_grad()
             loss.backward()
