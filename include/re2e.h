@@ -48,7 +48,7 @@ typedef struct ihipStream_t* re2e_stream_t; /* == hipStream_t */
 /* ABI version of this header: bumped whenever an entry point is added or a signature changes (positional arguments carry no
  * names across the boundary).  re2e_version() returns the value the library was built with; a binding written for another value
  * must refuse to call (robust_e2e_gan_amd/lib.py load()). */
-#define RE2E_ABI_VERSION 338
+#define RE2E_ABI_VERSION 339
 int re2e_version(void);
 const char* re2e_last_error(void);
 /* 1 when device 0 is gfx950, 0 when another arch, <0 on HIP error. */
@@ -828,6 +828,34 @@ int re2e_wlm_multilevel_fix(const float* lsm, const float* wlm_logprobs, int n, 
                             const int* wid, int N, const float* clm_prev, const float* log_y_prev, const int* labels, int Vc,
                             int space, int eos, int word_unk, int word_eos, float subwordlm_weight, float log_oov_penalty,
                             int open_vocab, float* log_y, float* clm_out, re2e_stream_t stream);
+
+/* ---- N-gram (ARPA back-off) LMs in the beam search (model/ngram.py; NgramCharacterKenLM, extlm.py:46-72 upstream; csrc/ngram.hip) ----
+ * The model is flat arrays on the device: N nodes, node 0 the root (the empty context), one node per n-gram of length 1 .. order-1.  Per
+ * node: bo[N] its back-off weight, bo_node[N] the node of its longest proper suffix that is a node (the root for the root), succ_off[N+1]
+ * its successors as entries succ_off[k] .. succ_off[k+1]-1 of succ_label (ascending inside a node), succ_logp and succ_next (nsucc entries
+ * each; succ_next = the node of the longest suffix of context.label that is a node).  The root's successors are the dense rows uni_logp[V],
+ * uni_next[V]; its CSR list is empty.  All values are natural logarithms in fp32.  order: 1 .. 8 (a back-off chain has at most order nodes,
+ * the root included; chains are followed for at most 8).  No workspace; any n; every element of every output is written.
+ * re2e_ngram_step, one search position.  Row r < n: s = state_in[r] (state_in == NULL: the root) advances by x[r]: along s, bo_node[s], ..,
+ * root the first node that has x[r] among its successors (binary search; the root has every label) gives state_out[r] = that entry's next.
+ * Then with d0 = state_out[r], d_{i+1} = bo_node[d_i]: lp_out[r][v] = (bo[d0] + .. + bo[d_{j-1}]) + logp_j(v), j the first level of that
+ * chain that holds v; the back-offs are added in fp32 from the deep end, then the log-probability in one more fp32 addition (level 0:
+ * 0 + logp), so a row's bits depend on nothing but its state and label.  att (n,V) and comb_out (n,V) go together (both NULL or neither):
+ * comb_out = att + lm_weight * lp_out, the product rounded to fp32, then the sum (e2e_decoder.py:272).  A state outside [0, N), a label
+ * outside [0, V) or an index read from the tables that falls outside its array: that row is NaN in lp_out (and comb_out) and -1 in
+ * state_out, never an out-of-range access; other rows are not affected.  One workgroup per row and 4096 labels. */
+int re2e_ngram_step(const float* uni_logp, const int* uni_next, const float* bo, const int* bo_node, const int* succ_off,
+                    const int* succ_label, const float* succ_logp, const int* succ_next, int N, int nsucc, int V, int order,
+                    const int* state_in, const int* x, int n, const float* att, float lm_weight, int* state_out, float* lp_out,
+                    float* comb_out, re2e_stream_t stream);
+/* The summed log-probability of S label sequences (rescoring, perplexity): labels (S, Lmax) int32, lens[S] in [0, Lmax].  Sequence q starts
+ * from the context [eos] (node uni_next[eos]); its labels are scored in ascending position, then eos when append_eos != 0; every term is
+ * the fp32 value re2e_ngram_step gives that label, the terms are added in double: total_out[q] (S doubles on the device).  A length or a
+ * label out of range gives NaN.  One thread per sequence. */
+int re2e_ngram_score_seqs(const float* uni_logp, const int* uni_next, const float* bo, const int* bo_node, const int* succ_off,
+                          const int* succ_label, const float* succ_logp, const int* succ_next, int N, int nsucc, int V, int order,
+                          const int* labels, int Lmax, const int* lens, int S, int eos, int append_eos, double* total_out,
+                          re2e_stream_t stream);
 
 /* ---- N3 beam pruning on the device (csrc/beamsearch.hip), several utterances per launch.  The nh rows of a position are grouped by
  * utterance: utterance u owns rows seg_off_dev[u] .. seg_off_dev[u+1]-1 (U+1 offsets; max_seg_rows = the largest group, known to the host).

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # RE2E_LIB selects another build of the same C ABI (A/B measurements of kernel changes inside one GPU session)
 LIB_PATH = os.environ.get('RE2E_LIB') or os.path.join(_HERE, 'libre2e_hip.so')
-ABI_VERSION = 338    # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
+ABI_VERSION = 339    # include/re2e.h RE2E_ABI_VERSION this table was written for (checked against the library in load())
 
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_LRELU, ACT_SIGMOID, ACT_SIGMOID_MASK_MUL = range(6)
 LOSS_L2, LOSS_L1, LOSS_SMOOTH_L1, LOSS_BCE = range(4)
@@ -176,6 +176,8 @@ SIGNATURES = {
     're2e_wlm_softmax_cumsum': (I, [P, I, I, P, I, P, P]),
     're2e_wlm_lookahead': (I, [P, I, I, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, F, I, P, P]),
     're2e_wlm_multilevel_fix': (I, [P, P, I, I, P, P, P, I, P, P, P, I, I, I, I, I, F, F, I, P, P, P]),
+    're2e_ngram_step': (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, P, I, P, F, P, P, P, P]),
+    're2e_ngram_score_seqs': (I, [P, P, P, P, P, P, P, P, I, I, I, I, P, I, P, I, I, I, P, P]),
     're2e_beam_prune': (I, [P, I, I, P, P, P, I, I, I, P, P, P, P, P, P, Z, P]),
     're2e_align_counts_workspace_bytes': (Z, [P, I, P, P, I, I]),
     're2e_align_counts': (I, [P, P, I, L, P, P, P, I, L, I, I, I, P, P, P, L, P, Z, P]),

@@ -153,7 +153,8 @@ class Decoder(torch.nn.Module):
 
     def _check_decode_lm(self, rnnlm, fstlm, device):
         """What recognize_beam and recognize_beam_batch accept as a decode-time LM: a ClassifierWithState over an RNNLM, over an FSRNNLM
-        (model/fsrnn.py) or over a word-level LM of model/extlm.py (LookAheadWordLM, MultiLevelLM), shallow fusion only."""
+        (model/fsrnn.py), over a word-level LM of model/extlm.py (LookAheadWordLM, MultiLevelLM) or over an n-gram LM (model/ngram.py NgramLM),
+        shallow fusion only."""
         if fstlm is not None:
             raise Re2eError('decode-time LM: only RNNLM shallow fusion (rnnlm=ClassifierWithState(RNNLM(...))) is supported; '
                             'n-gram / FST LMs (fstlm) are out of scope')
@@ -161,10 +162,11 @@ class Decoder(torch.nn.Module):
             from .extlm import LookAheadWordLM, MultiLevelLM
             from .fsrnn import FSRNNLM
             from .lm import RNNLM, ClassifierWithState
+            from .ngram import NgramLM
             if self.fusion in ('deep_fusion', 'cold_fusion'):
                 raise Re2eError("decode-time LM: only shallow fusion is supported; fusion=%r changes the trained decoder and is out of scope"
                                 % self.fusion)
-            if not isinstance(rnnlm, ClassifierWithState) or not isinstance(rnnlm.predictor, (RNNLM, FSRNNLM, LookAheadWordLM, MultiLevelLM)):
+            if not isinstance(rnnlm, ClassifierWithState) or not isinstance(rnnlm.predictor, (RNNLM, FSRNNLM, LookAheadWordLM, MultiLevelLM, NgramLM)):
                 raise Re2eError('decode-time LM: only a ClassifierWithState over an RNNLM, an FSRNNLM, a LookAheadWordLM or a MultiLevelLM is '
                                 'supported (shallow fusion); n-gram LMs and %s are out of scope' % type(rnnlm).__name__)
             pred, V = rnnlm.predictor, self.output.weight.shape[0]
@@ -172,6 +174,8 @@ class Decoder(torch.nn.Module):
                 labels, lm_device, what = pred.n_vocab, pred.lo.weight.device, 'RNNLM'
             elif isinstance(pred, FSRNNLM):
                 labels, lm_device, what = pred.n_vocab, pred.out.weight.device, 'FSRNNLM'
+            elif isinstance(pred, NgramLM):
+                labels, lm_device, what = pred.n_vocab, pred.device, 'NgramLM'
             else:
                 labels, lm_device, what = pred.subword_dict_size, pred.device, type(pred).__name__
                 if any(prm.device != lm_device for prm in pred.parameters()):

@@ -20,7 +20,7 @@ per call over a nested dict tree, with a softmax and cumsum over the word vocabu
 ``ARBITER_PATH`` swaps in the same predictors over torch ops on device tensors (softmax, cumsum, log_softmax) with a per-row Python walk
 of the flat tree: the tests' arbiter and the timing baseline (tools/bench_recog_wordlm.py), not a user option.
 
-Out of scope: NgramCharacterKenLM (kenlm), training."""
+NgramCharacterKenLM (extlm.py:46-72 upstream) is model/ngram.py here: ARPA back-off models on kernels of their own.  Out of scope: training."""
 import math
 
 import numpy as np

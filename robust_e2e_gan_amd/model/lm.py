@@ -12,7 +12,9 @@ weights through registers once.  ``COMPOSED_PATH`` swaps in the same arithmetic 
 (tools/bench_recog_lm.py), not a user option.
 
 Word-level LMs (LookAheadWordLM, MultiLevelLM: model/extlm.py here) are predictors over one or two RNNLMs; they return log-probabilities
-(``normalized``) and take the labels the search holds on the host (``host_labels``, the ``labels=`` of ``predict_combined``).
+(``normalized``) and take the labels the search holds on the host (``host_labels``, the ``labels=`` of ``predict_combined``).  N-gram
+back-off LMs (the reference's NgramCharacterKenLM / --kenlm) are model/ngram.py: ``NgramLM`` is a predictor over flat ARPA tables, one
+launch per position, which also returns the shallow-fusion sum (``forward_combined``).
 
 Training (lm_train.py, ``train`` / ``evaluate`` below).  A truncated-BPTT window of T steps x B rows runs as ONE pass,
 ``RNNLM.forward_seq``: embedding -> dropout -> the W_ih product of all T*B rows (both biases in its epilogue) -> the recurrence
@@ -26,7 +28,8 @@ per step as its recurrence (tools/bench_lm_train.py).
 
 Out of scope (refused with Re2eError where they can be asked for): the FS-RNN LM in ``train`` (--lm-type fsrnnlm is trained by
 model/fsrnn.py, not by this function; ``ClassifierWithState`` and ``evaluate`` take an FSRNNLM predictor as they take an RNNLM), training on
-several GPUs or on the CPU, n-gram / FST LMs (NgramCharacterKenLM), deep and cold fusion."""
+several GPUs or on the CPU, FST LMs (model/fstlm.py upstream) and n-gram LMs in KenLM's binary format (ARPA files: model/ngram.py), deep and
+cold fusion."""
 import logging
 import os
 
@@ -241,6 +244,8 @@ class ClassifierWithState(torch.nn.Module):
         """``predict`` plus, when ``att`` (n, V) is given, ``att + lm_weight * log_probs`` (the shallow-fusion score of
         e2e_decoder.py:272, product and sum each rounded to fp32) from the same pass over the rows: (state, log_probs, combined).
         ``labels``: the labels of ``x`` as a host array, for the predictors that branch on them (``host_labels``: model/extlm.py)."""
+        if hasattr(self.predictor, 'forward_combined'):          # model/ngram.py NgramLM: the sum comes out of the step's own launch
+            return self.predictor.forward_combined(state, x, att, lm_weight)
         if labels is not None and getattr(self.predictor, 'host_labels', False):
             state, z = self.predictor(state, x, labels=labels)
         else:

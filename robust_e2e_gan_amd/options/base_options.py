@@ -49,6 +49,10 @@ class BaseOptions(object):
         for flag in _BOOL_FLAGS:
             self.parser.add_argument(flag, action='store_true')
         self.parser.add_argument('--enhace_resume', dest='enhance_resume', type=str, help='alias: upstream typo (enhance_base_train.py:56)')
+        # --lmtype ngram (model/ngram.py; not upstream): the ARPA file is --kenlm, upstream's flag, or its alias --ngram-lm
+        self.parser.add_argument('--ngram-lm', dest='kenlm', type=str, help='alias of --kenlm: ARPA n-gram LM for --lmtype ngram')
+        self.parser.add_argument('--ngram-tokens', type=str, default='symbols', choices=['symbols', 'ids'],
+                                 help='tokens of the ARPA file: dictionary symbols, or decimal label ids (what the reference feeds kenlm)')
         self.initialized = True
 
     def parse(self, argv=None, save=True):

@@ -14,7 +14,9 @@ reference's loop, one ``recognize`` per utterance.  Only the n-best lists come b
 
 The filterbank CMVN is ``--fbank_cmvn`` if given, else ``exp_path/fbank_cmvn.npy`` (what the reference reads), else
 ``exp_path/enhance_cmvn.npy`` (what joint_train writes).  LM widths are read from the LM checkpoint's tensor shapes (the reference hard-codes
-650 / 300, which does not fit the recipe's own LMs).  ``--nj`` is accepted and ignored; FST / n-gram LMs are refused."""
+650 / 300, which does not fit the recipe's own LMs).  ``--lmtype ngram --kenlm FILE`` (alias ``--ngram-lm``) decodes with an ARPA back-off
+model (model/ngram.py; ``--ngram-tokens symbols|ids`` says what the file's tokens are; the tables are cached beside the file as FILE.npz).
+``--nj`` is accepted and ignored; FST LMs (--lmtype fstlm --fstlm-path) and binary KenLM files are refused."""
 import json
 import os
 
@@ -96,6 +98,12 @@ def build_lm(opt, char_list, device):
             word = _rnnlm_of(_state_dict(opt.word_rnnlm), opt.word_rnnlm)
             lm = ClassifierWithState(MultiLevelLM(word.predictor, lm.predictor, word_dict, char_dict) if lm is not None
                                      else LookAheadWordLM(word.predictor, word_dict, char_dict))
+    elif opt.lmtype == 'ngram':
+        from .model.ngram import NgramLM, load_tables
+        path = opt.kenlm                                    # --kenlm or its alias --ngram-lm
+        if not path:
+            raise Re2eError('--lmtype ngram needs the ARPA file: --kenlm PATH (the reference\'s flag) or --ngram-lm PATH')
+        lm = ClassifierWithState(NgramLM(load_tables(path, char_list, getattr(opt, 'ngram_tokens', 'symbols'))))
     elif opt.lmtype == 'fsrnnlm' and opt.rnnlm:
         from .model.fsrnn import FSRNNLM
         sd = _state_dict(opt.rnnlm)
