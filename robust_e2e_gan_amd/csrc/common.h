@@ -145,10 +145,11 @@ __device__ __forceinline__ void block_topk256(float* row, int n, int k, int* out
   }
 }
 
+// torch.tanh / torch.relu / F.leaky_relu(0.2) / torch.sigmoid, NaN and +-inf included: a NaN stays a NaN (fmaxf(v, 0) would drop it), ReLU(-inf) = 0
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
     case RE2E_ACT_TANH: return tanhf_(v);
-    case RE2E_ACT_RELU: return fmaxf(v, 0.f);
+    case RE2E_ACT_RELU: return v < 0.f ? 0.f : v;
     case RE2E_ACT_LRELU: return v > 0.f ? v : 0.2f * v;
     case RE2E_ACT_SIGMOID: return sigmoidf_(v);
     default: return v;

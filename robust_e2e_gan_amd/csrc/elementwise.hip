@@ -403,13 +403,15 @@ __device__ __forceinline__ float loss_elem(float d, int kind) {
 __device__ __forceinline__ float loss_grad(float d, int kind) {
   if (kind == RE2E_LOSS_L2) return 2.f * d;
   if (kind == RE2E_LOSS_L1) return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-  return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f);
+  return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : (d < 0.f ? -1.f : d));     // a NaN difference stays a NaN, as in smooth_l1_loss_backward (L1: sign(NaN) = 0, as torch)
 }
 // RE2E_LOSS_BCE: nn.BCELoss on probabilities (gan_model.py:157-160 with --no_lsgan): -(t log a + (1-t) log(1-a)) with both
-// logarithms clamped at -100, gradient (a - t) / max(a (1-a), 1e-12) -- ATen's binary_cross_entropy forward / backward.
+// logarithms clamped at -100, gradient (a - t) / max(a (1-a), 1e-12) -- ATen's binary_cross_entropy forward / backward.  The clamps
+// are selects: a NaN probability gives a NaN loss, which the NaN gate of the joint step must see (fmaxf would report 100 for it).
+__device__ __forceinline__ float clamp_log(float x) { return x < -100.f ? -100.f : x; }
 __device__ __forceinline__ float loss_elem2(float a, float t, int kind) {
   if (kind != RE2E_LOSS_BCE) return loss_elem(a - t, kind);
-  return -(t * fmaxf(logf(a), -100.f) + (1.f - t) * fmaxf(logf(1.f - a), -100.f));
+  return -(t * clamp_log(logf(a)) + (1.f - t) * clamp_log(logf(1.f - a)));
 }
 __device__ __forceinline__ float loss_grad2(float a, float t, int kind) {
   if (kind != RE2E_LOSS_BCE) return loss_grad(a - t, kind);

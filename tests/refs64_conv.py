@@ -11,6 +11,8 @@ from it on a given input.  For the Winograd families that fp32 yardstick is an e
 ``CONV_CASES`` holds one row per kernel form the plans (re2e_conv_plan: csrc/igemm.hip plan_conv_layer / plan_conv) can name on a 256-CU
 chip, keyed by ``form_key``, plus the sub-forms the Winograd files branch on below the plan (``sub``); tests/test_refs64_conv_cpu.py
 checks that the table is closed under a sweep of the plans.
+
+Every input here is finite.  What the same forms make of a NaN or an infinity in x or dz is tests/refs64_nonfinite.py's subject (poison_conv).
 """
 import collections
 

@@ -14,6 +14,8 @@ tests/test_refs64_gemm_cpu.py checks that the table is closed under a sweep of t
 and mask boundaries of each family.  The K-sliced batches (gemm_kslices, gemm_kslices_tn) have no C entry point of their own: they are
 covered through the F(2x2,4x4) rows of tests/test_conv_kernels_gpu.py and left out here.  The mask epilogue is swept and run on all three operand forms:
 re2e_gemm takes it in every form (ops.py asks for it on the enhancer's x W^T alone); its rows are the (b, t) frames of the OUTPUT.
+
+Every input here is finite.  What the same forms make of a NaN or an infinity in A is tests/refs64_nonfinite.py's subject (poison_dense).
 """
 import collections
 import math

@@ -71,9 +71,11 @@ def _canary(n, seed):
     return torch.randn(n, generator=torch.Generator().manual_seed(seed))
 
 
-def _run(lib, row):
-    """One call of the row's entry point on fresh buffers -> dict(C=(physical rows, N) [, mask_out]) on the CPU, after the canary checks."""
-    case, _ = _refs(_key(row))
+def _run(lib, row, case=None):
+    """One call of the row's entry point on fresh buffers -> dict(C=(physical rows, N) [, mask_out]) on the CPU, after the canary checks.
+    case: other inputs of the row's shape than its own (tests/test_nonfinite_kernels_gpu.py)."""
+    if case is None:
+        case, _ = _refs(_key(row))
     M, N, K = row.M, row.N, row.K
     lda, ldb, ldc = R.leading_dims(row)
     oa, ob, oc = row.off
